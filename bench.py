@@ -8,7 +8,11 @@ kernel launch + one border gather launch for the whole batch).  Frames are the s
 with N GPUs every rank (one process per GPU) holds its own batch and there is no data-path
 collective -- the only communication is the barrier and the MAX over ranks of the elapsed time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--config C2|C3|C4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--config C2|C3|C4] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line.  Everything else the
+benchmark measures or checks runs with --full only, after the timed region: the self-check against the reference's known
+answers, the shader-clock pass, the VALU pair probe, the border kernels alone, the host-to-host records and the CPU baseline.
 
 How N > 1 starts (frames shard, nothing is exchanged, so any of these is the same measurement):
   * under a launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`, the driver's form):
@@ -24,7 +28,7 @@ Rank 0 prints ONE JSON line (see the task contract): value = Mpix/s over all ran
   "roofline"     -- dominant (periodic-interior) kernel: algorithmic HBM bytes / its mean launch
                     duration measured with hipEvents on the launch stream, vs the 8 TB/s peak;
                     also the un-fused fp32 VALU fraction, the roof that actually binds;
-  "cpu_baseline" -- the CPU oracle (port of the reference opt=0 path) timed on this host's cores
+  "cpu_baseline" -- (--full) the CPU oracle (port of the reference opt=0 path) timed on this host's cores
                     on a bounded sample of the same workload (rank 0, N=1 only).
 """
 from __future__ import annotations
@@ -770,6 +774,47 @@ def self_check(torch, config, fmt, dst_t, ddims):
             "source": f"tests/golden/kat.json [{rec['name']}] (reference opt=0 on the Appendix-A LCG frame, seed 12345)"}
 
 
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: float32 samples in all (64 MB with room for the .npy headers)
+DUMP_SEED = 2024
+
+
+def dump_positions(frames, w, h, n):
+    """Which visible samples of one output plane of the batch --dump-outputs writes: all of them, in (frame, row, column) order,
+    when n >= frames * h * w; otherwise n positions drawn with a fixed seed (the same for every run, whatever the build), sorted.
+    Flat indices into the (frames, h, w) array of visible samples."""
+    import numpy as np
+    total = frames * h * w
+    if n >= total:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, n, dtype=np.int64))
+
+
+def dump_outputs(torch, out_dir, dst_t, ddims, fmt, dst_shift=0):
+    """--dump-outputs: what the timed path computed in its last step, i.e. the visible part of every output plane of the batch
+    (padding excluded) as float32.  DIR/plane<i>.npy has shape (frames, h, w) when the whole batch fits in DUMP_BUDGET_BYTES;
+    otherwise DIR/plane<i>_sample.npy holds the samples at dump_positions(...), the budget shared among the planes by size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frames = int(dst_t[0].shape[0])
+    sizes = [frames * w * h for (w, h) in ddims]
+    budget = DUMP_BUDGET_BYTES // 4
+    whole = sum(sizes) <= budget
+    sb = fmt.sample_bytes
+    for i, (t, (w, h)) in enumerate(zip(dst_t, ddims)):
+        pos = dump_positions(frames, w, h, sizes[i] if whole else budget * sizes[i] // sum(sizes))
+        f, rest = np.divmod(pos, h * w)
+        y, x = np.divmod(rest, w)
+        # byte offsets of the samples in the padded device tensor (rows start dst_shift bytes in), gathered on the device
+        off = f * (t.stride(0) * sb) + y * (t.stride(1) * sb) + x * sb + dst_shift
+        off_t = through_pinned_to_device(torch, torch.from_numpy(off))
+        got = t.view(torch.uint8).reshape(-1)[off_t[:, None] + torch.arange(sb, device=off_t.device)]
+        vals = through_pinned_to_host(torch, got).numpy().reshape(-1).view(np.dtype(fmt.dtype)).astype(np.float32)
+        if whole:
+            np.save(os.path.join(out_dir, f"plane{i}.npy"), vals.reshape(frames, h, w))
+        else:
+            np.save(os.path.join(out_dir, f"plane{i}_sample.npy"), vals)
+
+
 def make_workload(pkg, torch, config, frames, device, seed, lcg_first=False):
     """Creates the filter and a batch of `frames` synthetic frames resident in HBM (random samples, not
     zeros: DVFS differs); returns (filter, step(), stream, format, output plane dims).  One step() =
@@ -829,6 +874,7 @@ def make_workload(pkg, torch, config, frames, device, seed, lcg_first=False):
 
     step.keepalive = (src_t, dst_t)
     step.checkable = lcg_first
+    step.dst_shift = dst_shift
     return flt, step, stream, fmt, ddims
 
 
@@ -853,12 +899,21 @@ def parse_args(argv=None):
     ap.add_argument("--knob", action="append", default=[], metavar="NAME=VALUE",
                     help="A/B / tuning knob of the library (include/jincresize_hip_test.h enum jinc_knob, lower-case name, e.g. quad_rg=8); "
                          "JINC_<NAME> environment variables are translated the same way -- the library itself reads no environment")
-    ap.add_argument("--no-self-check", action="store_true", help="skip the crc32 of frame 0's output against tests/golden/kat.json")
+    ap.add_argument("--no-self-check", action="store_true",
+                    help="leave the Appendix-A frame out of the batch, and with --full skip the crc32 of its output against tests/golden/kat.json")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the self-check, the shader-clock pass, the VALU pair probe, the border kernels "
+                         "alone, the host-to-host records and the CPU baseline (a plain run times the steps and prints the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy in float32 (rank 0's first device; at most 64 MB: "
+                         "the whole batch, or a fixed seeded sample of it)")
     args = ap.parse_args(argv)
     if args.config not in CONFIGS:
         ap.error(f"unknown --config {args.config}; choose from {', '.join(sorted(CONFIGS))}")
     if args.gpus < 1:
         ap.error("--gpus must be at least 1")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     return args
 
 
@@ -918,7 +973,7 @@ def main(argv=None):
     fmt_name, sw, sh, dw, dh, kw, default_frames = CONFIGS[args.config]
     strong = args.config == "C5"
     profiled = under_profiler()
-    quiet = profiled or args.no_clock_sampler   # no second dispatch, no probe kernels in a profile
+    quiet = profiled or args.no_clock_sampler or not args.full   # no second dispatch, no probe kernels in a profile or a plain run
 
     # one workload per device this process drives (one, unless --inproc): a plan replica, a batch resident in that device's
     # HBM, a stream.  Frames are the sharding unit; with C5 (one clip, strong scaling) shard k owns a contiguous run of them.
@@ -978,9 +1033,11 @@ def main(argv=None):
     per_ms, per_n, gat_ms, gat_n = flt.kernel_times()
     flt.set_profiling(False)
     dom_instance = flt.last_instance(0)   # the timed steps' interior kernel with its template arguments
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, loads[0]["step"].keepalive[1], ddims, fmt, loads[0]["step"].dst_shift)
     # every rank checks the batch of every device it drives; rank 0 reports its own detail and how many batches of the job failed
     check, bad_here = None, 0
-    if not args.simd_order or FORCE_SELF_CHECK:
+    if args.full and (not args.simd_order or FORCE_SELF_CHECK):
         for w in loads:
             if not getattr(w["step"], "checkable", False):
                 continue
@@ -1108,7 +1165,7 @@ def main(argv=None):
                        "untimed_spinup_ms_before_warmup": spin_ms, "parallelism": how_parallel,
                        "kernel": dom_name, "direct_kernel_premise": flt.direct_premise, "filter_size": fs, "plan_sets": info.num_sets,
                        "plan_bytes": int(info.plan_bytes), "under_profiler": profiled, "knobs": knobs_applied or None},
-            # frame 0 of the batch is the Appendix-A frame; its OUTPUT after the timed steps against the reference's crc32
+            # (--full) frame 0 of the batch is the Appendix-A frame; its OUTPUT after the timed steps against the reference's crc32
             "self_check": check["status"] if check else None, "self_check_detail": check,
             "roofline": {"bound": "hbm",   # the metric's wording (% of the HBM roofline); what BINDS the kernel is binding_roof below
                          "achieved": round(achieved_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1152,7 +1209,7 @@ def main(argv=None):
                          "border_ms_alone": round(border_alone_ms, 4) if border_alone_ms is not None else None},
         }
         line["e2e"] = None
-        if n_gpus == 1 and not args.no_e2e and not profiled:
+        if n_gpus == 1 and args.full and not args.no_e2e and not profiled:
             try:
                 line["e2e"] = e2e_record(pkg, args.config)
             except Exception as exc:  # noqa: BLE001  (a record next to the value, never a reason to lose the line)
@@ -1160,12 +1217,12 @@ def main(argv=None):
         # the host-to-host leg over ALL the job's devices, from this one process (rank 0), for every N -- the curve the
         # driver draws from `value` is the device-resident one; this record is the path with host threads and the links in it
         line["e2e_batch"] = None
-        if not args.no_e2e and not profiled:
+        if args.full and not args.no_e2e and not profiled:
             try:
                 line["e2e_batch"] = e2e_batch_record(pkg, args.config, n_gpus, pin_mode=E2E_MODE)
             except Exception as exc:  # noqa: BLE001
                 line["e2e_batch"] = {"error": str(exc)}
-        if n_gpus == 1 and not args.no_cpu_baseline and not profiled:
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline and not profiled:
             line["cpu_baseline"] = cpu_baseline(args.config)
         else:
             line["cpu_baseline"] = None

@@ -9,7 +9,7 @@ run() {
   envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done
   shift
-  line=$(env "${envs[@]}" python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-e2e "$@" 2>/dev/null | tail -1)
+  line=$(env "${envs[@]}" python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-e2e "$@" 2>/dev/null | tail -1)
   echo "$label $(echo "$line" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["config"]["workload"].split(":")[0], d["config"]["frames_per_step_per_gpu"], "value", d["value"], "ms/step", d["ms_per_step"], "kernel_ms", r["kernel_ms_per_launch"], "x", r["launches_per_step"], "step-interior", r["step_minus_interior_ms"], "border_alone", r["border_ms_alone"])')" >> $out
 }
 for round in 1 2; do

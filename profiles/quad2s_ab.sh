@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 for rep in 1 2 3; do
   for c in ${@:-C2 C1 C2H C2YUV}; do
     for k in 0 1; do
-      line=$(timeout 120 python bench.py --config $c --steps 30 --warmup 3 --no-cpu-baseline --no-e2e --no-clock-sampler --knob quad2s=$k 2>/dev/null | tail -1)
+      line=$(timeout 120 python bench.py --full --config $c --steps 30 --warmup 3 --no-cpu-baseline --no-e2e --no-clock-sampler --knob quad2s=$k 2>/dev/null | tail -1)
       python - "$c" "$k" "$line" <<'PY'
 import json, sys
 c, k, line = sys.argv[1:4]

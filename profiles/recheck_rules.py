@@ -6,7 +6,7 @@ per cent of level -- this is the tool that says which ones a given box would set
 
     python profiles/recheck_rules.py [out.log]            (through gpurun, from the repository root)
 
-Every run is a child process (`bench.py --steps 20 --no-cpu-baseline --no-e2e --no-clock-sampler`) with the A/B knob in its environment."""
+Every run is a child process (`bench.py --full --steps 20 --no-cpu-baseline --no-e2e --no-clock-sampler`) with the A/B knob in its environment."""
 import json
 import os
 import subprocess
@@ -67,7 +67,7 @@ def run(cfg, frames, variant):
     env = dict(os.environ)
     env.update(variant.get("env", {}))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--frames", str(frames), "--steps", "20", "--warmup", "3",
-           "--no-cpu-baseline", "--no-e2e", "--no-clock-sampler"] + variant.get("args", [])
+           "--full", "--no-cpu-baseline", "--no-e2e", "--no-clock-sampler"] + variant.get("args", [])
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300).stdout.strip().splitlines()
     line = json.loads(out[-1])
     return line["value"], line["roofline"]["kernel"]

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 for rep in 1 2; do
   for c in C3 T6; do
     for k in 1 1016 1032 1064; do
-      line=$(timeout 120 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --no-clock-sampler --knob rows_pair=$k 2>/dev/null | tail -1)
+      line=$(timeout 120 python bench.py --full --config $c --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --no-clock-sampler --knob rows_pair=$k 2>/dev/null | tail -1)
       python - "$c" "$k" "$line" <<'PY'
 import json, sys
 c, k, line = sys.argv[1:4]

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,7 +26,7 @@ def test_bench_under_torch_distributed_run_with_one_rank(gpu_pkg, config, extra)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", config, *extra,
-           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e"]
+           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -56,7 +57,7 @@ QUICK = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no
 
 def test_bench_started_plainly_runs_the_clip_config(gpu_pkg):
     """`python bench.py --gpus 1 --config C5 --steps 3`, no launcher, no environment."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C5", *QUICK], cwd=ROOT, env=_plain_env(),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C5", *QUICK, "--full"], cwd=ROOT, env=_plain_env(),
                        capture_output=True, text=True, timeout=300)
     d = _one_line(r)
     assert d["n_gpus"] == 1 and d["scaling"] == "strong" and d["value"] > 0
@@ -73,13 +74,13 @@ def test_bench_self_check_fails_loudly_when_the_output_is_wrong(gpu_pkg):
     a few pixels of C1, and bench.py (which skips the check for that switch) is asked to check anyway."""
     r = subprocess.run([sys.executable, "-c",
                         "import sys, bench; bench.FORCE_SELF_CHECK = True; bench.main(sys.argv[1:])",
-                        "--config", "C1", "--frames", "8", "--simd-order", "2", *QUICK], cwd=ROOT, env=_plain_env(), capture_output=True, text=True, timeout=300)
+                        "--config", "C1", "--frames", "8", "--simd-order", "2", *QUICK, "--full"], cwd=ROOT, env=_plain_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 1 and "SELF-CHECK FAILED" in r.stderr and not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
 @pytest.mark.parametrize("config,frames", [("C3", "2"), ("C4", "4")])
 def test_bench_checks_the_other_baseline_configs(gpu_pkg, config, frames):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--frames", frames, *QUICK], cwd=ROOT, env=_plain_env(),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--frames", frames, *QUICK, "--full"], cwd=ROOT, env=_plain_env(),
                        capture_output=True, text=True, timeout=600)
     d = _one_line(r)
     assert d["self_check"] == "ok", d["self_check_detail"]
@@ -111,3 +112,36 @@ def test_bench_under_a_launcher_with_the_store_for_the_barrier(gpu_pkg):
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C1", "--frames", "64", "--sync", "store", *QUICK]
     d = _one_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300))
     assert d["config"]["sync"] == "store" and d["config"]["launch"] == "launcher" and d["value"] > 0
+
+
+@pytest.mark.parametrize("frames", ["8", "40"], ids=["whole_batch", "seeded_sample"])
+def test_a_plain_run_dumps_what_its_last_step_computed(gpu_pkg, O, tmp_path, frames):
+    """`--dump-outputs DIR` without --full: the timed steps, the line (no self-check, no records beside it) and the output planes of
+    the last step as float32 -- where the batch holds the Appendix-A frame, exactly the oracle's output for it."""
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C1", "--frames", frames, "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)], cwd=ROOT, env=_plain_env(), capture_output=True, text=True, timeout=300)
+    d = _one_line(r)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["self_check"] is None and d["e2e"] is None and d["e2e_batch"] is None and d["cpu_baseline"] is None
+    assert d["roofline"]["shader_clock_ghz"] is None and d["roofline"]["border_ms_alone"] is None
+    import bench
+    fmt_name, sw, sh, dw, dh, kw, _ = bench.CONFIGS["C1"]
+    want = O.OracleFilter(O.FORMATS[fmt_name], sw, sh, dw, dh, **kw).get_frame(O.lcg_frame(O.FORMATS[fmt_name], sw, sh))[0][:dh, :dw]
+    B = int(frames)
+    if B * dw * dh * 4 <= bench.DUMP_BUDGET_BYTES:
+        assert os.listdir(out) == ["plane0.npy"]
+        got = np.load(out / "plane0.npy")
+        assert got.dtype == np.float32 and got.shape == (B, dh, dw)
+        for pos in bench.check_positions(B):
+            assert np.array_equal(got[pos], want.astype(np.float32)), pos
+    else:
+        assert os.listdir(out) == ["plane0_sample.npy"]
+        got = np.load(out / "plane0_sample.npy")
+        assert got.dtype == np.float32 and got.nbytes <= bench.DUMP_BUDGET_BYTES
+        idx = bench.dump_positions(B, dw, dh, bench.DUMP_BUDGET_BYTES // 4)
+        f, rest = np.divmod(idx, dw * dh)
+        y, x = np.divmod(rest, dw)
+        lcg = np.isin(f, bench.check_positions(B))
+        assert got.shape == idx.shape and lcg.sum() > 100_000
+        assert np.array_equal(got[lcg], want[y[lcg], x[lcg]].astype(np.float32))
