@@ -27,7 +27,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JINC_LIB") or os.path.join(_HERE, "lib", "libjincresize_hip.so")  # JINC_LIB: A/B runs against another build
 SIMD_ORDER_ISA_PATH = os.path.join(_HERE, "lib", "kernel_simdorder-gfx950.s")  # the one unit with (explicit) fused multiply-adds
-ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
+ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
                        "kernel_quasi_exact_fs9", "kernel_quasi_lane_fs7", "kernel_quasi_lane_fs9")]
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip.h")
 TEST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip_test.h")  # introspection, knobs, hooks
@@ -77,7 +77,7 @@ ARG_BITS = {"src_left": 1 << 0, "src_top": 1 << 1, "src_width": 1 << 2, "src_hei
             "quant_y": 1 << 5, "tap": 1 << 6, "blur": 1 << 7, "cplace": 1 << 8, "threads": 1 << 9, "opt": 1 << 10,
             "initial_capacity": 1 << 11, "initial_factor": 1 << 12}
 
-EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_filter_create", "jinc_filter_free", "jinc_filter_output_info",
+EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_filter_create", "jinc_filter_create_ex", "jinc_batch_create_ex", "jinc_debug_convert_half", "jinc_filter_free", "jinc_filter_output_info",
            "jinc_filter_chroma_location", "jinc_filter_set_chroma_location_mode", "jinc_filter_get_frame", "jinc_filter_process_device", "jinc_filter_sync",
            "jinc_alias_args", "jinc_filter_num_tables", "jinc_filter_plan_info", "jinc_filter_plan_pixel",
            "jinc_filter_plan_dump", "jinc_filter_plan_runs", "jinc_filter_plan_set", "jinc_filter_lut", "jinc_filter_set_kernel_mode", "jinc_filter_set_border_strips", "jinc_filter_interior_kernel", "jinc_filter_last_kernel",
@@ -105,6 +105,9 @@ def lib():
         L.jinc_filter_create.restype = C.c_int
         L.jinc_filter_create.argtypes = [C.POINTER(VideoInfo), C.POINTER(Args), C.c_int, C.POINTER(C.c_void_p),
                                          C.c_char_p, C.c_size_t]
+        L.jinc_filter_create_ex.restype = C.c_int
+        L.jinc_filter_create_ex.argtypes = [C.POINTER(VideoInfo), C.POINTER(Args), C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                            C.c_char_p, C.c_size_t]
         L.jinc_filter_free.restype = None
         L.jinc_filter_free.argtypes = [C.c_void_p]
         L.jinc_filter_output_info.argtypes = [C.c_void_p, C.POINTER(VideoInfo)]
@@ -150,6 +153,7 @@ def lib():
         L.jinc_filter_last_kernel.argtypes = [C.c_void_p, C.c_int]
         L.jinc_filter_last_kernel.restype = C.c_char_p
         L.jinc_debug_convert.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int]
+        L.jinc_debug_convert_half.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.jinc_filter_set_profiling.argtypes = [C.c_void_p, C.c_int]
         L.jinc_filter_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                                C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -166,6 +170,8 @@ def lib():
         L.jinc_shard_device.argtypes = [C.c_int, C.c_int]
         L.jinc_batch_create.argtypes = [C.POINTER(VideoInfo), C.POINTER(Args), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                         C.c_char_p, C.c_size_t]
+        L.jinc_batch_create_ex.argtypes = [C.POINTER(VideoInfo), C.POINTER(Args), C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         L.jinc_batch_devices.argtypes = [C.c_void_p]
         L.jinc_batch_device_of_frame.argtypes = [C.c_void_p, C.c_int]
         L.jinc_batch_process.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _I4, C.c_void_p, _I4]
@@ -395,6 +401,21 @@ def debug_convert(sums: np.ndarray, dtype, peak: float, device: int = 0) -> np.n
     return out
 
 
+def debug_convert_half(sums: np.ndarray, device: int = 0) -> np.ndarray:
+    """The half planes' fp32 -> binary16 store path applied to `sums` on the device (test hook); returns float16."""
+    sums = np.ascontiguousarray(sums, dtype=np.float32)
+    out = np.zeros(sums.shape, dtype=np.uint16)
+    rc = lib().jinc_debug_convert_half(sums.ctypes.data, out.ctypes.data, sums.size, device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return out.view(np.float16)
+
+
+# Sample types of jinc_filter_create_ex / jinc_batch_create_ex
+SAMPLE_DEFAULT = 0
+SAMPLE_FLOAT16 = 1
+
+
 # ---- clip / format model (what an AviSynth+ host would provide) -----------------------------------
 @dataclass(frozen=True)
 class Format:
@@ -404,13 +425,20 @@ class Format:
     sub_w: int = 0
     sub_h: int = 0
     rgb: bool = False
+    half: bool = False  # IEEE binary16 samples (bits 16, 2 bytes): created with SAMPLE_FLOAT16; bits == 32 stays fp32
 
     @property
     def sample_bytes(self) -> int:
         return 1 if self.bits == 8 else (2 if self.bits <= 16 else 4)
 
     @property
+    def sample_type(self) -> int:
+        return SAMPLE_FLOAT16 if self.half else SAMPLE_DEFAULT
+
+    @property
     def dtype(self):
+        if self.half:
+            return np.float16
         return {1: np.uint8, 2: np.uint16, 4: np.float32}[self.sample_bytes]
 
     def plane_dims(self, w: int, h: int) -> List[Tuple[int, int]]:
@@ -435,6 +463,13 @@ def _fmts() -> Dict[str, Format]:
         out[f"RGBP{tag}"] = Format(f"RGBP{tag}", bits, 3, rgb=True)
         out[f"RGBAP{tag}"] = Format(f"RGBAP{tag}", bits, 4, rgb=True)
     out["YV12"], out["YV16"], out["YV24"], out["YV411"] = out["YUV420P8"], out["YUV422P8"], out["YUV444P8"], out["YUV411P8"]
+    # half-precision float planes (beyond the reference: VapourSynth GRAYH / YUV4xxPH / RGBH)
+    out["YH"] = Format("YH", 16, 1, half=True)
+    for fam, sw, sh in (("420", 1, 1), ("422", 1, 0), ("444", 0, 0), ("411", 2, 0)):
+        out[f"YUV{fam}PH"] = Format(f"YUV{fam}PH", 16, 3, sw, sh, half=True)
+        out[f"YUVA{fam}PH"] = Format(f"YUVA{fam}PH", 16, 4, sw, sh, half=True)
+    out["RGBPH"] = Format("RGBPH", 16, 3, rgb=True, half=True)
+    out["RGBAPH"] = Format("RGBAPH", 16, 4, rgb=True, half=True)
     return out
 
 
@@ -517,8 +552,8 @@ class Batch:
         vi, a, self._keep = _build_args(fmt, width, height, target_width, target_height, -1, True, (True, True, True), None, kw)
         self._h = C.c_void_p()
         err = C.create_string_buffer(512)
-        rc = lib().jinc_batch_create(C.byref(vi), C.byref(a), int(ndevices), int(streams), int(register_host_buffers),
-                                     C.byref(self._h), err, len(err))
+        rc = lib().jinc_batch_create_ex(C.byref(vi), C.byref(a), fmt.sample_type, int(ndevices), int(streams), int(register_host_buffers),
+                                        C.byref(self._h), err, len(err))
         if rc != 0:
             raise JincError(rc, err.value.decode())
         self.dst_w, self.dst_h = int(target_width), int(target_height)
@@ -596,7 +631,7 @@ class Filter:
                                         cpu_flags, alias_taps, kw)
         self._h = C.c_void_p()
         err = C.create_string_buffer(512)
-        rc = lib().jinc_filter_create(C.byref(vi), C.byref(a), int(device), C.byref(self._h), err, len(err))
+        rc = lib().jinc_filter_create_ex(C.byref(vi), C.byref(a), fmt.sample_type, int(device), C.byref(self._h), err, len(err))
         if rc != 0:
             raise JincError(rc, err.value.decode())
         out = VideoInfo()

@@ -25,10 +25,37 @@ namespace {
 
 #define JINC_CONSTANT __attribute__((address_space(4)))
 
+// IEEE binary16 planes (PlaneIO::sample_kind == kSampleHalf): samples widen exactly to fp32 on load (v_cvt_f32_f16), the fp32 chain
+// is the float planes' one, and the result narrows under the default round mode (round to nearest even, v_cvt_f16_f32): overflow
+// to +-inf, subnormals and the sign of zero kept, no clamp -- float planes' semantics end to end.  (Never the packed
+// round-toward-zero conversion: it saturates at 65504 and rounds differently.)
+using half_t = _Float16;
+
+// Float-like samples (fp32 and binary16): no clamp, non-finite samples possible -- no zero-tap elision on frames that hold one.
+template <typename T>
+inline constexpr bool is_float_sample_v = std::is_same_v<T, float> || std::is_same_v<T, half_t>;
+
 template <typename T>
 __device__ __forceinline__ float to_float(T v) {
     return static_cast<float>(v);
 }
+
+// Bit 31 set when v is an infinity or a NaN (exponent field all ones: the biased field plus one carries into the sign bit);
+// 0 for integer samples.
+template <typename T>
+__device__ __forceinline__ uint32_t nonfinite_bit(T v) {
+    if constexpr (std::is_same_v<T, float>)
+        return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) + 0x00800000u;
+    else if constexpr (std::is_same_v<T, half_t>)
+        return ((static_cast<uint32_t>(__builtin_bit_cast(uint16_t, v)) & 0x7c00u) + 0x0400u) << 16;
+    else
+        return 0u;
+}
+
+__device__ __forceinline__ uint16_t half_bits(float r) { return __builtin_bit_cast(uint16_t, static_cast<half_t>(r)); }
+// The two binary16 samples of a dword (low half first) widened to fp32.
+__device__ __forceinline__ float half_lo(uint32_t w) { return static_cast<float>(__builtin_bit_cast(half_t, static_cast<uint16_t>(w))); }
+__device__ __forceinline__ float half_hi(uint32_t w) { return static_cast<float>(__builtin_bit_cast(half_t, static_cast<uint16_t>(w >> 16))); }
 
 // ref :581-582 -- clamp(result, 0, peak) then lrintf (round-half-even).  For every non-NaN input
 // v_med3_f32(r, 0, peak) equals the reference's "upper bound first, then lower" clamp; a NaN (only
@@ -52,10 +79,25 @@ __device__ __forceinline__ uint32_t round_pair_u16(float a, float b, float peak)
     return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, cb), __builtin_bit_cast(uint32_t, ca), 0x05040100u);
 }
 
+// Two binary16 samples as one dword, (a) in the low half: round_pair_u16's analogue for half planes (two v_cvt_f16_f32).
+__device__ __forceinline__ uint32_t round_pair_f16(float a, float b) {
+    return static_cast<uint32_t>(half_bits(a)) | (static_cast<uint32_t>(half_bits(b)) << 16);
+}
+// A pair of samples of type T packed into one dword (2-byte samples only).
+template <typename T>
+__device__ __forceinline__ uint32_t round_pair16(float a, float b, float peak) {
+    if constexpr (std::is_same_v<T, half_t>)
+        return round_pair_f16(a, b);
+    else
+        return round_pair_u16(a, b, peak);
+}
+
 template <typename T>
 __device__ __forceinline__ T convert_sample(float r, float peak) {
     if constexpr (std::is_same_v<T, float>)
         return r;
+    else if constexpr (std::is_same_v<T, half_t>)
+        return static_cast<half_t>(r);
     else if constexpr (std::is_same_v<T, uint8_t>)
         return static_cast<uint8_t>(round_sample_u8(r));
     else
@@ -77,6 +119,8 @@ template <typename T>
 __device__ __forceinline__ void store_sample_buf(BufferRsrc rsrc, uint32_t voffset, uint32_t soffset, float r, float peak) {
     if constexpr (std::is_same_v<T, float>)
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, r), rsrc, voffset, soffset, 0);
+    else if constexpr (std::is_same_v<T, half_t>)
+        __builtin_amdgcn_raw_buffer_store_b16(half_bits(r), rsrc, voffset, soffset, 0);
     else if constexpr (std::is_same_v<T, uint8_t>)
         __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(round_sample_u8(r)), rsrc, voffset, soffset, 0);
     else

@@ -240,7 +240,7 @@ void attach_rowpair(DeviceTable& t, jinc::PeriodicArgs& pa, int n, int ny, const
 void trim_periodic(const jinc::PlanePlan& p, DeviceTable& t, bool integer_samples) {
     t.trim_fs = 0;
     t.trim_nx = 0;
-    t.trim_needs_finite = !integer_samples;  // float planes: only frames without infinities / NaNs (dispatch.cpp, kernel_scan.hip)
+    t.trim_needs_finite = !integer_samples;  // float and half planes: only frames without infinities / NaNs (dispatch.cpp, kernel_scan.hip)
     if (!t.use_periodic) return;
     if (!knobs::flag(JINC_KNOB_TRIM, true)) return;  // A/B knob: TRIM = 0 keeps the full window
     const jinc::PeriodicArgs& pa = t.periodic;
@@ -1063,12 +1063,12 @@ void init_device(jinc_filter& f, int device) {
             for (int ph = 0; ph < 4; ++ph) sets.push_back(f.plans[i].set_ptr(f.tables[i].periodic.set[ph]));
             attach_quad(f.tables[i], f.tables[i].periodic, f.plans[i].fs, sets);
         }
-        trim_periodic(f.plans[i], f.tables[i], f.vi_in.component_size < 4);
+        trim_periodic(f.plans[i], f.tables[i], !f.float_samples());
         plan_quasi(f.plans[i], f.tables[i]);
         plan_direct(f.plans[i], f.tables[i]);
-        trim_direct(f.plans[i], f.tables[i], f.vi_in.component_size < 4);
-        plan_edge_columns(f.plans[i], f.tables[i], f.vi_in.component_size < 4);
-        plan_rowpair_rows(f.plans[i], f.tables[i], f.vi_in.component_size < 4);
+        trim_direct(f.plans[i], f.tables[i], !f.float_samples());
+        plan_edge_columns(f.plans[i], f.tables[i], !f.float_samples());
+        plan_rowpair_rows(f.plans[i], f.tables[i], !f.float_samples());
         plan_colpair(f.plans[i], f.tables[i]);
         plan_runs(f.plans[i], f.tables[i]);
         {   // every interior variant of a table must cover the same extent: the border frame is laid out once

@@ -192,10 +192,12 @@ struct Choice {
     const size_t* src_fs;
     const int nframes;
     const int sb;
+    const int rule_sb;  // sample size the rules see: half planes take the decisions of fp32 planes of the same geometry
     double call_samples = 0.0;  // output samples of the whole call
 
     Choice(const jinc_filter& filter, const int src_pitch_[4], const size_t src_fs_[4], int nframes_)
-        : f(filter), src_pitch(src_pitch_), src_fs(src_fs_), nframes(nframes_), sb(filter.vi_in.component_size) {
+        : f(filter), src_pitch(src_pitch_), src_fs(src_fs_), nframes(nframes_), sb(filter.vi_in.component_size),
+          rule_sb(filter.half ? 4 : filter.vi_in.component_size) {
         for (int i = 0; i < f.planecount; ++i) {
             const DeviceTable& t = f.tables[f.table_of_plane(i)];
             call_samples += static_cast<double>(t.plan.dst_w) * t.plan.dst_h;
@@ -315,7 +317,7 @@ struct Choice {
         // the 6-row x 7-column support exists for the quad2 form only: where that form is not what runs, the full window
         if (t.trim_nx != t.trim_fs && !(f.kernel_mode == 13 || (f.kernel_mode == 0 && quad2_fills(t)))) return false;
         // ... and the 8-row x 9-column one (chroma at tap 4) for ewa_periodic_quad2x8_kernel only
-        if (t.trim_nx != t.trim_fs && t.trim_fs == 8 && !(knobs::flag(JINC_KNOB_QUAD8, Rules::kQuad8) && quad2x8_chosen(t, f.vi_in.component_size))) return false;
+        if (t.trim_nx != t.trim_fs && t.trim_fs == 8 && !(knobs::flag(JINC_KNOB_QUAD8, Rules::kQuad8) && quad2x8_chosen(t, rule_sb))) return false;
         if (!t.trim_needs_finite) return true;
         // (Float planes: the trimmed launch is its own finite-sample scan -- launch_plane -- so what is left of the price is a cleared
         // flag set, a scan of the plane's rim and a second launch that returns at once: from kFloatTrimMinTaps taps per plane and call.
@@ -401,7 +403,7 @@ struct Choice {
         if (f.planecount == 1 && f.border_strips < 0) {
             const DeviceTable& t = f.tables[f.table_of_plane(0)];
             const bool edge_form = t.use_edge_cols && t.strips_ok && (f.kernel_mode == 0 || f.kernel_mode == 13) && trimmed(t) && quad_chosen(t) &&
-                                   (periodic_fs(t) == 6 || (periodic_fs(t) == 8 && quad2x8_chosen(t, f.vi_in.component_size))) &&
+                                   (periodic_fs(t) == 6 || (periodic_fs(t) == 8 && quad2x8_chosen(t, rule_sb))) &&
                                    knobs::flag(JINC_KNOB_EDGE_COLS, true) && knobs::geti(JINC_KNOB_ROWPAIR_SMALL, 0) != 1;
             if (edge_form) return taps * nframes >= Rules::kStripBorderMinTapsEdgeCols;
         }
@@ -438,6 +440,7 @@ void launch_plane(jinc_filter& f, const Choice& c, int i, const void* const src[
     io.nframes = nframes;
     if (pair) io.src_frame_stride = pair->src_stride, io.dst_frame_stride = pair->dst_stride, io.nframes = 2;
     io.sample_bytes = sb;
+    io.sample_kind = f.half ? jinc::kSampleHalf : 0;
     io.peak = f.peak;
     auto timed = [&](std::vector<EventPair>& sink, hipStream_t s, const char* what, auto&& launch) {
         EventPair ev;
@@ -581,7 +584,7 @@ void launch_plane(jinc_filter& f, const Choice& c, int i, const void* const src[
         // border frame: rows on kernel_direct.hip + columns on the gather kernel, or the gather kernel for all of it
         const bool strips = c.wants_border_strips() && t.strips_ok && c.direct_ok(t, i);
         edge_fused = strips && periodic && t.use_edge_cols && (f.border_strips < 0 || f.border_strips == 4) && (f.kernel_mode == 0 || f.kernel_mode == 13) && c.trimmed(t) &&
-                     c.quad_chosen(t) && (c.periodic_fs(t) == 6 || (c.periodic_fs(t) == 8 && c.quad2x8_chosen(t, sb))) &&
+                     c.quad_chosen(t) && (c.periodic_fs(t) == 6 || (c.periodic_fs(t) == 8 && c.quad2x8_chosen(t, c.rule_sb))) &&
                      knobs::flag(JINC_KNOB_EDGE_COLS, true) && knobs::geti(JINC_KNOB_ROWPAIR_SMALL, 0) != 1;  // (that knob sends the launch to the row-pair kernel)
         if (strips) {
             jinc::DirectArgs rs = t.row_strips;
@@ -723,7 +726,7 @@ void launch_plane(jinc_filter& f, const Choice& c, int i, const void* const src[
                     const int force_rg = knobs::geti(JINC_KNOB_QUAD_RG, 0);  // A/B knob: 8 / 4 forces full / half-height tiles of the quad forms
                     if (force_rg == 8) variant = 5;
                     if (force_rg == 4) variant = 6;
-                    if (pfs == 8 && c.quad2x8_chosen(t, sb)) variant = 7;  // two periods per lane
+                    if (pfs == 8 && c.quad2x8_chosen(t, c.rule_sb)) variant = 7;  // two periods per lane
                 }
                 if (c.trimmed(t) && t.trim_needs_finite) {
                     // float plane: which frames hold nothing but finite samples?  Those run on the trimmed support; the others

@@ -71,12 +71,22 @@ const char* jinc_last_error(void) { return g_last_error.c_str(); }
 
 int jinc_filter_create(const jinc_video_info* vi, const jinc_args* args, int device, jinc_filter** out, char* err,
                        size_t err_len) {
+    return jinc_filter_create_ex(vi, args, JINC_SAMPLE_DEFAULT, device, out, err, err_len);
+}
+
+int jinc_filter_create_ex(const jinc_video_info* vi, const jinc_args* args, int sample_type, int device, jinc_filter** out, char* err,
+                          size_t err_len) {
     if (out) *out = nullptr;
     if (err && err_len) err[0] = '\0';
     if (!vi || !args || !out) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     std::unique_ptr<jinc_filter> f(new (std::nothrow) jinc_filter());
     if (!f) return fail(JINC_ERR_NOMEM, "JincResize: out of memory.");
     int rc = guarded([&] {
+        if (sample_type != JINC_SAMPLE_DEFAULT && sample_type != JINC_SAMPLE_FLOAT16)
+            throw ArgError("JincResize: sample type must be JINC_SAMPLE_DEFAULT or JINC_SAMPLE_FLOAT16.");
+        if (sample_type == JINC_SAMPLE_FLOAT16 && (vi->bits_per_component != 16 || vi->component_size != 2))
+            throw ArgError("JincResize: half-precision float clips must have 16 bits per component and 2-byte samples.");
+        f->half = sample_type == JINC_SAMPLE_FLOAT16;
         configure(*f, *vi, *args);
         if (device >= 0) init_device(*f, device);
     });
@@ -363,6 +373,23 @@ int jinc_filter_kernel_times(jinc_filter* f, double* periodic_ms, int* periodic_
     });
 }
 
+int jinc_debug_convert_half(const float* sums, uint16_t* out, int n, int device) {
+    if (!sums || !out || n < 0) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        float* d_in = nullptr;
+        uint16_t* d_out = nullptr;
+        hip_check(hipMalloc(&d_in, sizeof(float) * (n + 1)), "hipMalloc");
+        hip_check(hipMalloc(&d_out, sizeof(uint16_t) * (n + 1)), "hipMalloc");
+        bounce_upload(d_in, sums, sizeof(float) * n, "upload of the sums");
+        hip_check(static_cast<hipError_t>(jinc::launch_debug_convert_half(d_in, d_out, n, nullptr)), "convert launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bounce_download(out, d_out, sizeof(uint16_t) * n, "download of the samples");
+        (void)hipFree(d_in);
+        (void)hipFree(d_out);
+    });
+}
+
 int jinc_debug_convert(const float* sums, void* out, int n, int sample_bytes, float peak, int device) {
     if (!sums || !out || n < 0 || (sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4))
         return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
@@ -454,6 +481,8 @@ double jinc_filter_periodic_taps(const jinc_filter* f, int table, int rows_kerne
 
 int jinc_filter_set_simd_order(jinc_filter* f, int order) {
     if (!f || order < 0 || order > 3) return fail(JINC_ERR_INVALID_ARG, "JincResize: SIMD order must be 0..3.");
+    if (f->half && order != 0)
+        return fail(JINC_ERR_UNSUPPORTED, "JincResize: SIMD-order modes do not exist for half-precision float clips (the reference has no half path).");
     f->simd_order = order;
     return JINC_OK;
 }

@@ -202,6 +202,9 @@ struct jinc_filter {
     int chroma_location_by_siting = -1;  // 0 / 1 / 2 by cplace: what the reference's source means to write
     int chroma_location_mode = 0;        // jinc_filter_set_chroma_location_mode
     float peak = 0.f;
+    bool half = false;  // JINC_SAMPLE_FLOAT16: IEEE binary16 samples (component_size 2); float planes' semantics
+    // Float-like samples (fp32 or binary16): no clamp, and the trimmed support only on frames whose samples are all finite.
+    bool float_samples() const { return half || vi_in.component_size == 4; }
     int planecount = 0;
     bool subsampled = false;
     jinc::JincLut lut;

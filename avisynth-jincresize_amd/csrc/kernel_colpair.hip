@@ -155,8 +155,8 @@ __global__ __launch_bounds__(256) void ewa_colpair_kernel(const ColPairArgs a, c
                 v = __builtin_amdgcn_cvt_pk_u8_f32(r[2], 2u, v);
                 v = __builtin_amdgcn_cvt_pk_u8_f32(r[3], 3u, v);
                 __builtin_amdgcn_raw_buffer_store_b32(v, drsrc, voff, 0, 0);
-            } else if constexpr (std::is_same_v<T, uint16_t>) {
-                const u32x2 v = {round_pair_u16(r[0], r[1], io.peak), round_pair_u16(r[2], r[3], io.peak)};
+            } else if constexpr (sizeof(T) == 2) {  // uint16_t, half_t
+                const u32x2 v = {round_pair16<T>(r[0], r[1], io.peak), round_pair16<T>(r[2], r[3], io.peak)};
                 __builtin_amdgcn_raw_buffer_store_b64(v, drsrc, voff, 0, 0);
             } else {
                 // (8-byte stores: a 16-byte store that is not 16-byte aligned does not put its dwords where they belong on this part)
@@ -202,7 +202,9 @@ int launch_colpair(const ColPairArgs& args, const PlaneIO& io, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (io.sample_bytes) {
         case 1: return launch_colpair_t<uint8_t>(args, io, s);
-        case 2: return launch_colpair_t<uint16_t>(args, io, s);
+        case 2:
+            if (io.sample_kind == kSampleHalf) return launch_colpair_t<half_t>(args, io, s);
+            return launch_colpair_t<uint16_t>(args, io, s);
         default: return launch_colpair_t<float>(args, io, s);
     }
 }

@@ -150,7 +150,9 @@ int launch_colstrip(const ColStripArgs& args, const PlaneIO& io, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (io.sample_bytes) {
         case 1: return launch_colstrip_t<uint8_t>(args, io, s);
-        case 2: return launch_colstrip_t<uint16_t>(args, io, s);
+        case 2:
+            if (io.sample_kind == kSampleHalf) return launch_colstrip_t<half_t>(args, io, s);
+            return launch_colstrip_t<uint16_t>(args, io, s);
         default: return launch_colstrip_t<float>(args, io, s);
     }
 }

@@ -23,7 +23,9 @@ template <int MODE>
 int launch_direct_mode(const DirectArgs& args, const PlaneIO& io, hipStream_t s) {
     switch (io.sample_bytes) {
         case 1: return launch_direct_sx<uint8_t, MODE>(args, io, s);
-        case 2: return launch_direct_sx<uint16_t, MODE>(args, io, s);
+        case 2:
+            if (io.sample_kind == kSampleHalf) return launch_direct_sx<half_t, MODE>(args, io, s);
+            return launch_direct_sx<uint16_t, MODE>(args, io, s);
         default: return launch_direct_sx<float, MODE>(args, io, s);
     }
 }
@@ -86,7 +88,9 @@ int launch_direct(const DirectArgs& args, const PlaneIO& io, void* stream) {
     }
     switch (io.sample_bytes) {
         case 1: JINC_WALK_BY_SX(u8)
-        case 2: JINC_WALK_BY_SX(u16)
+        case 2:
+            if (io.sample_kind == kSampleHalf) JINC_WALK_BY_SX(f16)
+            JINC_WALK_BY_SX(u16)
         default: JINC_WALK_BY_SX(f32)
     }
 #undef JINC_WALK_BY_SX
@@ -107,7 +111,9 @@ int launch_direct_runs(const DirectArgs& args, const PlaneIO& io, void* stream) 
     }
     switch (io.sample_bytes) {
         case 1: JINC_RUNS_SX(u8)
-        case 2: JINC_RUNS_SX(u16)
+        case 2:
+            if (io.sample_kind == kSampleHalf) JINC_RUNS_SX(f16)
+            JINC_RUNS_SX(u16)
         default: JINC_RUNS_SX(f32)
     }
 #undef JINC_RUNS_SX

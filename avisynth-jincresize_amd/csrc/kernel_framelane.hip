@@ -445,7 +445,9 @@ int launch_framelane(const FrameLaneArgs& args, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (args.io.sample_bytes) {
         case 1: return launch_fl_fs<uint8_t>(args, s);
-        case 2: return launch_fl_fs<uint16_t>(args, s);
+        case 2:
+            if (args.io.sample_kind == kSampleHalf) return launch_fl_fs<half_t>(args, s);
+            return launch_fl_fs<uint16_t>(args, s);
         default: return launch_fl_fs<float>(args, s);
     }
 }

@@ -14,6 +14,10 @@ struct FlPack<uint16_t> {
     using type = uint2;
 };
 template <>
+struct FlPack<half_t> {
+    using type = uint2;
+};
+template <>
 struct FlPack<float> {
     using type = float4;
 };
@@ -30,6 +34,8 @@ __device__ __forceinline__ typename FlPack<T>::type fl_pack(const float (&r)[4],
         w.x = round_sample(r[0], peak) | (round_sample(r[1], peak) << 16);
         w.y = round_sample(r[2], peak) | (round_sample(r[3], peak) << 16);
         return w;
+    } else if constexpr (std::is_same_v<T, half_t>) {
+        return make_uint2(round_pair_f16(r[0], r[1]), round_pair_f16(r[2], r[3]));
     } else {
         return make_float4(r[0], r[1], r[2], r[3]);
     }
@@ -100,7 +106,7 @@ template <typename T, int PS, int UF, int US>
 __device__ __forceinline__ void fl_stage(const FrameLaneArgs& a, const FlTile& t, char* tile, int row_pos, int col_pos, int lane,
                                          int wave, int nwaves) {
     constexpr int SB = static_cast<int>(sizeof(T));
-    using Raw = std::conditional_t<sizeof(T) == 4, uint32_t, T>;  // (samples travel as bits, one 32-bit register each)
+    using Raw = std::conditional_t<sizeof(T) == 4, uint32_t, std::conditional_t<sizeof(T) == 2, uint16_t, uint8_t>>;  // (samples travel as bits, one 32-bit register each)
     const int tw = t.tw, th = t.th;
     const int sh = tw <= 1 ? 0 : 32 - __builtin_clz(static_cast<unsigned>(tw - 1));  // lanes per row = 1 << sh >= tw
     const int lc = lane & ((1 << sh) - 1), lr = lane >> sh, rps = 64 >> sh;

@@ -40,6 +40,10 @@ __device__ __forceinline__ f32x2 flp_load(const char* p) {
         const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
         r.x = static_cast<float>(v & 0xffffu);
         r.y = static_cast<float>(v >> 16);
+    } else if constexpr (std::is_same_v<T, half_t>) {
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
+        r.x = half_lo(v);
+        r.y = half_hi(v);
     } else {
         r = *reinterpret_cast<const f32x2*>(p);
     }
@@ -295,7 +299,9 @@ int launch_framelane_pair(const FrameLaneArgs& args, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (args.io.sample_bytes) {
         case 1: return launch_flp_fs<uint8_t>(args, s);
-        case 2: return launch_flp_fs<uint16_t>(args, s);
+        case 2:
+            if (args.io.sample_kind == kSampleHalf) return launch_flp_fs<half_t>(args, s);
+            return launch_flp_fs<uint16_t>(args, s);
         default: return launch_flp_fs<float>(args, s);
     }
 }

@@ -293,7 +293,9 @@ int launch_framelane_sub(const FrameLaneArgs& args, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (args.io.sample_bytes) {
         case 1: return launch_sub_fs<uint8_t>(args, s);
-        case 2: return launch_sub_fs<uint16_t>(args, s);
+        case 2:
+            if (args.io.sample_kind == kSampleHalf) return launch_sub_fs<half_t>(args, s);
+            return launch_sub_fs<uint16_t>(args, s);
         default: return launch_sub_fs<float>(args, s);
     }
 }

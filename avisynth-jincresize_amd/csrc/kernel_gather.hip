@@ -319,10 +319,10 @@ __global__ void convert_kernel(const float* in, T* out, int n, float peak) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const BufferRsrc rsrc = make_rsrc(out, static_cast<uint32_t>(n) * sizeof(T));
-    if constexpr (std::is_same_v<T, uint16_t>) {  // the packed-pair kernels' path (round_pair_u16): elements 4k + 2 and 4k + 3 as one dword
+    if constexpr (sizeof(T) == 2) {  // the packed-pair kernels' path (round_pair16): elements 4k + 2 and 4k + 3 as one dword
         if ((i & 3) == 2 && i + 1 < n) {
-            const uint32_t v = round_pair_u16(in[i], in[i + 1], peak);
-            out[i] = static_cast<uint16_t>(v), out[i + 1] = static_cast<uint16_t>(v >> 16);
+            const uint32_t v = round_pair16<T>(in[i], in[i + 1], peak);
+            reinterpret_cast<uint16_t*>(out)[i] = static_cast<uint16_t>(v), reinterpret_cast<uint16_t*>(out)[i + 1] = static_cast<uint16_t>(v >> 16);
             return;
         }
         if ((i & 3) == 3) return;
@@ -343,6 +343,13 @@ int launch_debug_convert(const float* in, void* out, int n, int sample_bytes, fl
         case 2: hipLaunchKernelGGL(convert_kernel<uint16_t>, grid, block, 0, s, in, static_cast<uint16_t*>(out), n, peak); break;
         default: hipLaunchKernelGGL(convert_kernel<float>, grid, block, 0, s, in, static_cast<float*>(out), n, peak); break;
     }
+    return static_cast<int>(hipGetLastError());
+}
+
+int launch_debug_convert_half(const float* in, uint16_t* out, int n, void* stream) {
+    if (n <= 0) return 0;
+    const dim3 grid((n + 255) / 256), block(256);
+    hipLaunchKernelGGL(convert_kernel<half_t>, grid, block, 0, static_cast<hipStream_t>(stream), in, reinterpret_cast<half_t*>(out), n, 0.f);
     return static_cast<int>(hipGetLastError());
 }
 
@@ -392,7 +399,9 @@ int launch_gather(const DevicePlan& plan, const PlaneIO& io, const RectList& rec
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (io.sample_bytes) {
         case 1: return launch_gather_fs<uint8_t>(ga, total, s);
-        case 2: return launch_gather_fs<uint16_t>(ga, total, s);
+        case 2:
+            if (io.sample_kind == kSampleHalf) return launch_gather_fs<half_t>(ga, total, s);
+            return launch_gather_fs<uint16_t>(ga, total, s);
         default: return launch_gather_fs<float>(ga, total, s);
     }
 }

@@ -163,7 +163,7 @@ __device__ __forceinline__ void store_pair_buf(BufferRsrc rsrc, uint32_t voffset
         w = __builtin_amdgcn_cvt_pk_u8_f32(r.y, 1u, w);
         __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(w), rsrc, voffset, soffset, 0);
     } else {
-        __builtin_amdgcn_raw_buffer_store_b32(round_pair_u16(r.x, r.y, peak), rsrc, voffset, soffset, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(round_pair16<T>(r.x, r.y, peak), rsrc, voffset, soffset, 0);
     }
 }
 
@@ -1149,9 +1149,9 @@ __device__ __forceinline__ void store_quad_buf(BufferRsrc rsrc, uint32_t voffset
         else __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(w), rsrc, voffset, soffset, 0);
     } else {
         typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        const uint32_t lo = round_pair_u16(a.x, a.y, peak);
+        const uint32_t lo = round_pair16<T>(a.x, a.y, peak);
         if (b_ok) {
-            const u32x2 v = {lo, round_pair_u16(b.x, b.y, peak)};
+            const u32x2 v = {lo, round_pair16<T>(b.x, b.y, peak)};
             __builtin_amdgcn_raw_buffer_store_b64(v, rsrc, voffset, soffset, 0);
         } else {
             __builtin_amdgcn_raw_buffer_store_b32(lo, rsrc, voffset, soffset, 0);
@@ -1168,7 +1168,7 @@ __device__ __forceinline__ void store_quad_buf(BufferRsrc rsrc, uint32_t voffset
 // out carry zero coefficients (checked on the host).
 template <typename T>
 __device__ __forceinline__ bool edge_tile_of(const PeriodicArgs& a, int tile_x) {
-    if constexpr (std::is_same_v<T, float>) return false;  // (float planes: the border kernels, whatever the samples)
+    if constexpr (is_float_sample_v<T>) return false;  // (float and half planes: the border kernels, whatever the samples)
     return a.edge.coeffs != nullptr && ((a.edge.n[0] > 0 && tile_x == a.edge.tile_x[0]) || (a.edge.n[1] > 0 && tile_x == a.edge.tile_x[1]));
 }
 
@@ -1306,14 +1306,14 @@ __global__ __launch_bounds__(256, 6) void ewa_periodic_quad2_kernel(const Period
                 if (r < Cfg::kLdsRows && c < Cfg::kLdsCols) tile[r * Cfg::kLdsPitch + c] = nonfinite.take(staged[i][k]);
             }
         }
-        if constexpr (!std::is_same_v<T, float>) {
+        if constexpr (!is_float_sample_v<T>) {
             if (edge_tile) stage_edge_column<T, Cfg>(a, io, tile, tile_x, sbase, gx0, gy0, wave, lane);
         }
     }
     __syncthreads();
     const BufferRsrc drsrc = make_rsrc(static_cast<char*>(io.dst) + frame * io.dst_frame_stride,
                                        static_cast<uint32_t>(io.dst_pitch) * a.dst_h);  // wave-uniform
-    if constexpr (!std::is_same_v<T, float>) {
+    if constexpr (!is_float_sample_v<T>) {
         if (edge_tile) quad2_edge_columns<T, Cfg, 6, 7>(a, io, tile, tile_x, j0, wave, lane, drsrc);
     }
     const int ia = i0 + 2 * lane;  // the lane's first period
@@ -1572,14 +1572,14 @@ __global__ __launch_bounds__(256, 5) void ewa_periodic_quad2x8_kernel(const Peri
                 }
             }
         }
-        if constexpr (!std::is_same_v<T, float>) {
+        if constexpr (!is_float_sample_v<T>) {
             if (edge_tile) stage_edge_column<T, Cfg>(a, io, tile, tile_x, sbase, gx0, gy0, wave, lane);
         }
     }
     __syncthreads();
     const BufferRsrc drsrc = make_rsrc(static_cast<char*>(io.dst) + frame * io.dst_frame_stride,
                                        static_cast<uint32_t>(io.dst_pitch) * a.dst_h);  // wave-uniform
-    if constexpr (!std::is_same_v<T, float>) {
+    if constexpr (!is_float_sample_v<T>) {
         if (edge_tile) quad2_edge_columns<T, Cfg, 8, 9>(a, io, tile, tile_x, j0, wave, lane, drsrc);
     }
     const int ia = i0 + 2 * lane;
@@ -2008,7 +2008,9 @@ int launch_periodic(const PeriodicArgs& args, int fs, const PlaneIO& io, void* s
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (io.sample_bytes) {
         case 1: return launch_periodic_fs<uint8_t>(args, fs, io, s, variant);
-        case 2: return launch_periodic_fs<uint16_t>(args, fs, io, s, variant);
+        case 2:
+            if (io.sample_kind == kSampleHalf) return launch_periodic_fs<half_t>(args, fs, io, s, variant);
+            return launch_periodic_fs<uint16_t>(args, fs, io, s, variant);
         default: return launch_periodic_fs<float>(args, fs, io, s, variant);
     }
 }

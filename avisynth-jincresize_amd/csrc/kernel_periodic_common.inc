@@ -21,11 +21,11 @@ struct NonFinite {
     __device__ __forceinline__ NonFinite(const PeriodicArgs& a_, size_t frame_) : a(a_), frame(frame_) {}
     __device__ __forceinline__ float take(T v) {
         // (exponent 0xff: the biased field plus one carries into the sign bit)
-        if constexpr (std::is_same_v<T, float>) acc |= (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) + 0x00800000u;
+        if constexpr (is_float_sample_v<T>) acc |= nonfinite_bit(v);
         return to_float(v);
     }
     __device__ __forceinline__ ~NonFinite() {
-        if constexpr (std::is_same_v<T, float>) {
+        if constexpr (is_float_sample_v<T>) {
             if (a.run_when == kRunAllAndFlag && (acc & 0x80000000u)) const_cast<uint32_t*>(a.frame_flags)[frame] = 1u;  // (every writer writes 1)
         }
     }

@@ -273,7 +273,9 @@ int JINC_QUASI_ENTRY(const QuasiArgs& args, const PlaneIO& io, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (io.sample_bytes) {
         case 1: return launch_quasi_sx<uint8_t, JINC_QUASI_FS>(args, io, s);
-        case 2: return launch_quasi_sx<uint16_t, JINC_QUASI_FS>(args, io, s);
+        case 2:
+            if (io.sample_kind == kSampleHalf) return launch_quasi_sx<half_t, JINC_QUASI_FS>(args, io, s);
+            return launch_quasi_sx<uint16_t, JINC_QUASI_FS>(args, io, s);
         default: return launch_quasi_sx<float, JINC_QUASI_FS>(args, io, s);
     }
 }

@@ -1,4 +1,4 @@
-// kernel_scan.hip -- does a batch of float planes hold nothing but finite samples?
+// kernel_scan.hip -- does a batch of float (fp32 or binary16) planes hold nothing but finite samples?
 //
 // The periodic kernels may run float planes on the TRIMMED support (device_plan.cpp trim_periodic) only where every source
 // sample is finite: a tap whose coefficient is 0.0f contributes sample * 0 = +-0 and may be left out -- unless the sample
@@ -14,6 +14,14 @@ namespace {
 constexpr int kScanThreads = 256;
 constexpr int kScanRowsPerBlock = 8;
 
+// Sample of a float plane as its bits: fp32 (W = uint32_t) or binary16 (W = uint16_t, PlaneIO::sample_kind == kSampleHalf).
+template <typename W>
+__device__ __forceinline__ uint32_t nonfinite_sample(W v) {
+    constexpr uint32_t kExp = sizeof(W) == 4 ? 0x7f800000u : 0x7c00u;  // exponent all ones: infinity or NaN
+    return (static_cast<uint32_t>(v) & kExp) == kExp ? 1u : 0u;
+}
+
+template <typename W>
 __global__ __launch_bounds__(kScanThreads) void finite_scan_kernel(const char* __restrict__ base, uint32_t pitch, size_t frame_stride, int w,
                                                                    int h, uint32_t* __restrict__ flags) {
     const size_t frame = blockIdx.z;
@@ -23,15 +31,15 @@ __global__ __launch_bounds__(kScanThreads) void finite_scan_kernel(const char* _
     for (int r = 0; r < kScanRowsPerBlock; ++r) {
         const int y = y0 + r;
         if (y >= h) break;
-        const uint32_t* row = reinterpret_cast<const uint32_t*>(plane + static_cast<size_t>(y) * pitch);
-        for (int x = blockIdx.x * kScanThreads + threadIdx.x; x < w; x += gridDim.x * kScanThreads)
-            bad |= ((row[x] & 0x7f800000u) == 0x7f800000u) ? 1u : 0u;  // exponent all ones: infinity or NaN
+        const W* row = reinterpret_cast<const W*>(plane + static_cast<size_t>(y) * pitch);
+        for (int x = blockIdx.x * kScanThreads + threadIdx.x; x < w; x += gridDim.x * kScanThreads) bad |= nonfinite_sample(row[x]);
     }
     if (__builtin_amdgcn_ballot_w64(bad != 0) != 0 && (threadIdx.x & 63) == 0) flags[frame] = 1u;  // (every writer writes 1)
 }
 
 // The plane minus the rectangle [rx0, rx1) x [ry0, ry1): rows above and below it over the whole width, columns left and right of
 // it over its height.  A few thousand samples per frame: one workgroup per frame walks them.
+template <typename W>
 __global__ __launch_bounds__(kScanThreads) void finite_scan_outside_kernel(const char* __restrict__ base, uint32_t pitch, size_t frame_stride, int w,
                                                                            int h, int rx0, int ry0, int rx1, int ry1,
                                                                            uint32_t* __restrict__ flags) {
@@ -39,8 +47,7 @@ __global__ __launch_bounds__(kScanThreads) void finite_scan_outside_kernel(const
     const char* plane = base + frame * frame_stride;
     uint32_t bad = 0;
     auto check = [&](int x, int y) {
-        const uint32_t v = *reinterpret_cast<const uint32_t*>(plane + static_cast<size_t>(y) * pitch + static_cast<size_t>(x) * 4u);
-        bad |= ((v & 0x7f800000u) == 0x7f800000u) ? 1u : 0u;
+        bad |= nonfinite_sample(*reinterpret_cast<const W*>(plane + static_cast<size_t>(y) * pitch + static_cast<size_t>(x) * sizeof(W)));
     };
     const int tid = blockIdx.x * kScanThreads + threadIdx.x, nthreads = gridDim.x * kScanThreads;
     const int rows_above = ry0, rows_below = h - ry1, cols_left = rx0, cols_right = w - rx1, mid = ry1 - ry0;
@@ -59,7 +66,8 @@ int launch_finite_scan(const PlaneIO& io, int w, int h, uint32_t* flags, void* s
     if (w <= 0 || h <= 0 || io.nframes <= 0) return 0;
     const int bx = std::max(1, std::min(8, (w + kScanThreads * 4 - 1) / (kScanThreads * 4)));
     dim3 grid(bx, (h + kScanRowsPerBlock - 1) / kScanRowsPerBlock, io.nframes);
-    hipLaunchKernelGGL(finite_scan_kernel, grid, dim3(kScanThreads), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(io.sample_kind == kSampleHalf ? finite_scan_kernel<uint16_t> : finite_scan_kernel<uint32_t>, grid, dim3(kScanThreads), 0,
+                       static_cast<hipStream_t>(stream),
                        static_cast<const char*>(io.src), static_cast<uint32_t>(io.src_pitch), io.src_frame_stride, w, h, flags);
     return static_cast<int>(hipGetLastError());
 }
@@ -71,7 +79,8 @@ int launch_finite_scan_outside(const PlaneIO& io, int w, int h, int rx0, int ry0
     const long long outside = static_cast<long long>(w) * h - static_cast<long long>(rx1 - rx0) * (ry1 - ry0);
     if (outside <= 0) return 0;
     const int bx = static_cast<int>(std::max<long long>(1, std::min<long long>(16, outside / (kScanThreads * 16))));
-    hipLaunchKernelGGL(finite_scan_outside_kernel, dim3(bx, 1, io.nframes), dim3(kScanThreads), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(io.sample_kind == kSampleHalf ? finite_scan_outside_kernel<uint16_t> : finite_scan_outside_kernel<uint32_t>,
+                       dim3(bx, 1, io.nframes), dim3(kScanThreads), 0, static_cast<hipStream_t>(stream),
                        static_cast<const char*>(io.src), static_cast<uint32_t>(io.src_pitch), io.src_frame_stride, w, h, rx0, ry0, rx1, ry1, flags);
     return static_cast<int>(hipGetLastError());
 }

@@ -23,6 +23,8 @@ struct DevicePlan {
     int gather_period_x = 1, gather_period_y = 1;
 };
 
+constexpr int kSampleHalf = 1;
+
 // One plane of a batch of frames, device pointers, pitches/strides in bytes.
 struct PlaneIO {
     const void* src = nullptr;
@@ -30,7 +32,8 @@ struct PlaneIO {
     int src_pitch = 0, dst_pitch = 0;
     size_t src_frame_stride = 0, dst_frame_stride = 0;
     int nframes = 1;
-    int sample_bytes = 1;  // 1: uint8, 2: uint16, 4: float
+    int sample_bytes = 1;  // 1: uint8, 2: uint16 or binary16 (sample_kind), 4: float
+    int sample_kind = 0;   // kSampleHalf: IEEE binary16 samples (sample_bytes 2); else integer (1, 2 bytes) or fp32 (4 bytes)
     float peak = 255.f;    // clamp ceiling of integer planes (ref JincResize.cpp:582, :793)
 };
 
@@ -290,6 +293,7 @@ int last_direct_shape();
     int launch_direct_walk_##tag##_sx4(const DirectArgs&, const PlaneIO&, void* stream, int shape);
 JINC_DECLARE_DIRECT_WALK(u8)
 JINC_DECLARE_DIRECT_WALK(u16)
+JINC_DECLARE_DIRECT_WALK(f16)
 JINC_DECLARE_DIRECT_WALK(f32)
 #undef JINC_DECLARE_DIRECT_WALK
 int launch_direct_row_strips(const DirectArgs& args, const PlaneIO& io, void* stream);
@@ -303,6 +307,7 @@ int launch_direct_runs(const DirectArgs& args, const PlaneIO& io, void* stream);
     int launch_direct_runs_##tag##_sx4(const DirectArgs&, const PlaneIO&, void* stream);
 JINC_DECLARE_DIRECT_RUNS(u8)
 JINC_DECLARE_DIRECT_RUNS(u16)
+JINC_DECLARE_DIRECT_RUNS(f16)
 JINC_DECLARE_DIRECT_RUNS(f32)
 #undef JINC_DECLARE_DIRECT_RUNS
 
@@ -441,5 +446,7 @@ int launch_valu_pair_probe(float* out, int blocks, int iters, void* stream);
 
 // Test hook: applies the kernels' float -> sample conversion (clamp, round-half-even, store) to n sums.
 int launch_debug_convert(const float* in, void* out, int n, int sample_bytes, float peak, void* stream);
+// ... the binary16 stores of half planes (both the plain and the buffer-store paths, and the packed pair)
+int launch_debug_convert_half(const float* in, uint16_t* out, int n, void* stream);
 
 }  // namespace jinc

@@ -39,6 +39,7 @@ template <typename T> constexpr const char* type_name();
 template <> constexpr const char* type_name<unsigned char>() { return "unsigned char"; }
 template <> constexpr const char* type_name<unsigned short>() { return "unsigned short"; }
 template <> constexpr const char* type_name<float>() { return "float"; }
+template <> constexpr const char* type_name<_Float16>() { return "_Float16"; }
 
 }  // namespace knobs
 }  // namespace jinc

@@ -135,6 +135,23 @@ JINC_API const char *jinc_last_error(void);
 JINC_API int jinc_filter_create(const jinc_video_info *vi, const jinc_args *args, int device,
                                 jinc_filter **out, char *err, size_t err_len);
 
+/* Sample types beyond the reference.  JINC_SAMPLE_DEFAULT: the type bits_per_component says (8 .. 16: unsigned integers,
+ * 32: fp32), exactly what jinc_filter_create does.  JINC_SAMPLE_FLOAT16: IEEE binary16 planes (VapourSynth GRAYH, YUV4xxPH,
+ * RGBH), which need bits_per_component == 16 and component_size == 2.  A half plane is defined by the fp32 path: every
+ * sample widens exactly to fp32 (subnormals, infinities and NaNs included), the result is what the library computes for
+ * that fp32 plane (same plan, same un-fused (ly, lx) chain, the trimmed support only on frames whose samples are all
+ * finite), and it narrows to binary16 with round-to-nearest-even: |r| >= 65520 becomes an infinity, subnormal results
+ * and the sign of zero are kept, nothing is clamped.  The reference has no half formats; its SIMD-order modes
+ * (jinc_filter_set_simd_order 1 .. 3) do not exist for half filters. */
+#define JINC_SAMPLE_DEFAULT 0
+#define JINC_SAMPLE_FLOAT16 1
+
+/* jinc_filter_create with a sample type: jinc_filter_create(...) is jinc_filter_create_ex(..., JINC_SAMPLE_DEFAULT, ...).
+ * A sample type other than the two above, or JINC_SAMPLE_FLOAT16 with bits_per_component != 16 or component_size != 2,
+ * is JINC_ERR_INVALID_ARG with a "JincResize: ..." message.  device = -1 builds a host-only plan, as for create. */
+JINC_API int jinc_filter_create_ex(const jinc_video_info *vi, const jinc_args *args, int sample_type, int device,
+                                   jinc_filter **out, char *err, size_t err_len);
+
 /* free_JincResize (ref :632-647). NULL is allowed. */
 JINC_API void jinc_filter_free(jinc_filter *f);
 
@@ -255,6 +272,9 @@ typedef struct jinc_batch jinc_batch;
 JINC_API int jinc_shard_device(int frame, int ndevices);
 JINC_API int jinc_batch_create(const jinc_video_info *vi, const jinc_args *args, int ndevices, int streams_per_device,
                                int register_host_buffers, jinc_batch **out, char *err, size_t err_len);
+/* jinc_batch_create with a sample type (JINC_SAMPLE_DEFAULT / JINC_SAMPLE_FLOAT16, as jinc_filter_create_ex). */
+JINC_API int jinc_batch_create_ex(const jinc_video_info *vi, const jinc_args *args, int sample_type, int ndevices,
+                                  int streams_per_device, int register_host_buffers, jinc_batch **out, char *err, size_t err_len);
 JINC_API int jinc_batch_devices(const jinc_batch *b);
 JINC_API int jinc_batch_set_affinity(jinc_batch *b, int on);
 JINC_API int jinc_batch_device_cpus(const jinc_batch *b, int device_index, int *cpus, int max_cpus);

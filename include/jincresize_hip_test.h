@@ -234,6 +234,9 @@ JINC_API int jinc_filter_set_border_overlap(jinc_filter *f, int enable);
  * ref :581-584) on `n` caller-supplied fp32 sums on device `device` and returns the samples
  * (sample_bytes 1, 2 or 4).  Lets tests probe ties, bounds, NaN and infinities directly. */
 JINC_API int jinc_debug_convert(const float *sums, void *out, int n, int sample_bytes, float peak, int device);
+/* ... the binary16 store path of half filters (JINC_SAMPLE_FLOAT16: round to nearest even, overflow to +-inf, no clamp),
+ * the plain, buffer and packed-pair stores alike, on `n` fp32 values; out receives the binary16 bit patterns. */
+JINC_API int jinc_debug_convert_half(const float *sums, uint16_t *out, int n, int device);
 
 /* Test hook: 1 when the device's buffer range check covers the scalar offset of buffer loads (the premise of the
  * direct kernel's bounded segment fetches; probed once per device, the direct kernel is not used where it fails), 0 when

@@ -246,7 +246,8 @@ void VS_CC jinc_vs_create(const VSMap* in, VSMap* out, void* userData, VSCore* c
     jvi.is_rgb = vi->format.colorFamily == cfRGB;
     jvi.sub_w = vi->format.subSamplingW;
     jvi.sub_h = vi->format.subSamplingH;
-    if (vi->format.sampleType == stFloat && vi->format.bitsPerSample != 32) return fail("JincResize: half-precision float clips are not supported.");
+    // half-precision float clips (GRAYH, YUV4xxPH, RGBH) run as JINC_SAMPLE_FLOAT16 planes; the library checks 16 bits / 2 bytes
+    const bool half = vi->format.sampleType == stFloat && vi->format.bitsPerSample == 16;
 
     jinc_args a;
     std::memset(&a, 0, sizeof a);
@@ -308,7 +309,9 @@ void VS_CC jinc_vs_create(const VSMap* in, VSMap* out, void* userData, VSCore* c
 
     char msg[512];
     jinc_filter* filter = nullptr;
-    if (jinc_filter_create(&jvi, &final_args, jinc_pick_device(), &filter, msg, sizeof msg) != JINC_OK) return fail(msg);
+    if (jinc_filter_create_ex(&jvi, &final_args, half ? JINC_SAMPLE_FLOAT16 : JINC_SAMPLE_DEFAULT, jinc_pick_device(), &filter, msg, sizeof msg) !=
+        JINC_OK)
+        return fail(msg);
 
     Instance* d = new Instance;
     d->node = node;
@@ -320,7 +323,9 @@ void VS_CC jinc_vs_create(const VSMap* in, VSMap* out, void* userData, VSCore* c
     d->chroma_location = jinc_filter_chroma_location(filter);
     // JINCRESIZE_SIMD_ORDER=auto | 1 | 2 | 3: as in the AviSynth shell -- the summation order of the path the reference's
     // ladder would pick for this `opt` on this CPU (ref :897-899) instead of the opt=0 result; default off
-    if (const char* e = std::getenv("JINCRESIZE_SIMD_ORDER")) {
+    // (half clips: the reference has no half path whose order could be reproduced -- the hook does not apply to them)
+    const char* simd_env = half ? nullptr : std::getenv("JINCRESIZE_SIMD_ORDER");
+    if (const char* e = simd_env) {
         int order = 0;
         if (std::strcmp(e, "auto") == 0) {
             const int opt = (final_args.defined & JINC_ARG_OPT) ? final_args.opt : -1;
