@@ -381,6 +381,19 @@ void trim_periodic(const jinc::PlanePlan& p, DeviceTable& t, bool integer_sample
                     if (zero) inner |= 1u << (2 * ly + q);
                 }
             t.periodic_trim.quad_inner = inner;
+            // integer planes whose phase sets follow the 2x symmetry classes: the kInnerTap3 instance shares products between
+            // mirrored outputs on frame pairs (kernels.h quad2_share_classes).  Knob QUAD_SHARE = 0 fails the check (tests, A/B).
+            jinc::PeriodicArgs& tr = t.periodic_trim;
+            tr.quad_share = 0;
+            if (integer_samples && (inner & jinc::PeriodicArgs::kQuadInnerTap3) == jinc::PeriodicArgs::kQuadInnerTap3 &&
+                knobs::flag(JINC_KNOB_QUAD_SHARE, true)) {
+                const float* const phase_sets[4] = {sets[0], sets[1], sets[2], sets[3]};
+                float w[jinc::kQuad2ShareClasses] = {};
+                if (jinc::quad2_share_classes(phase_sets, w)) {
+                    tr.quad_share = 1;
+                    std::copy(w, w + jinc::kQuad2ShareClasses, tr.share_w);
+                }
+            }
         }
         if (n == 8 && t.periodic_trim.quad) {  // 8 x 8 support: taps every (kernel row, q) leaves out per side for both p
             const bool off = !knobs::flag(JINC_KNOB_QUAD_INNER, true);

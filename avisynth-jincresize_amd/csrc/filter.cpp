@@ -540,6 +540,12 @@ int jinc_debug_chord_pattern(int taps_per_row, uint64_t spans) {
     return -1;
 }
 
+int jinc_debug_quad2_share(const float* sets, float* share_w) {
+    if (!sets || !share_w) return 0;
+    const float* const phase_sets[4] = {sets, sets + 36, sets + 72, sets + 108};
+    return jinc::quad2_share_classes(phase_sets, share_w) ? 1 : 0;
+}
+
 // Shader-clock sampler beside the kernels being timed (kernel_probe.hip).
 struct jinc_clock_sampler {
     int device = 0;

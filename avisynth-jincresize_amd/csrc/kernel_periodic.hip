@@ -6,6 +6,7 @@
 // See device_common.hpp for the parity rules.
 #include "device_common.hpp"
 #include "knobs.h"
+#include <utility>
 
 #pragma clang fp contract(off)
 
@@ -1187,7 +1188,8 @@ __device__ __forceinline__ void stage_edge_column(const PeriodicArgs& a, const P
     }
 }
 
-template <typename T, typename Cfg, int NR, int NC>
+// ES: floats per staged sample (2: the frame-pair tile of the symmetry-class form, `tile` pointing at the frame's half of the first pair).
+template <typename T, typename Cfg, int NR, int NC, int ES = 1>
 __device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const PlaneIO& io, const float* tile, int tile_x, int j0, int wave, int lane,
                                                    BufferRsrc drsrc) {
     constexpr int NCP = (NC + 3) & ~3;  // floats per coefficient row
@@ -1202,10 +1204,10 @@ __device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const 
         // shifts (read from LDS, the lanes' rows lie a pitch apart: four banks for 64 lanes, a 16-way conflict per read.  Measured
         // level with this form all the same -- round5/edge_cols_ab.log -- the chains are what the edge tiles pay for).
         static_assert(Cfg::kLdsRows <= 64, "one tile row per lane");
-        const float* wp = tile + (lane < Cfg::kLdsRows ? lane : 0) * Cfg::kLdsPitch + a.edge.lds_col[s];
+        const float* wp = tile + ((lane < Cfg::kLdsRows ? lane : 0) * Cfg::kLdsPitch + a.edge.lds_col[s]) * ES;
         float w[NR][NC];
 #pragma unroll
-        for (int lx = 0; lx < NC; ++lx) w[0][lx] = wp[lx];
+        for (int lx = 0; lx < NC; ++lx) w[0][lx] = wp[lx * ES];
 #pragma unroll
         for (int ly = 1; ly < NR; ++ly)
 #pragma unroll
@@ -1251,6 +1253,189 @@ __device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same interior on frame pairs, one product per (source sample, symmetry class) (integer planes, kQuad2InnerTap3)
+// ------------------------------------------------------------------------------------------------
+// The reference computes every output as its own chain of un-fused acc = acc + sample * coeff in (ly, lx) order.  That fixes each
+// chain's adds and the value of each product, not where the product is computed: fl(s * c) depends on the bits of s and c alone, so
+// one product added into several chains is bit-identical to a product per chain.  At exactly 2x the outputs sit +-1/4 and +-3/4 of
+// a source step from the samples and a coefficient depends on the unordered pair of distance classes (kernels.h quad2_share_class;
+// the host checks the plan's four phase sets against it, PeriodicArgs::quad_share): a product sample * w(class) is needed by up to
+// eight outputs.  A lane owns 2 x 2 periods = 4 x 4 outputs of TWO frames (the packed halves: frames 2z and 2z + 1, each source
+// sample staged as one f32x2) and walks their 7 x 7 source window row by row, left to right: per (sample, class) the block needs,
+// one v_pk_mul_f32 (the class coefficient broadcast from an SGPR by op_sel), then one v_pk_add_f32 into each chain that takes it
+// -- 351 multiplies and 496 adds per block, 21.9 + 31 per output pair, where the per-frame form above issues 34 + 34 (three zero taps;
+// leaving them out is exact for integer samples, see Quad2Cfg).  Every chain still meets its taps in (ly, lx) order: ly and lx
+// grow with the source row and column.  The last pair of an odd frame count stages the low frame twice and stores it once.
+// Tiles of 128 x 16 periods: each wave two blocks of 2 period rows (the pair tile is twice the bytes of a frame's, and 16 rows keep
+// six workgroups per CU in LDS).
+struct Quad2ShareCfg {
+    static constexpr int kTileCols = 128;                     // periods per tile row (Quad2Cfg's: the edge columns' tile_x)
+    static constexpr int kBlocksPerWave = 2;                  // 2 x 2-period blocks per lane, one above the other
+    static constexpr int kTileRows = 4 * 2 * kBlocksPerWave;  // period rows per tile
+    static constexpr int kLdsCols = kTileCols + 6;            // (pairs) as Quad2Cfg: the edge columns' windows reach column 133
+    static constexpr int kLdsPitch = 136;                     // pairs: rows 16-byte aligned, a spare pair per row (column -1 of the next)
+    static constexpr int kLdsRows = kTileRows + 5;
+    static constexpr int kLdsFloats = 2 * (2 + kLdsRows * kLdsPitch);  // two pairs in front of the tile: row 0's column -1
+};
+
+// Both launcher and kernel: does this launch of the integer kInnerTap3 instance (launched for plans with quad_share only) run the
+// frame-pair form?  The full-tile instance (RG 8: long batches) has no other body -- the per-frame form's window and tile would cost
+// it registers and LDS; the half-tile one (RG 4) keeps the per-frame form for single frames, where a pair's second half is wasted.
+template <int RG>
+__host__ __device__ inline bool quad2_share_runs(const PlaneIO& io) { return RG == 8 || io.nframes > 1; }
+
+// The lane's outputs (bit 4 * oy + ox; oy = 2 * period row + q, ox = 2 * period column + p) that take sample (r, c) of the block's
+// 7 x 7 window with a coefficient of class k.
+constexpr uint32_t quad2_share_outs(int r, int c, int k) {
+    uint32_t m = 0;
+    for (int oy = 0; oy < 4; ++oy)
+        for (int ox = 0; ox < 4; ++ox) {
+            const int ly = r - (oy >> 1), lx = c - (ox >> 1);
+            if (ly < 0 || ly > 5 || lx < 0 || lx > 5) continue;
+            if (quad2_share_class(quad2_share_m(ox & 1, lx), quad2_share_m(oy & 1, ly)) == k) m |= 1u << (4 * oy + ox);
+        }
+    return m;
+}
+
+// Sample (R, C) times class K (the high / low half of SGPR pair K / 2, for both frames), where the block needs that product.
+template <int R, int C, int K>
+__device__ __forceinline__ void quad2_share_mul(f32x2& t, f32x2 s, const f32x2 (&w)[kQuad2ShareClasses / 2]) {
+    if constexpr (quad2_share_outs(R, C, K) != 0) {
+        if constexpr (K & 1)
+            asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(t) : "v"(s), "s"(w[K >> 1]));
+        else
+            asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(s), "s"(w[K >> 1]));
+    }
+}
+// ... added into every chain that takes it
+template <int R, int C, int K>
+__device__ __forceinline__ void quad2_share_adds(f32x2 (&acc)[16], f32x2 t) {
+    constexpr uint32_t outs = quad2_share_outs(R, C, K);
+#pragma unroll
+    for (int o = 0; o < 16; ++o)
+        if constexpr (outs != 0)
+            if ((outs >> o) & 1u) asm("v_pk_add_f32 %0, %0, %1" : "+v"(acc[o]) : "v"(t));
+}
+// All products of a sample first, then their adds: no add waits on the multiply just issued in front of it.
+template <int R, int C, int... K>
+__device__ __forceinline__ void quad2_share_sample(f32x2 (&acc)[16], f32x2 s, const f32x2 (&w)[kQuad2ShareClasses / 2], std::integer_sequence<int, K...>) {
+    f32x2 t[kQuad2ShareClasses];
+    (quad2_share_mul<R, C, K>(t[K], s, w), ...);
+    (quad2_share_adds<R, C, K>(acc, t[K]), ...);
+}
+// Source row R of the block's window: pairs row[0 .. 6] = columns 0 .. 6 (row[7] is loaded with them and unused).
+template <int R, int... C>
+__device__ __forceinline__ void quad2_share_row(f32x2 (&acc)[16], const f32x2 (&row)[8], const f32x2 (&w)[kQuad2ShareClasses / 2], std::integer_sequence<int, C...>) {
+    (quad2_share_sample<R, C>(acc, row[C], w, std::make_integer_sequence<int, kQuad2ShareClasses>{}), ...);
+}
+
+template <typename T>
+__device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const PlaneIO& io, float* lds) {
+    using Cfg = Quad2ShareCfg;
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    f32x2* const tile = reinterpret_cast<f32x2*>(lds) + 2;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int tile_x, tile_y;
+    swizzled_tile(tile_x, tile_y);
+    const int i0 = tile_x * Cfg::kTileCols;
+    const int j0 = tile_y * Cfg::kTileRows;
+    const size_t f0 = 2 * static_cast<size_t>(blockIdx.z);
+    const bool f1_ok = f0 + 1 < static_cast<size_t>(io.nframes);  // the last pair of an odd count: the high half repeats the low frame
+    const size_t f1 = f1_ok ? f0 + 1 : f0;
+    const bool edge_tile = edge_tile_of<T>(a, tile_x);
+    {   // stage both frames' source tiles as f32 pairs, all loads in front of the LDS writes (see ewa_periodic_kernel)
+        const int gx0 = a.min_sx + i0;
+        const int gy0 = a.min_sy + j0;
+        const char* sb0 = static_cast<const char*>(io.src) + f0 * io.src_frame_stride;
+        const char* sb1 = static_cast<const char*>(io.src) + f1 * io.src_frame_stride;
+        constexpr int kRowsPerWave = (Cfg::kLdsRows + 3) / 4;
+        constexpr int kColsPerLane = (Cfg::kLdsCols + 63) / 64;
+        T s0[kRowsPerWave][kColsPerLane], s1[kRowsPerWave][kColsPerLane];
+#pragma unroll
+        for (int i = 0; i < kRowsPerWave; ++i) {
+            int gy = gy0 + wave + 4 * i;
+            gy = gy < a.src_h ? gy : a.src_h - 1;
+            const T* r0 = reinterpret_cast<const T*>(sb0 + static_cast<size_t>(gy) * io.src_pitch);
+            const T* r1 = reinterpret_cast<const T*>(sb1 + static_cast<size_t>(gy) * io.src_pitch);
+#pragma unroll
+            for (int k = 0; k < kColsPerLane; ++k) {
+                int gx = gx0 + lane + 64 * k;
+                gx = gx < a.src_w ? gx : a.src_w - 1;
+                s0[i][k] = r0[gx];
+                s1[i][k] = r1[gx];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kRowsPerWave; ++i) {
+            const int r = wave + 4 * i;
+#pragma unroll
+            for (int k = 0; k < kColsPerLane; ++k) {
+                const int c = lane + 64 * k;
+                if (r < Cfg::kLdsRows && c < Cfg::kLdsCols) tile[r * Cfg::kLdsPitch + c] = f32x2{to_float(s0[i][k]), to_float(s1[i][k])};
+            }
+        }
+        // an edge window that starts one column in front of the tile: that column into the pair in front of each row (stage_edge_column)
+        const bool in_front = edge_tile && ((a.edge.n[0] > 0 && tile_x == a.edge.tile_x[0] && a.edge.lds_col[0] < 0) ||
+                                            (a.edge.n[1] > 0 && tile_x == a.edge.tile_x[1] && a.edge.lds_col[1] < 0));
+        if (in_front && wave == 0 && lane < Cfg::kLdsRows && gx0 > 0) {
+            int gy = gy0 + lane;
+            gy = gy < a.src_h ? gy : a.src_h - 1;
+            tile[lane * Cfg::kLdsPitch - 1] = f32x2{to_float(reinterpret_cast<const T*>(sb0 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1]),
+                                                    to_float(reinterpret_cast<const T*>(sb1 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1])};
+        }
+    }
+    __syncthreads();
+    const uint32_t plane_bytes = static_cast<uint32_t>(io.dst_pitch) * a.dst_h;
+    const BufferRsrc d0 = make_rsrc(static_cast<char*>(io.dst) + f0 * io.dst_frame_stride, plane_bytes);  // wave-uniform
+    const BufferRsrc d1 = make_rsrc(static_cast<char*>(io.dst) + f1 * io.dst_frame_stride, plane_bytes);
+    if (edge_tile) {
+        quad2_edge_columns<T, Cfg, 6, 7, 2>(a, io, reinterpret_cast<const float*>(tile), tile_x, j0, wave, lane, d0);
+        if (f1_ok) quad2_edge_columns<T, Cfg, 6, 7, 2>(a, io, reinterpret_cast<const float*>(tile) + 1, tile_x, j0, wave, lane, d1);
+    }
+    const int ia = i0 + 2 * lane;  // the lane's first period
+    if (ia >= a.ni) return;        // no barrier below
+    const bool b_ok = ia + 1 < a.ni;
+    f32x2 w[kQuad2ShareClasses / 2];
+#pragma unroll
+    for (int k = 0; k < kQuad2ShareClasses / 2; ++k) w[k] = f32x2{a.share_w[2 * k], a.share_w[2 * k + 1]};
+    const uint32_t xoff = static_cast<uint32_t>(a.ix0 + 2 * ia) * static_cast<uint32_t>(sizeof(T));
+    for (int blk = 0; blk < Cfg::kBlocksPerWave; ++blk) {
+        const int jb = 2 * (wave * Cfg::kBlocksPerWave + blk);  // the block's first period row in the tile
+        if (j0 + jb >= a.nj) break;                             // wave-uniform: bottom tiles
+        const f32x2* wb = tile + jb * Cfg::kLdsPitch + 2 * lane;
+        f32x2 acc[16];
+#pragma unroll
+        for (int o = 0; o < 16; ++o) acc[o] = f32x2{0.f, 0.f};
+#define JINC_SHARE_ROW(R)                                                                                 \
+    {                                                                                                     \
+        const f32x4* p4 = reinterpret_cast<const f32x4*>(wb + (R) * Cfg::kLdsPitch);                      \
+        f32x2 row[8];                                                                                     \
+        _Pragma("unroll") for (int m = 0; m < 4; ++m) {                                                   \
+            const f32x4 v = p4[m];                                                                        \
+            row[2 * m] = f32x2{v.x, v.y};                                                                 \
+            row[2 * m + 1] = f32x2{v.z, v.w};                                                             \
+        }                                                                                                 \
+        quad2_share_row<R>(acc, row, w, std::make_integer_sequence<int, 7>{});                            \
+    }
+        JINC_SHARE_ROW(0) JINC_SHARE_ROW(1) JINC_SHARE_ROW(2) JINC_SHARE_ROW(3) JINC_SHARE_ROW(4) JINC_SHARE_ROW(5) JINC_SHARE_ROW(6)
+#undef JINC_SHARE_ROW
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) {
+            const int j = j0 + jb + pr;
+            if (j >= a.nj) break;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const uint32_t so = static_cast<uint32_t>(a.iy0 + 2 * j + q) * static_cast<uint32_t>(io.dst_pitch);
+                const f32x2* r = acc + 4 * (2 * pr + q);
+                store_quad_buf<T>(d0, xoff, so, f32x2{r[0].x, r[1].x}, f32x2{r[2].x, r[3].x}, io.peak, b_ok);
+                if (f1_ok) store_quad_buf<T>(d1, xoff, so, f32x2{r[0].y, r[1].y}, f32x2{r[2].y, r[3].y}, io.peak, b_ok);
+            }
+        }
+    }
+}
+
 // INNER: bit 2 * ly + q set = taps 0 and 5 of kernel row ly are zero for both phases p of q and are not executed (the disc's chord
 // in the box's edge rows).  Instantiated for no such rows and for the pattern of the 2x up-scale with tap 3 at blur 1 (q = 0: the
 // last kernel row, q = 1: the first): the launcher takes the instantiation whose mask is a subset of the plan's.
@@ -1263,7 +1448,21 @@ __global__ __launch_bounds__(256, 6) void ewa_periodic_quad2_kernel(const Period
     constexpr int FS = Cfg::FS;
     static_assert(RG % 4 == 0, "the four waves of a workgroup take RG / 4 row groups each");
     // (two words in front of the tile: row 0's "column -1", see the edge columns below; the tile stays 8-byte aligned)
-    __shared__ __attribute__((aligned(16))) float tile_words[2 + Cfg::kLdsRows * Cfg::kLdsPitch];
+    // The frame-pair form (quad2_share_body) of the integer kInnerTap3 instances stages its tile into the same words.
+    constexpr bool kShare = !is_float_sample_v<T> && INNER == kQuad2InnerTap3 && NT == 6;
+    constexpr int kWords = 2 + Cfg::kLdsRows * Cfg::kLdsPitch;
+    if constexpr (kShare && RG == 8) {  // (what follows is dead code here: neither its registers nor its tile are allocated)
+        __shared__ __attribute__((aligned(16))) float share_words[Quad2ShareCfg::kLdsFloats];
+        quad2_share_body<T>(a, io, share_words);
+        return;
+    }
+    __shared__ __attribute__((aligned(16))) float tile_words[kShare && Quad2ShareCfg::kLdsFloats > kWords ? Quad2ShareCfg::kLdsFloats : kWords];
+    if constexpr (kShare) {
+        if (quad2_share_runs<RG>(io)) {  // workgroup-uniform
+            quad2_share_body<T>(a, io, tile_words);
+            return;
+        }
+    }
     float* const tile = tile_words + 2;
 
     const int lane = threadIdx.x & 63;
@@ -1907,6 +2106,17 @@ int launch_periodic_quad2_t(const PeriodicArgs& pa, const PlaneIO& io, hipStream
         hipLaunchKernelGGL((ewa_periodic_quad2_kernel<T, RG, 0u, 7>), grid, dim3(256, 1, 1), 0, stream, pa, io);
         knobs::note_instance("ewa_periodic_quad2_kernel", "%s, %d, 0u, 7", knobs::type_name<T>(), RG);
     } else if ((pa.quad_inner & kQuad2InnerTap3) == kQuad2InnerTap3) {
+        bool share = false;
+        if constexpr (!is_float_sample_v<T>) share = true;
+        if (share && pa.quad_share) {  // integer planes: the frame-pair form, on tiles of its own (quad2_share_body)
+            if (quad2_share_runs<RG>(io))
+                grid = dim3((pa.ni + Quad2ShareCfg::kTileCols - 1) / Quad2ShareCfg::kTileCols, (pa.nj + Quad2ShareCfg::kTileRows - 1) / Quad2ShareCfg::kTileRows,
+                            (io.nframes + 1) / 2);
+        } else if (share) {  // ... whose instance needs the symmetry classes: a plan that does not follow them takes every tap
+            hipLaunchKernelGGL((ewa_periodic_quad2_kernel<T, RG, 0u>), grid, dim3(256, 1, 1), 0, stream, pa, io);
+            knobs::note_instance("ewa_periodic_quad2_kernel", "%s, %d, 0u, 6", knobs::type_name<T>(), RG);
+            return static_cast<int>(hipGetLastError());
+        }
         hipLaunchKernelGGL((ewa_periodic_quad2_kernel<T, RG, kQuad2InnerTap3>), grid, dim3(256, 1, 1), 0, stream, pa, io);
         knobs::note_instance("ewa_periodic_quad2_kernel", "%s, %d, %uu, 6", knobs::type_name<T>(), RG, kQuad2InnerTap3);
     } else {

@@ -3,6 +3,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 namespace jinc {
 
@@ -76,6 +77,34 @@ inline long long gather_item_count(int w, int h, int axis, int P) {
 // Phase-periodic interior (see plan.h): output pixel (ix0 + px*i + p, iy0 + py*j + q) reads the
 // source window at (start_x[p] + i, start_y[q] + j) with coefficient set set[q*px + p].
 constexpr uint32_t span7_form(int ly, int q, uint32_t form) { return form << (2 * (2 * ly + q)); }  // (PeriodicArgs::kQuadSpan7Mpeg2)
+
+// Symmetry classes of the 2x up-scale with tap 3 on the trimmed 6 x 6 support (ewa_periodic_quad2_kernel<integer, RG,
+// kQuadInnerTap3, 6> on frame pairs; host check: device_plan.cpp quad2_share_classes).  Phase 0 of an axis sits 2.25 taps
+// behind the window origin, phase 1 2.75, so tap t of phase ph is (2 m + 1) / 4 source steps from the output's centre with
+// m = quad2_share_m(ph, t) in 0 .. 5.  An EWA weight depends on the distance alone: a tap's coefficient is a function of the
+// unordered pair (m_x, m_y).  The 21 pairs are 18 inside the disc of radius 3.24 and 3 outside ((2 a + 1)^2 + (2 b + 1)^2 > 162:
+// (3, 5), (4, 5), (5, 5)), whose coefficients are 0.  quad2_share_class numbers the 18 in (min, max) order, -1 for the others.
+constexpr int kQuad2ShareClasses = 18;
+constexpr int quad2_share_m(int ph, int t) {
+    const int d = 4 * t - 9 - 2 * ph;
+    return ((d < 0 ? -d : d) - 1) / 2;
+}
+constexpr bool quad2_share_inside(int a, int b) { return (2 * a + 1) * (2 * a + 1) + (2 * b + 1) * (2 * b + 1) <= 162; }
+constexpr int quad2_share_class(int mx, int my) {
+    const int a = mx < my ? mx : my, b = mx < my ? my : mx;
+    if (!quad2_share_inside(a, b)) return -1;
+    int k = 0;
+    for (int lo = 0; lo < 6; ++lo)
+        for (int hi = lo; hi < 6; ++hi) {
+            if (!quad2_share_inside(lo, hi)) continue;
+            if (lo == a && hi == b) return k;
+            ++k;
+        }
+    return -1;
+}
+static_assert(quad2_share_class(4, 4) == kQuad2ShareClasses - 1 && quad2_share_class(5, 2) == 14 && quad2_share_class(3, 5) < 0 &&
+                  quad2_share_m(0, 2) == 0 && quad2_share_m(1, 3) == 0 && quad2_share_m(0, 5) == 5 && quad2_share_m(1, 0) == 5,
+              "class numbering");
 struct PeriodicArgs {
     const float* coeffs = nullptr;
     int px = 1, py = 1;
@@ -105,6 +134,11 @@ struct PeriodicArgs {
     static constexpr uint32_t kQuadSpan7Mpeg2Swapped = span7_form(0, 1, 3) | span7_form(1, 1, 1) | span7_form(5, 1, 2) | span7_form(0, 0, 2) |
                                                        span7_form(4, 0, 1) | span7_form(5, 0, 3);
     static constexpr uint32_t kQuadInnerTap3 = (1u << (2 * 5 + 0)) | (1u << (2 * 0 + 1));  // the mask the kernel is instantiated for
+    // integer planes on the 6 x 6 support whose four phase sets follow the symmetry classes above bit for bit (quad_share = 1):
+    // share_w[class] is every tap of that class, the taps outside the disc are 0.0f.  The kInnerTap3 instance then computes frame
+    // pairs, one product per (source sample, class) for all of the lane's outputs that need it (quad2_share_runs).
+    int quad_share = 0;
+    alignas(8) float share_w[kQuad2ShareClasses] = {};
     // quad forms on the 8 x 8 support: taps kernel row ly of q leaves out per side (0 .. 3), two bits at 2 * (2 * ly + q)
     uint32_t quad_trim8 = 0;
     static const uint32_t kQuad8TrimTap4;  // the pattern the kernels are instantiated for (below)
@@ -172,6 +206,31 @@ inline bool quad_span9_fits(uint64_t plan, uint64_t pattern) {  // plan: lead / 
         if (form > 4) return false;
         if (static_cast<int>((plan >> (4 * k)) & 3u) < lead[form] || static_cast<int>((plan >> (4 * k + 2)) & 3u) < trail[form]) return false;
     }
+    return true;
+}
+// Do the four phase sets of a 6 x 6 support follow the symmetry classes of quad2_share_class bit for bit?  sets[q * 2 + p] = the
+// dense 6 x 6 set of phase (p, q).  Every tap of a class must hold the same bits (share_w[class] receives them), every tap outside
+// the disc exactly 0.0f: then one product per (sample, class) feeds every chain that takes that tap, bit-identical to a product per
+// chain.  Host only.
+inline bool quad2_share_classes(const float* const sets[4], float* share_w) {
+    bool seen[kQuad2ShareClasses] = {};
+    for (int q = 0; q < 2; ++q)
+        for (int p = 0; p < 2; ++p)
+            for (int ly = 0; ly < 6; ++ly)
+                for (int lx = 0; lx < 6; ++lx) {
+                    const float c = sets[q * 2 + p][ly * 6 + lx];
+                    const int k = quad2_share_class(quad2_share_m(p, lx), quad2_share_m(q, ly));
+                    if (k < 0) {
+                        if (c != 0.f) return false;
+                        continue;
+                    }
+                    if (!seen[k]) {
+                        seen[k] = true;
+                        share_w[k] = c;
+                    } else if (std::memcmp(&share_w[k], &c, sizeof(float)) != 0) {
+                        return false;
+                    }
+                }
     return true;
 }
 inline int quad_span9_taps(uint64_t pattern) {  // taps the pattern executes over the 16 (ly, q) rows: twice the taps per sample

@@ -149,6 +149,7 @@ typedef enum jinc_knob {
     JINC_KNOB_COPY_THREADS,           /* CPU threads that copy a large pageable plane to / from the library's pinned buffers: 1 = the calling thread only; default 6 on hosts with 12 CPUs or more, 4 from 8 on, 2 from 4 on (round 6) */
     JINC_KNOB_STAGE_BANDS,            /* row bands a pageable plane is cut into between the CPU's copy and the DMA engine: default 4 (2 MiB each at least), 1 = whole planes (round 6) */
     JINC_KNOB_STAGE_DEFER_KB,         /* pageable frames of up to this many KiB of source in groups of 4 or more are copied to the library's pinned buffer when the group is launched (one job, one DMA copy per plane) instead of at submit: default 1536, 0 = never (round 6) */
+    JINC_KNOB_QUAD_SHARE,             /* 0: the 2x tap-3 interior of integer planes without its frame-pair symmetry-class form (the plan's class check fails; tests, A/B) */
     JINC_KNOB_COUNT
 } jinc_knob;
 JINC_API int jinc_debug_set_knob(int knob, double value);
@@ -159,6 +160,10 @@ JINC_API int jinc_debug_get_knob(int knob, double *value);  /* 1: set (*value re
  * (capped at 3) at 4 * (2 * ly + q) and 4 * (2 * ly + q) + 2.  Returns 1 / 2 if the kernels' compile-time pattern / its row-phase-swapped twin
  * leaves out no more than that, 0 if neither (all taps of the support then), -1 for a tap count without patterns.  Host only: no device call. */
 JINC_API int jinc_debug_chord_pattern(int taps_per_row, uint64_t spans);
+/* The symmetry-class check of the 2x tap-3 interior (ewa_periodic_quad2_kernel's frame-pair form): `sets` = the four dense 6 x 6 phase
+ * sets of the trimmed support, set (p, q) at sets + 36 * (2 * q + p).  Returns 1 and the 18 class coefficients in share_w if every tap
+ * equals its class's coefficient bit for bit and every tap outside the disc is 0.0f, else 0.  Host only: no device call. */
+JINC_API int jinc_debug_quad2_share(const float *sets, float *share_w);
 JINC_API const char *jinc_debug_knob_name(int knob);        /* lower-case name ("quad_rg"); NULL beyond the last knob */
 /* Taps per axis the periodic interior kernels of `table` execute under the current kernel mode: the plan's filter size, or
  * the side of the trimmed support on integer planes (kernel mode 15 switches trimming off); 0 when the table has no
