@@ -1260,24 +1260,37 @@ __device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const 
 // chain's adds and the value of each product, not where the product is computed: fl(s * c) depends on the bits of s and c alone, so
 // one product added into several chains is bit-identical to a product per chain.  At exactly 2x the outputs sit +-1/4 and +-3/4 of
 // a source step from the samples and a coefficient depends on the unordered pair of distance classes (kernels.h quad2_share_class;
-// the host checks the plan's four phase sets against it, PeriodicArgs::quad_share): a product sample * w(class) is needed by up to
-// eight outputs.  A lane owns 2 x 2 periods = 4 x 4 outputs of TWO frames (the packed halves: frames 2z and 2z + 1, each source
-// sample staged as one f32x2) and walks their 7 x 7 source window row by row, left to right: per (sample, class) the block needs,
-// one v_pk_mul_f32 (the class coefficient broadcast from an SGPR by op_sel), then one v_pk_add_f32 into each chain that takes it
-// -- 351 multiplies and 496 adds per block, 21.9 + 31 per output pair, where the per-frame form above issues 34 + 34 (three zero taps;
-// leaving them out is exact for integer samples, see Quad2Cfg).  Every chain still meets its taps in (ly, lx) order: ly and lx
-// grow with the source row and column.  The last pair of an odd frame count stages the low frame twice and stores it once.
-// Tiles of 128 x 16 periods: each wave two blocks of 2 period rows (the pair tile is twice the bytes of a frame's, and 16 rows keep
-// six workgroups per CU in LDS).
-struct Quad2ShareCfg {
-    static constexpr int kTileCols = 128;                     // periods per tile row (Quad2Cfg's: the edge columns' tile_x)
-    static constexpr int kBlocksPerWave = 2;                  // 2 x 2-period blocks per lane, one above the other
-    static constexpr int kTileRows = 4 * 2 * kBlocksPerWave;  // period rows per tile
-    static constexpr int kLdsCols = kTileCols + 6;            // (pairs) as Quad2Cfg: the edge columns' windows reach column 133
-    static constexpr int kLdsPitch = 136;                     // pairs: rows 16-byte aligned, a spare pair per row (column -1 of the next)
+// the host checks the plan's four phase sets against it, PeriodicArgs::quad_share): a product sample * w(class) is needed by every
+// output at that class's distance, in the period rows above and below the lane's as much as in its own.  A lane owns a strip 2
+// periods across and H period rows down = 4 x 2H outputs of TWO frames (the packed halves: frames 2z and 2z + 1, each source sample
+// staged as one f32x2) and walks the strip's 7-column x (H + 5)-row source window row by row, left to right: per (sample, class) an
+// open chain needs, one v_pk_mul_f32 (the class coefficient broadcast from an SGPR by op_sel), then one v_pk_add_f32 into each chain
+// that takes it.  Period row j opens at source row j and is complete after source row j + 5: it is stored there, and its registers
+// serve period row j + 6 (the walk is unrolled whole, so at most six period rows = 48 packed accumulators are live).  Every chain
+// still meets its taps in (ly, lx) order: ly and lx grow with the source row and column.  Three taps per row phase are zero (leaving
+// them out is exact for integer samples, see Quad2Cfg).  The last pair of an odd frame count stages the low frame twice and stores
+// it once.  Per output pair the per-frame form above issues 34 multiplies + 34 adds, strips of H = 2 (2 x 2-period blocks)
+// 21.9 + 31, strips of H = 8 15.5 + 31.
+//   Full tiles (RG 8, long batches): 128 x 32 periods, one strip of 8 period rows per wave, 37 staged rows of f32 pairs (40.3 KB of
+// LDS: four workgroups per CU, as many as the 96 live accumulators leave waves per SIMD).  Its products come one class at a time,
+// the adds of each behind the next multiply: all of a sample's products at once would not fit beside the accumulators.
+//   Half tiles (RG 4, short batches): 128 x 16 periods, two strips of 2 period rows per wave (22.9 KB, six workgroups per CU), all
+// of a sample's products in front of their adds, so that no add waits on the multiply just issued.
+template <int H, int StripsPerWave, int MulLead>
+struct Quad2ShareTile {
+    static constexpr int kTileCols = 128;                    // periods per tile row (Quad2Cfg's: the edge columns' tile_x)
+    static constexpr int kStripRows = H;                     // period rows per strip
+    static constexpr int kStripsPerWave = StripsPerWave;     // strips per lane, one below the other
+    static constexpr int kMulLead = MulLead;                 // multiplies issued ahead of the adds that take them
+    static constexpr int kTileRows = 4 * H * StripsPerWave;  // period rows per tile
+    static constexpr int kLdsCols = kTileCols + 6;           // (pairs) as Quad2Cfg: the edge columns' windows reach column 133
+    static constexpr int kLdsPitch = 136;                    // pairs: rows 16-byte aligned, a spare pair per row (column -1 of the next)
     static constexpr int kLdsRows = kTileRows + 5;
     static constexpr int kLdsFloats = 2 * (2 + kLdsRows * kLdsPitch);  // two pairs in front of the tile: row 0's column -1
+    static_assert(8 * H <= 64, "a strip's outputs index one 64-bit mask");
 };
+template <int RG>
+using Quad2ShareCfg = std::conditional_t<RG == 8, Quad2ShareTile<8, 1, 1>, Quad2ShareTile<2, 2, kQuad2ShareClasses>>;
 
 // Both launcher and kernel: does this launch of the integer kInnerTap3 instance (launched for plans with quad_share only) run the
 // frame-pair form?  The full-tile instance (RG 8: long batches) has no other body -- the per-frame form's window and tile would cost
@@ -1285,23 +1298,24 @@ struct Quad2ShareCfg {
 template <int RG>
 __host__ __device__ inline bool quad2_share_runs(const PlaneIO& io) { return RG == 8 || io.nframes > 1; }
 
-// The lane's outputs (bit 4 * oy + ox; oy = 2 * period row + q, ox = 2 * period column + p) that take sample (r, c) of the block's
-// 7 x 7 window with a coefficient of class k.
-constexpr uint32_t quad2_share_outs(int r, int c, int k) {
-    uint32_t m = 0;
-    for (int oy = 0; oy < 4; ++oy)
+// The strip's outputs (bit 4 * oy + ox; oy = 2 * period row + q, ox = 2 * period column + p) that take sample (r, c) of its
+// 7-column x (H + 5)-row window with a coefficient of class k.
+template <int H>
+constexpr uint64_t quad2_share_outs(int r, int c, int k) {
+    uint64_t m = 0;
+    for (int oy = 0; oy < 2 * H; ++oy)
         for (int ox = 0; ox < 4; ++ox) {
             const int ly = r - (oy >> 1), lx = c - (ox >> 1);
             if (ly < 0 || ly > 5 || lx < 0 || lx > 5) continue;
-            if (quad2_share_class(quad2_share_m(ox & 1, lx), quad2_share_m(oy & 1, ly)) == k) m |= 1u << (4 * oy + ox);
+            if (quad2_share_class(quad2_share_m(ox & 1, lx), quad2_share_m(oy & 1, ly)) == k) m |= uint64_t{1} << (4 * oy + ox);
         }
     return m;
 }
 
-// Sample (R, C) times class K (the high / low half of SGPR pair K / 2, for both frames), where the block needs that product.
-template <int R, int C, int K>
+// Sample (R, C) times class K (the high / low half of SGPR pair K / 2, for both frames), where the strip needs that product.
+template <int H, int R, int C, int K>
 __device__ __forceinline__ void quad2_share_mul(f32x2& t, f32x2 s, const f32x2 (&w)[kQuad2ShareClasses / 2]) {
-    if constexpr (quad2_share_outs(R, C, K) != 0) {
+    if constexpr (quad2_share_outs<H>(R, C, K) != 0) {
         if constexpr (K & 1)
             asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(t) : "v"(s), "s"(w[K >> 1]));
         else
@@ -1309,31 +1323,56 @@ __device__ __forceinline__ void quad2_share_mul(f32x2& t, f32x2 s, const f32x2 (
     }
 }
 // ... added into every chain that takes it
-template <int R, int C, int K>
-__device__ __forceinline__ void quad2_share_adds(f32x2 (&acc)[16], f32x2 t) {
-    constexpr uint32_t outs = quad2_share_outs(R, C, K);
+template <int H, int R, int C, int K>
+__device__ __forceinline__ void quad2_share_adds(f32x2 (&acc)[8 * H], f32x2 t) {
+    constexpr uint64_t outs = quad2_share_outs<H>(R, C, K);
 #pragma unroll
-    for (int o = 0; o < 16; ++o)
+    for (int o = 0; o < 8 * H; ++o)
         if constexpr (outs != 0)
             if ((outs >> o) & 1u) asm("v_pk_add_f32 %0, %0, %1" : "+v"(acc[o]) : "v"(t));
 }
-// All products of a sample first, then their adds: no add waits on the multiply just issued in front of it.
-template <int R, int C, int... K>
-__device__ __forceinline__ void quad2_share_sample(f32x2 (&acc)[16], f32x2 s, const f32x2 (&w)[kQuad2ShareClasses / 2], std::integer_sequence<int, K...>) {
-    f32x2 t[kQuad2ShareClasses];
-    (quad2_share_mul<R, C, K>(t[K], s, w), ...);
-    (quad2_share_adds<R, C, K>(acc, t[K]), ...);
+// Step K of a sample: the multiply of class K, then the adds of class K - kMulLead.
+template <typename Cfg, int R, int C, int K>
+__device__ __forceinline__ void quad2_share_step(f32x2 (&acc)[8 * Cfg::kStripRows], f32x2 (&t)[kQuad2ShareClasses], f32x2 s,
+                                                 const f32x2 (&w)[kQuad2ShareClasses / 2]) {
+    if constexpr (K < kQuad2ShareClasses) quad2_share_mul<Cfg::kStripRows, R, C, K>(t[K], s, w);
+    if constexpr (K >= Cfg::kMulLead) quad2_share_adds<Cfg::kStripRows, R, C, K - Cfg::kMulLead>(acc, t[K - Cfg::kMulLead]);
 }
-// Source row R of the block's window: pairs row[0 .. 6] = columns 0 .. 6 (row[7] is loaded with them and unused).
-template <int R, int... C>
-__device__ __forceinline__ void quad2_share_row(f32x2 (&acc)[16], const f32x2 (&row)[8], const f32x2 (&w)[kQuad2ShareClasses / 2], std::integer_sequence<int, C...>) {
-    (quad2_share_sample<R, C>(acc, row[C], w, std::make_integer_sequence<int, kQuad2ShareClasses>{}), ...);
+template <typename Cfg, int R, int C, int... K>
+__device__ __forceinline__ void quad2_share_sample(f32x2 (&acc)[8 * Cfg::kStripRows], f32x2 s, const f32x2 (&w)[kQuad2ShareClasses / 2],
+                                                   std::integer_sequence<int, K...>) {
+    f32x2 t[kQuad2ShareClasses];
+    (quad2_share_step<Cfg, R, C, K>(acc, t, s, w), ...);
+}
+// Source row R of the strip's window: pairs row[0 .. 6] = columns 0 .. 6 (row[7] is loaded with them and unused).  Period row R opens here.
+template <typename Cfg, int R, int... C>
+__device__ __forceinline__ void quad2_share_row(f32x2 (&acc)[8 * Cfg::kStripRows], const f32x2* wb, const f32x2 (&w)[kQuad2ShareClasses / 2],
+                                                std::integer_sequence<int, C...>) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    if constexpr (R < Cfg::kStripRows) {
+#pragma unroll
+        for (int o = 0; o < 8; ++o) acc[8 * R + o] = f32x2{0.f, 0.f};
+    }
+    const f32x4* p4 = reinterpret_cast<const f32x4*>(wb + R * Cfg::kLdsPitch);
+    f32x2 row[8];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const f32x4 v = p4[m];
+        row[2 * m] = f32x2{v.x, v.y};
+        row[2 * m + 1] = f32x2{v.z, v.w};
+    }
+    (quad2_share_sample<Cfg, R, C>(acc, row[C], w, std::make_integer_sequence<int, kQuad2ShareClasses + Cfg::kMulLead>{}), ...);
+}
+// The whole strip, source rows 0 .. H + 4: after row R, period row R - 5 is complete and leaves by store(integral_constant<R - 5>).
+template <typename Cfg, int... R, typename Store>
+__device__ __forceinline__ void quad2_share_strip(f32x2 (&acc)[8 * Cfg::kStripRows], const f32x2* wb, const f32x2 (&w)[kQuad2ShareClasses / 2],
+                                                  std::integer_sequence<int, R...>, Store&& store) {
+    ((quad2_share_row<Cfg, R>(acc, wb, w, std::make_integer_sequence<int, 7>{}), store(std::integral_constant<int, R - 5>{})), ...);
 }
 
-template <typename T>
+template <typename T, int RG>
 __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const PlaneIO& io, float* lds) {
-    using Cfg = Quad2ShareCfg;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    using Cfg = Quad2ShareCfg<RG>;
     f32x2* const tile = reinterpret_cast<f32x2*>(lds) + 2;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1401,38 +1440,26 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
 #pragma unroll
     for (int k = 0; k < kQuad2ShareClasses / 2; ++k) w[k] = f32x2{a.share_w[2 * k], a.share_w[2 * k + 1]};
     const uint32_t xoff = static_cast<uint32_t>(a.ix0 + 2 * ia) * static_cast<uint32_t>(sizeof(T));
-    for (int blk = 0; blk < Cfg::kBlocksPerWave; ++blk) {
-        const int jb = 2 * (wave * Cfg::kBlocksPerWave + blk);  // the block's first period row in the tile
-        if (j0 + jb >= a.nj) break;                             // wave-uniform: bottom tiles
+    for (int st = 0; st < Cfg::kStripsPerWave; ++st) {
+        const int jb = Cfg::kStripRows * (wave * Cfg::kStripsPerWave + st);  // the strip's first period row in the tile
+        if (j0 + jb >= a.nj) break;                                          // wave-uniform: bottom tiles
         const f32x2* wb = tile + jb * Cfg::kLdsPitch + 2 * lane;
-        f32x2 acc[16];
+        f32x2 acc[8 * Cfg::kStripRows];
+        quad2_share_strip<Cfg>(acc, wb, w, std::make_integer_sequence<int, Cfg::kStripRows + 5>{}, [&](auto PR) {
+            constexpr int pr = decltype(PR)::value;
+            if constexpr (pr >= 0) {
+                const int j = j0 + jb + pr;
+                if (j < a.nj) {  // wave-uniform: partial strips of bottom tiles
 #pragma unroll
-        for (int o = 0; o < 16; ++o) acc[o] = f32x2{0.f, 0.f};
-#define JINC_SHARE_ROW(R)                                                                                 \
-    {                                                                                                     \
-        const f32x4* p4 = reinterpret_cast<const f32x4*>(wb + (R) * Cfg::kLdsPitch);                      \
-        f32x2 row[8];                                                                                     \
-        _Pragma("unroll") for (int m = 0; m < 4; ++m) {                                                   \
-            const f32x4 v = p4[m];                                                                        \
-            row[2 * m] = f32x2{v.x, v.y};                                                                 \
-            row[2 * m + 1] = f32x2{v.z, v.w};                                                             \
-        }                                                                                                 \
-        quad2_share_row<R>(acc, row, w, std::make_integer_sequence<int, 7>{});                            \
-    }
-        JINC_SHARE_ROW(0) JINC_SHARE_ROW(1) JINC_SHARE_ROW(2) JINC_SHARE_ROW(3) JINC_SHARE_ROW(4) JINC_SHARE_ROW(5) JINC_SHARE_ROW(6)
-#undef JINC_SHARE_ROW
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) {
-            const int j = j0 + jb + pr;
-            if (j >= a.nj) break;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const uint32_t so = static_cast<uint32_t>(a.iy0 + 2 * j + q) * static_cast<uint32_t>(io.dst_pitch);
-                const f32x2* r = acc + 4 * (2 * pr + q);
-                store_quad_buf<T>(d0, xoff, so, f32x2{r[0].x, r[1].x}, f32x2{r[2].x, r[3].x}, io.peak, b_ok);
-                if (f1_ok) store_quad_buf<T>(d1, xoff, so, f32x2{r[0].y, r[1].y}, f32x2{r[2].y, r[3].y}, io.peak, b_ok);
+                    for (int q = 0; q < 2; ++q) {
+                        const uint32_t so = static_cast<uint32_t>(a.iy0 + 2 * j + q) * static_cast<uint32_t>(io.dst_pitch);
+                        const f32x2* r = acc + 4 * (2 * pr + q);
+                        store_quad_buf<T>(d0, xoff, so, f32x2{r[0].x, r[1].x}, f32x2{r[2].x, r[3].x}, io.peak, b_ok);
+                        if (f1_ok) store_quad_buf<T>(d1, xoff, so, f32x2{r[0].y, r[1].y}, f32x2{r[2].y, r[3].y}, io.peak, b_ok);
+                    }
+                }
             }
-        }
+        });
     }
 }
 
@@ -1442,24 +1469,30 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
 constexpr uint32_t kQuad2InnerTap3 = PeriodicArgs::kQuadInnerTap3;
 // NT: taps per kernel row -- 6, or 7 for the 6-row x 7-column support (chroma planes sited as MPEG-2 at 2x: the disc spans six
 // source rows but, shifted by an eighth of a sample, seven columns; PeriodicArgs::quad_taps).
+// The integer kInnerTap3 instances have the frame-pair form (quad2_share_body); the full-tile one's strips of 8 period rows hold 96
+// accumulators and run at four waves per SIMD (128 VGPRs), every other instance at six (80).
+template <typename T, uint32_t INNER, int NT>
+constexpr bool quad2_share_instance() { return !is_float_sample_v<T> && INNER == kQuad2InnerTap3 && NT == 6; }
 template <typename T, int RG, uint32_t INNER, int NT = 6>
-__global__ __launch_bounds__(256, 6) void ewa_periodic_quad2_kernel(const PeriodicArgs a, const PlaneIO io) {
+__global__ __launch_bounds__(256, (quad2_share_instance<T, INNER, NT>() && RG == 8 ? 4 : 6)) void ewa_periodic_quad2_kernel(const PeriodicArgs a,
+                                                                                                                       const PlaneIO io) {
     using Cfg = Quad2Cfg<RG>;
     constexpr int FS = Cfg::FS;
     static_assert(RG % 4 == 0, "the four waves of a workgroup take RG / 4 row groups each");
     // (two words in front of the tile: row 0's "column -1", see the edge columns below; the tile stays 8-byte aligned)
     // The frame-pair form (quad2_share_body) of the integer kInnerTap3 instances stages its tile into the same words.
-    constexpr bool kShare = !is_float_sample_v<T> && INNER == kQuad2InnerTap3 && NT == 6;
+    constexpr bool kShare = quad2_share_instance<T, INNER, NT>();
+    using ShareCfg = Quad2ShareCfg<RG>;
     constexpr int kWords = 2 + Cfg::kLdsRows * Cfg::kLdsPitch;
     if constexpr (kShare && RG == 8) {  // (what follows is dead code here: neither its registers nor its tile are allocated)
-        __shared__ __attribute__((aligned(16))) float share_words[Quad2ShareCfg::kLdsFloats];
-        quad2_share_body<T>(a, io, share_words);
+        __shared__ __attribute__((aligned(16))) float share_words[ShareCfg::kLdsFloats];
+        quad2_share_body<T, RG>(a, io, share_words);
         return;
     }
-    __shared__ __attribute__((aligned(16))) float tile_words[kShare && Quad2ShareCfg::kLdsFloats > kWords ? Quad2ShareCfg::kLdsFloats : kWords];
+    __shared__ __attribute__((aligned(16))) float tile_words[kShare && ShareCfg::kLdsFloats > kWords ? ShareCfg::kLdsFloats : kWords];
     if constexpr (kShare) {
         if (quad2_share_runs<RG>(io)) {  // workgroup-uniform
-            quad2_share_body<T>(a, io, tile_words);
+            quad2_share_body<T, RG>(a, io, tile_words);
             return;
         }
     }
@@ -2109,8 +2142,9 @@ int launch_periodic_quad2_t(const PeriodicArgs& pa, const PlaneIO& io, hipStream
         bool share = false;
         if constexpr (!is_float_sample_v<T>) share = true;
         if (share && pa.quad_share) {  // integer planes: the frame-pair form, on tiles of its own (quad2_share_body)
+            using ShareCfg = Quad2ShareCfg<RG>;
             if (quad2_share_runs<RG>(io))
-                grid = dim3((pa.ni + Quad2ShareCfg::kTileCols - 1) / Quad2ShareCfg::kTileCols, (pa.nj + Quad2ShareCfg::kTileRows - 1) / Quad2ShareCfg::kTileRows,
+                grid = dim3((pa.ni + ShareCfg::kTileCols - 1) / ShareCfg::kTileCols, (pa.nj + ShareCfg::kTileRows - 1) / ShareCfg::kTileRows,
                             (io.nframes + 1) / 2);
         } else if (share) {  // ... whose instance needs the symmetry classes: a plan that does not follow them takes every tap
             hipLaunchKernelGGL((ewa_periodic_quad2_kernel<T, RG, 0u>), grid, dim3(256, 1, 1), 0, stream, pa, io);
