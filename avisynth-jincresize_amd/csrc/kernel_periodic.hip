@@ -1188,10 +1188,24 @@ __device__ __forceinline__ void stage_edge_column(const PeriodicArgs& a, const P
     }
 }
 
-// ES: floats per staged sample (2: the frame-pair tile of the symmetry-class form, `tile` pointing at the frame's half of the first pair).
-template <typename T, typename Cfg, int NR, int NC, int ES = 1>
-__device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const PlaneIO& io, const float* tile, int tile_x, int j0, int wave, int lane,
-                                                   BufferRsrc drsrc) {
+// wave_shl:1 -- lane l takes lane l + 1's value
+__device__ __forceinline__ float wave_shl1(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
+}
+__device__ __forceinline__ f32x2 wave_shl1(f32x2 v) { return f32x2{wave_shl1(v.x), wave_shl1(v.y)}; }
+__device__ __forceinline__ float frame_lo(float v) { return v; }
+__device__ __forceinline__ float frame_lo(f32x2 v) { return v.x; }
+__device__ __forceinline__ float frame_hi(float v) { return v; }
+__device__ __forceinline__ float frame_hi(f32x2 v) { return v.y; }
+
+// V: a staged sample -- float, or the f32x2 of the frame-pair tile (quad2_share_body): both frames' chains run in the packed halves
+// (v_pk_mul_f32 with the coefficient broadcast, v_pk_add_f32: each half is the per-frame chain, same order, un-fused) and leave to
+// drsrc and, when hi_ok, drsrc_hi.  ES: staged samples per tile word of type V (2: one frame's half of the frame-pair tile, read as floats
+// with `tile` pointing at that half of the first pair -- the half-tile instance, whose 80 VGPRs do not hold a window of pairs).
+template <typename T, typename Cfg, int NR, int NC, typename V = float, int ES = 1>
+__device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const PlaneIO& io, const V* tile, int tile_x, int j0, int wave, int lane,
+                                                   BufferRsrc drsrc, BufferRsrc drsrc_hi, bool hi_ok) {
+    constexpr bool kPair = !std::is_same_v<V, float>;
     constexpr int NCP = (NC + 3) & ~3;  // floats per coefficient row
     for (int s = 0; s < 2; ++s) {
         const int n = a.edge.n[s];
@@ -1204,25 +1218,24 @@ __device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const 
         // shifts (read from LDS, the lanes' rows lie a pitch apart: four banks for 64 lanes, a 16-way conflict per read.  Measured
         // level with this form all the same -- round5/edge_cols_ab.log -- the chains are what the edge tiles pay for).
         static_assert(Cfg::kLdsRows <= 64, "one tile row per lane");
-        const float* wp = tile + ((lane < Cfg::kLdsRows ? lane : 0) * Cfg::kLdsPitch + a.edge.lds_col[s]) * ES;
-        float w[NR][NC];
+        const V* wp = tile + ((lane < Cfg::kLdsRows ? lane : 0) * Cfg::kLdsPitch + a.edge.lds_col[s]) * ES;
+        V w[NR][NC];
 #pragma unroll
         for (int lx = 0; lx < NC; ++lx) w[0][lx] = wp[lx * ES];
 #pragma unroll
         for (int ly = 1; ly < NR; ++ly)
 #pragma unroll
-            for (int lx = 0; lx < NC; ++lx)  // wave_shl:1 -- lane l takes lane l + 1's value
-                w[ly][lx] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, w[ly - 1][lx]), 0x130, 0xf, 0xf, false));
+            for (int lx = 0; lx < NC; ++lx) w[ly][lx] = wave_shl1(w[ly - 1][lx]);
         const uint32_t row_off = static_cast<uint32_t>(a.iy0 + 2 * (j0 + lane) + q) * static_cast<uint32_t>(io.dst_pitch);
         for (int k0 = k_begin; k0 < k_end; k0 += 4) {  // wave-uniform
             const int nk = k_end - k0 < 4 ? k_end - k0 : 4;
-            float r[4];
+            V r[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                r[k] = 0.f;
+                r[k] = V{};
                 if (k < nk) {  // wave-uniform
                     const JINC_CONSTANT float* cs = (const JINC_CONSTANT float*)(a.edge.coeffs) + ((s * PeriodicArgs::EdgeColumns::kMaxPerSide + k0 + k) * 2 + q) * (NR * NCP);
-                    float acc = 0.f;
+                    V acc = V{};
 #pragma unroll
                     for (int ly = 0; ly < NR; ++ly)
 #pragma unroll
@@ -1232,22 +1245,28 @@ __device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const 
             }
             if (!live) continue;
             const uint32_t voff = row_off + static_cast<uint32_t>(a.edge.x0[s] + k0) * static_cast<uint32_t>(sizeof(T));
-            if (nk == 4) {
-                if constexpr (std::is_same_v<T, uint8_t>) {
-                    uint32_t v = __builtin_amdgcn_cvt_pk_u8_f32(r[0], 0u, 0u);
-                    v = __builtin_amdgcn_cvt_pk_u8_f32(r[1], 1u, v);
-                    v = __builtin_amdgcn_cvt_pk_u8_f32(r[2], 2u, v);
-                    v = __builtin_amdgcn_cvt_pk_u8_f32(r[3], 3u, v);
-                    __builtin_amdgcn_raw_buffer_store_b32(v, drsrc, voff, 0, 0);
+            auto store = [&](BufferRsrc d, auto frame) {
+                if (nk == 4) {
+                    if constexpr (std::is_same_v<T, uint8_t>) {
+                        uint32_t v = __builtin_amdgcn_cvt_pk_u8_f32(frame(r[0]), 0u, 0u);
+                        v = __builtin_amdgcn_cvt_pk_u8_f32(frame(r[1]), 1u, v);
+                        v = __builtin_amdgcn_cvt_pk_u8_f32(frame(r[2]), 2u, v);
+                        v = __builtin_amdgcn_cvt_pk_u8_f32(frame(r[3]), 3u, v);
+                        __builtin_amdgcn_raw_buffer_store_b32(v, d, voff, 0, 0);
+                    } else {
+                        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+                        const u32x2 v = {round_pair_u16(frame(r[0]), frame(r[1]), io.peak), round_pair_u16(frame(r[2]), frame(r[3]), io.peak)};
+                        __builtin_amdgcn_raw_buffer_store_b64(v, d, voff, 0, 0);
+                    }
                 } else {
-                    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-                    const u32x2 v = {round_pair_u16(r[0], r[1], io.peak), round_pair_u16(r[2], r[3], io.peak)};
-                    __builtin_amdgcn_raw_buffer_store_b64(v, drsrc, voff, 0, 0);
-                }
-            } else {
 #pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    if (k < nk) store_sample_buf<T>(drsrc, voff + static_cast<uint32_t>(k * sizeof(T)), 0, r[k], io.peak);
+                    for (int k = 0; k < 3; ++k)
+                        if (k < nk) store_sample_buf<T>(d, voff + static_cast<uint32_t>(k * sizeof(T)), 0, frame(r[k]), io.peak);
+                }
+            };
+            store(drsrc, [](V v) { return frame_lo(v); });
+            if constexpr (kPair) {
+                if (hi_ok) store(drsrc_hi, [](V v) { return frame_hi(v); });
             }
         }
     }
@@ -1270,11 +1289,11 @@ __device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const 
 // still meets its taps in (ly, lx) order: ly and lx grow with the source row and column.  Three taps per row phase are zero (leaving
 // them out is exact for integer samples, see Quad2Cfg).  The last pair of an odd frame count stages the low frame twice and stores
 // it once.  Per output pair the per-frame form above issues 34 multiplies + 34 adds, strips of H = 2 (2 x 2-period blocks)
-// 21.9 + 31, strips of H = 8 15.5 + 31.
-//   Full tiles (RG 8, long batches): 128 x 32 periods, one strip of 8 period rows per wave, 37 staged rows of f32 pairs (40.3 KB of
+// 21.9 + 31, strips of H = 8 15.5 + 31; a chain's first product opens it (quad2_share_adds), so one add of the 31 is not issued.
+//   Full tiles (RG 8, long batches): 128 x 32 periods, one strip of 8 period rows per wave, 37 staged rows of f32 pairs (40.9 KB of
 // LDS: four workgroups per CU, as many as the 96 live accumulators leave waves per SIMD).  Its products come one class at a time,
 // the adds of each behind the next multiply: all of a sample's products at once would not fit beside the accumulators.
-//   Half tiles (RG 4, short batches): 128 x 16 periods, two strips of 2 period rows per wave (22.9 KB, six workgroups per CU), all
+//   Half tiles (RG 4, short batches): 128 x 16 periods, two strips of 2 period rows per wave (23.2 KB, six workgroups per CU), all
 // of a sample's products in front of their adds, so that no add waits on the multiply just issued.
 template <int H, int StripsPerWave, int MulLead>
 struct Quad2ShareTile {
@@ -1284,9 +1303,11 @@ struct Quad2ShareTile {
     static constexpr int kMulLead = MulLead;                 // multiplies issued ahead of the adds that take them
     static constexpr int kTileRows = 4 * H * StripsPerWave;  // period rows per tile
     static constexpr int kLdsCols = kTileCols + 6;           // (pairs) as Quad2Cfg: the edge columns' windows reach column 133
-    static constexpr int kLdsPitch = 136;                    // pairs: rows 16-byte aligned, a spare pair per row (column -1 of the next)
+    static constexpr int kLdsSpare = 4;                      // pairs between the rows: what the staging's dwords hold beside the row,
+    static constexpr int kLdsPitch = kLdsCols + kLdsSpare;   // and column -1 of the next row (pairs: rows 16-byte aligned)
     static constexpr int kLdsRows = kTileRows + 5;
-    static constexpr int kLdsFloats = 2 * (2 + kLdsRows * kLdsPitch);  // two pairs in front of the tile: row 0's column -1
+    static constexpr int kLdsFloats = 2 * (kLdsSpare + kLdsRows * kLdsPitch);  // the spare pairs in front of row 0 too
+    static_assert(kLdsPitch % 2 == 0 && kLdsSpare % 2 == 0, "16-byte aligned rows");
     static_assert(8 * H <= 64, "a strip's outputs index one 64-bit mask");
 };
 template <int RG>
@@ -1312,6 +1333,28 @@ constexpr uint64_t quad2_share_outs(int r, int c, int k) {
     return m;
 }
 
+// The outputs among quad2_share_outs(r, c, k) whose chain sample (r, c) opens: it is their first tap with a non-zero coefficient.
+template <int H>
+constexpr uint64_t quad2_share_opens(int r, int c, int k) {
+    const uint64_t outs = r < H ? quad2_share_outs<H>(r, c, k) : 0;
+    uint64_t m = 0;
+    for (int o = 8 * r; outs != 0 && o < 8 * r + 8; ++o) {  // period row r's outputs: their kernel row 0 is source row r
+        if (!((outs >> o) & 1u)) continue;
+        const int p = o & 1, q = (o >> 2) & 1, lx = c - ((o & 3) >> 1);
+        bool first = true;
+        for (int l = 0; l < lx; ++l) first = first && quad2_share_class(quad2_share_m(p, l), quad2_share_m(q, 0)) < 0;
+        if (first) m |= uint64_t{1} << o;
+    }
+    return m;
+}
+constexpr bool quad2_share_row0_opens(int p, int q) {  // kernel row 0 has a non-zero tap: every chain opens in its first source row
+    for (int l = 0; l < 6; ++l)
+        if (quad2_share_class(quad2_share_m(p, l), quad2_share_m(q, 0)) >= 0) return true;
+    return false;
+}
+static_assert(quad2_share_row0_opens(0, 0) && quad2_share_row0_opens(1, 0) && quad2_share_row0_opens(0, 1) && quad2_share_row0_opens(1, 1),
+              "no accumulator is zeroed: the first source row of a period row must open all eight of its chains");
+
 // Sample (R, C) times class K (the high / low half of SGPR pair K / 2, for both frames), where the strip needs that product.
 template <int H, int R, int C, int K>
 __device__ __forceinline__ void quad2_share_mul(f32x2& t, f32x2 s, const f32x2 (&w)[kQuad2ShareClasses / 2]) {
@@ -1322,14 +1365,23 @@ __device__ __forceinline__ void quad2_share_mul(f32x2& t, f32x2 s, const f32x2 (
             asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(s), "s"(w[K >> 1]));
     }
 }
-// ... added into every chain that takes it
+// ... added into every chain that takes it.  A chain that this product opens takes the product itself: no accumulator is zeroed and
+// no 0 + p is added.  The opening chains come last, so the product's register becomes the accumulator of one of them without a move
+// (a product that opens several chains is copied for the others).  p and 0 + p differ only for p = -0 (a zero sample times a negative
+// coefficient).  A partial sum of -0 behaves as +0 in every later add, except that a chain of nothing but zero products may end as -0
+// where it ended as +0: the integer stores (v_cvt_pk_u8_f32, round_pair16) write 0 for both.  Float planes would keep the sign, and
+// do not run this body (quad2_share_instance).
 template <int H, int R, int C, int K>
 __device__ __forceinline__ void quad2_share_adds(f32x2 (&acc)[8 * H], f32x2 t) {
-    constexpr uint64_t outs = quad2_share_outs<H>(R, C, K);
+    constexpr uint64_t outs = quad2_share_outs<H>(R, C, K), opens = quad2_share_opens<H>(R, C, K);
 #pragma unroll
     for (int o = 0; o < 8 * H; ++o)
         if constexpr (outs != 0)
-            if ((outs >> o) & 1u) asm("v_pk_add_f32 %0, %0, %1" : "+v"(acc[o]) : "v"(t));
+            if (((outs & ~opens) >> o) & 1u) asm("v_pk_add_f32 %0, %0, %1" : "+v"(acc[o]) : "v"(t));
+#pragma unroll
+    for (int o = 0; o < 8 * H; ++o)
+        if constexpr (opens != 0)
+            if ((opens >> o) & 1u) acc[o] = t;
 }
 // Step K of a sample: the multiply of class K, then the adds of class K - kMulLead.
 template <typename Cfg, int R, int C, int K>
@@ -1344,15 +1396,11 @@ __device__ __forceinline__ void quad2_share_sample(f32x2 (&acc)[8 * Cfg::kStripR
     f32x2 t[kQuad2ShareClasses];
     (quad2_share_step<Cfg, R, C, K>(acc, t, s, w), ...);
 }
-// Source row R of the strip's window: pairs row[0 .. 6] = columns 0 .. 6 (row[7] is loaded with them and unused).  Period row R opens here.
+// Source row R of the strip's window: pairs row[0 .. 6] = columns 0 .. 6 (row[7] is loaded with them and unused).  Period row R's chains open here (quad2_share_adds).
 template <typename Cfg, int R, int... C>
 __device__ __forceinline__ void quad2_share_row(f32x2 (&acc)[8 * Cfg::kStripRows], const f32x2* wb, const f32x2 (&w)[kQuad2ShareClasses / 2],
                                                 std::integer_sequence<int, C...>) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    if constexpr (R < Cfg::kStripRows) {
-#pragma unroll
-        for (int o = 0; o < 8; ++o) acc[8 * R + o] = f32x2{0.f, 0.f};
-    }
     const f32x4* p4 = reinterpret_cast<const f32x4*>(wb + R * Cfg::kLdsPitch);
     f32x2 row[8];
 #pragma unroll
@@ -1373,7 +1421,7 @@ __device__ __forceinline__ void quad2_share_strip(f32x2 (&acc)[8 * Cfg::kStripRo
 template <typename T, int RG>
 __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const PlaneIO& io, float* lds) {
     using Cfg = Quad2ShareCfg<RG>;
-    f32x2* const tile = reinterpret_cast<f32x2*>(lds) + 2;
+    f32x2* const tile = reinterpret_cast<f32x2*>(lds) + Cfg::kLdsSpare;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int tile_x, tile_y;
@@ -1384,35 +1432,86 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
     const bool f1_ok = f0 + 1 < static_cast<size_t>(io.nframes);  // the last pair of an odd count: the high half repeats the low frame
     const size_t f1 = f1_ok ? f0 + 1 : f0;
     const bool edge_tile = edge_tile_of<T>(a, tile_x);
-    {   // stage both frames' source tiles as f32 pairs, all loads in front of the LDS writes (see ewa_periodic_kernel)
+    {   // Stage both frames' source tiles as f32 pairs, all loads in front of the LDS writes (see ewa_periodic_kernel).  A lane loads
+        // the aligned dword(s) that hold four samples of a row, through a descriptor over the frame's plane (widened to whole dwords:
+        // an aligned dword lies in one page, and a dword past the plane's last one reads as zero), the row's offset in an SGPR.  The
+        // dword that holds the tile's first sample starts up to three samples in front of it: the row lands that far to the left in
+        // the tile (a wave-uniform shift per row and frame, whatever the pitch), and the samples in front of column 0 or behind
+        // column kLdsCols - 1 fall into the spare pairs between the rows.
         const int gx0 = a.min_sx + i0;
         const int gy0 = a.min_sy + j0;
         const char* sb0 = static_cast<const char*>(io.src) + f0 * io.src_frame_stride;
         const char* sb1 = static_cast<const char*>(io.src) + f1 * io.src_frame_stride;
         constexpr int kRowsPerWave = (Cfg::kLdsRows + 3) / 4;
-        constexpr int kColsPerLane = (Cfg::kLdsCols + 63) / 64;
-        T s0[kRowsPerWave][kColsPerLane], s1[kRowsPerWave][kColsPerLane];
+        constexpr int kDwords = static_cast<int>(sizeof(T));              // per lane and row: four samples
+        constexpr int kLoadLanes = (Cfg::kLdsCols + 3 + 3) / 4;           // the shifted row's dwords (x kDwords)
+        static_assert(kLoadLanes <= 64 && 4 * (kLoadLanes - 1) < Cfg::kLdsPitch - 1 && 4 * (kLoadLanes - 2) + 3 < Cfg::kLdsPitch - 1 && Cfg::kLdsSpare > 3,
+                      "the last lane's first sample, the other lanes' four and the three samples in front of a row: spare pairs, not the next row's column -1");
+        const uint32_t plane_bytes = static_cast<uint32_t>(a.src_h - 1) * static_cast<uint32_t>(io.src_pitch) + static_cast<uint32_t>(a.src_w) * static_cast<uint32_t>(sizeof(T));
+        const uint32_t lead0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(sb0)) & 3u, lead1 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(sb1)) & 3u;
+        const BufferRsrc rs0 = make_rsrc(const_cast<char*>(sb0) - lead0, (plane_bytes + lead0 + 3u) & ~3u);  // wave-uniform
+        const BufferRsrc rs1 = make_rsrc(const_cast<char*>(sb1) - lead1, (plane_bytes + lead1 + 3u) & ~3u);
+        const uint32_t lead[2] = {lead0, lead1};
+        const uint32_t voff = static_cast<uint32_t>(lane) * (4u * kDwords);
+        uint32_t d[kRowsPerWave][2][kDwords];
+        int shift[kRowsPerWave][2];  // samples, wave-uniform
 #pragma unroll
         for (int i = 0; i < kRowsPerWave; ++i) {
             int gy = gy0 + wave + 4 * i;
             gy = gy < a.src_h ? gy : a.src_h - 1;
-            const T* r0 = reinterpret_cast<const T*>(sb0 + static_cast<size_t>(gy) * io.src_pitch);
-            const T* r1 = reinterpret_cast<const T*>(sb1 + static_cast<size_t>(gy) * io.src_pitch);
 #pragma unroll
-            for (int k = 0; k < kColsPerLane; ++k) {
-                int gx = gx0 + lane + 64 * k;
-                gx = gx < a.src_w ? gx : a.src_w - 1;
-                s0[i][k] = r0[gx];
-                s1[i][k] = r1[gx];
+            for (int f = 0; f < 2; ++f) {
+                const uint32_t so = lead[f] + static_cast<uint32_t>(gy) * static_cast<uint32_t>(io.src_pitch) + static_cast<uint32_t>(gx0) * static_cast<uint32_t>(sizeof(T));
+                shift[i][f] = static_cast<int>((so & 3u) / sizeof(T));
+#pragma unroll
+                for (int k = 0; k < kDwords; ++k) d[i][f][k] = __builtin_amdgcn_raw_buffer_load_b32(f ? rs1 : rs0, voff + 4u * k, so & ~3u, 0);
             }
         }
+        float* const tf = reinterpret_cast<float*>(tile) + 8 * lane;
+        auto sample = [&](int i, int f, int b) {
+            if constexpr (sizeof(T) == 1) return static_cast<float>((d[i][f][0] >> (8 * b)) & 0xffu);
+            else return static_cast<float>((d[i][f][b >> 1] >> (16 * (b & 1))) & 0xffffu);
+        };
+        if (lane < kLoadLanes) {
 #pragma unroll
-        for (int i = 0; i < kRowsPerWave; ++i) {
-            const int r = wave + 4 * i;
+            for (int i = 0; i < kRowsPerWave; ++i) {
+                const int r = wave + 4 * i;
+                if (r >= Cfg::kLdsRows) continue;  // wave-uniform
 #pragma unroll
-            for (int k = 0; k < kColsPerLane; ++k) {
-                const int c = lane + 64 * k;
-                if (r < Cfg::kLdsRows && c < Cfg::kLdsCols) tile[r * Cfg::kLdsPitch + c] = f32x2{to_float(s0[i][k]), to_float(s1[i][k])};
+                for (int f = 0; f < 2; ++f) tf[2 * (r * Cfg::kLdsPitch - shift[i][f]) + f] = sample(i, f, 0);
+            }
+        }
+        if (lane < kLoadLanes - 1) {
+#pragma unroll
+            for (int i = 0; i < kRowsPerWave; ++i) {
+                const int r = wave + 4 * i;
+                if (r >= Cfg::kLdsRows) continue;  // wave-uniform
+#pragma unroll
+                for (int f = 0; f < 2; ++f)
+#pragma unroll
+                    for (int b = 1; b < 4; ++b) tf[2 * (r * Cfg::kLdsPitch - shift[i][f] + b) + f] = sample(i, f, b);
+            }
+        }
+        // The tile column that reaches past the plane's last column: those columns replicate it (the dwords held the pitch's padding, the
+        // next row or zero there).  Behind the writes above, by the wave that wrote the row.
+        if (gx0 + Cfg::kLdsCols > a.src_w) {  // workgroup-uniform
+            float* const tr = reinterpret_cast<float*>(tile);
+#pragma unroll
+            for (int i = 0; i < kRowsPerWave; ++i) {
+                const int r = wave + 4 * i;
+                if (r >= Cfg::kLdsRows) continue;  // wave-uniform
+                int gy = gy0 + r;
+                gy = gy < a.src_h ? gy : a.src_h - 1;
+                const float v0 = to_float(reinterpret_cast<const T*>(sb0 + static_cast<size_t>(gy) * io.src_pitch)[a.src_w - 1]);
+                const float v1 = to_float(reinterpret_cast<const T*>(sb1 + static_cast<size_t>(gy) * io.src_pitch)[a.src_w - 1]);
+#pragma unroll
+                for (int k = 0; k < (Cfg::kLdsCols + 63) / 64; ++k) {
+                    const int c = lane + 64 * k;
+                    if (gx0 + c >= a.src_w && c < Cfg::kLdsCols) {
+                        tr[2 * (r * Cfg::kLdsPitch + c)] = v0;
+                        tr[2 * (r * Cfg::kLdsPitch + c) + 1] = v1;
+                    }
+                }
             }
         }
         // an edge window that starts one column in front of the tile: that column into the pair in front of each row (stage_edge_column)
@@ -1421,8 +1520,9 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
         if (in_front && wave == 0 && lane < Cfg::kLdsRows && gx0 > 0) {
             int gy = gy0 + lane;
             gy = gy < a.src_h ? gy : a.src_h - 1;
-            tile[lane * Cfg::kLdsPitch - 1] = f32x2{to_float(reinterpret_cast<const T*>(sb0 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1]),
-                                                    to_float(reinterpret_cast<const T*>(sb1 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1])};
+            float* const tc = reinterpret_cast<float*>(tile + lane * Cfg::kLdsPitch - 1);
+            tc[0] = to_float(reinterpret_cast<const T*>(sb0 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1]);
+            tc[1] = to_float(reinterpret_cast<const T*>(sb1 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1]);
         }
     }
     __syncthreads();
@@ -1430,8 +1530,12 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
     const BufferRsrc d0 = make_rsrc(static_cast<char*>(io.dst) + f0 * io.dst_frame_stride, plane_bytes);  // wave-uniform
     const BufferRsrc d1 = make_rsrc(static_cast<char*>(io.dst) + f1 * io.dst_frame_stride, plane_bytes);
     if (edge_tile) {
-        quad2_edge_columns<T, Cfg, 6, 7, 2>(a, io, reinterpret_cast<const float*>(tile), tile_x, j0, wave, lane, d0);
-        if (f1_ok) quad2_edge_columns<T, Cfg, 6, 7, 2>(a, io, reinterpret_cast<const float*>(tile) + 1, tile_x, j0, wave, lane, d1);
+        if constexpr (RG == 8) {
+            quad2_edge_columns<T, Cfg, 6, 7, f32x2>(a, io, tile, tile_x, j0, wave, lane, d0, d1, f1_ok);
+        } else {
+            quad2_edge_columns<T, Cfg, 6, 7, float, 2>(a, io, reinterpret_cast<const float*>(tile), tile_x, j0, wave, lane, d0, d0, false);
+            if (f1_ok) quad2_edge_columns<T, Cfg, 6, 7, float, 2>(a, io, reinterpret_cast<const float*>(tile) + 1, tile_x, j0, wave, lane, d1, d1, false);
+        }
     }
     const int ia = i0 + 2 * lane;  // the lane's first period
     if (ia >= a.ni) return;        // no barrier below
@@ -1546,7 +1650,7 @@ __global__ __launch_bounds__(256, (quad2_share_instance<T, INNER, NT>() && RG ==
     const BufferRsrc drsrc = make_rsrc(static_cast<char*>(io.dst) + frame * io.dst_frame_stride,
                                        static_cast<uint32_t>(io.dst_pitch) * a.dst_h);  // wave-uniform
     if constexpr (!is_float_sample_v<T>) {
-        if (edge_tile) quad2_edge_columns<T, Cfg, 6, 7>(a, io, tile, tile_x, j0, wave, lane, drsrc);
+        if (edge_tile) quad2_edge_columns<T, Cfg, 6, 7>(a, io, tile, tile_x, j0, wave, lane, drsrc, drsrc, false);
     }
     const int ia = i0 + 2 * lane;  // the lane's first period
     if (ia >= a.ni) return;        // no barrier below
@@ -1812,7 +1916,7 @@ __global__ __launch_bounds__(256, 5) void ewa_periodic_quad2x8_kernel(const Peri
     const BufferRsrc drsrc = make_rsrc(static_cast<char*>(io.dst) + frame * io.dst_frame_stride,
                                        static_cast<uint32_t>(io.dst_pitch) * a.dst_h);  // wave-uniform
     if constexpr (!is_float_sample_v<T>) {
-        if (edge_tile) quad2_edge_columns<T, Cfg, 8, 9>(a, io, tile, tile_x, j0, wave, lane, drsrc);
+        if (edge_tile) quad2_edge_columns<T, Cfg, 8, 9>(a, io, tile, tile_x, j0, wave, lane, drsrc, drsrc, false);
     }
     const int ia = i0 + 2 * lane;
     if (ia >= a.ni) return;  // no barrier below
