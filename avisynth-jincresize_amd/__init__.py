@@ -85,7 +85,7 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_set_pipeline_group", "jinc_filter_pipeline_group", "jinc_filter_flush", "jinc_filter_adopt_host_range", "jinc_filter_release_host_range", "jinc_batch_set_affinity", "jinc_batch_device_cpus", "jinc_debug_numa_cpus", "jinc_debug_batch_set_registrars", "jinc_debug_batch_refused", "jinc_debug_host_registrations", "jinc_debug_last_call", "jinc_filter_direct_premise", "jinc_debug_valu_pair_probe", "jinc_debug_clock_sampler_start", "jinc_debug_clock_sampler_stop",
            "jinc_filter_submit", "jinc_filter_wait", "jinc_shard_device", "jinc_batch_create", "jinc_batch_devices",
            "jinc_batch_device_of_frame", "jinc_batch_process", "jinc_batch_free", "jinc_batch_last_error",
-           "jinc_filter_last_instance", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share"]
+           "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -181,6 +181,7 @@ def lib():
         L.jinc_filter_last_instance.argtypes = [C.c_void_p, C.c_int]
         L.jinc_filter_last_instance.restype = C.c_char_p
         L.jinc_filter_last_border.argtypes = [C.c_void_p, C.c_int]
+        L.jinc_filter_last_finite_flags.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.jinc_debug_last_instance.restype = C.c_char_p
         L.jinc_debug_set_knob.argtypes = [C.c_int, C.c_double]
         L.jinc_debug_clear_knob.argtypes = [C.c_int]
@@ -761,6 +762,19 @@ class Filter:
     def last_instance(self, table: int = 0) -> str:
         """... with its template arguments, as rocprofv3 names it (the periodic family; the plain name otherwise)."""
         return lib().jinc_filter_last_instance(self._h, int(table)).decode()
+
+    def last_finite_flags(self, plane: int = 0) -> Optional[np.ndarray]:
+        """Float planes on the trimmed support: the flags the most recent frame call raised for `plane`, one uint32 per frame of that
+        call (1: a non-finite sample was met and the frame was computed again on the full window); None when that plane's last launch
+        did not take the flagged path (test header: jinc_filter_last_finite_flags).  Waits for the device."""
+        n = int(lib().jinc_filter_last_finite_flags(self._h, int(plane), None, 0))
+        if n < 0:
+            self._check(n)
+        if n == 0:
+            return None
+        out = np.zeros(n, np.uint32)
+        self._check(min(int(lib().jinc_filter_last_finite_flags(self._h, int(plane), out.ctypes.data, n)), 0))
+        return out
 
     def set_border_strips(self, mode) -> None:
         """Border frame of exactly periodic plans: -1 by call size (default), True/1 strip kernels, 2 rows only, False/0 gather kernel."""

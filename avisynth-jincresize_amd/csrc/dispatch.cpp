@@ -740,11 +740,18 @@ void launch_plane(jinc_filter& f, const Choice& c, int i, const void* const src[
                             (void)hipFree(f.finite_flags);
                         }
                         f.finite_flags = nullptr, f.finite_flags_frames = 0;
-                        hip_check(hipMalloc(reinterpret_cast<void**>(&f.finite_flags), sizeof(uint32_t) * kFlagSets * 4 * static_cast<size_t>(io.nframes)),
+                        for (auto& r : f.last_flags) r = {};  // (what earlier planes recorded lay in the old sets)
+                        // (room for two frames at least: a one-frame call's chroma planes travel as a pair behind the luma plane, and the sets
+                        // that plane's launches use must not be replaced in the middle of the call)
+                        const int room = std::max(io.nframes, 2);
+                        hip_check(hipMalloc(reinterpret_cast<void**>(&f.finite_flags), sizeof(uint32_t) * kFlagSets * 4 * static_cast<size_t>(room)),
                                   "hipMalloc(finite flags)");
-                        f.finite_flags_frames = io.nframes;
+                        f.finite_flags_frames = room;
                     }
                     uint32_t* flags = f.finite_flags + (static_cast<size_t>(f.finite_flags_turn % kFlagSets) * 4 + static_cast<size_t>(i)) * f.finite_flags_frames;
+                    // test hook: a pair of planes travels as two frames of plane i, so plane i + 1's flag is the second word
+                    for (int k = 0; k < (pair ? 2 : 1); ++k)
+                        f.last_flags[i + k] = {static_cast<size_t>(flags - f.finite_flags) + static_cast<size_t>(k), pair ? 1 : io.nframes};
                     hip_check(hipMemsetAsync(flags, 0, sizeof(uint32_t) * io.nframes, s), "hipMemsetAsync(finite flags)");
                     jinc::PeriodicArgs fin = t.periodic_trim, rest = t.periodic;
                     fin.frame_flags = rest.frame_flags = flags;
@@ -816,6 +823,7 @@ void enqueue_run(jinc_filter& f, const void* const src[4], const int src_pitch[4
     const bool plane_fork = c.wants_plane_fork(fork);
     const unsigned turn = f.fork_turn % jinc_filter::kForkEvents;
     ++f.finite_flags_turn;  // (float planes on the trimmed support: a flag set of its own per call)
+    for (auto& r : f.last_flags) r = {};  // (test hook: launch_plane records the planes that take the flagged path in this call)
     if (fork || plane_fork) {  // side-stream work may start once everything already queued on `stream` is done
         ++f.fork_turn;
         hip_check(hipEventRecord(f.ev_fork[turn], stream), "hipEventRecord(fork)");

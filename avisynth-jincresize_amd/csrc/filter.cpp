@@ -511,6 +511,19 @@ const char* jinc_filter_last_instance(const jinc_filter* f, int table) {
     return f->tables[table].last_instance.c_str();
 }
 
+int jinc_filter_last_finite_flags(const jinc_filter* f, int plane, uint32_t* flags, int capacity) {
+    if (!f || f->device < 0 || plane < 0 || plane >= f->planecount) return 0;
+    const jinc_filter::LastFlags& r = f->last_flags[plane];
+    if (r.frames <= 0 || !f->finite_flags) return 0;
+    const int rc = guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(finite flags)");  // the call's launches may lie on any stream
+        const int n = std::min(capacity, r.frames);
+        if (flags && n > 0) hip_check(hipMemcpy(flags, f->finite_flags + r.first, sizeof(uint32_t) * n, hipMemcpyDeviceToHost), "hipMemcpy(finite flags)");
+    });
+    return rc != JINC_OK ? rc : r.frames;
+}
+
 int jinc_debug_set_knob(int knob, double value) {
     if (knob < 0 || knob >= JINC_KNOB_COUNT) return fail(JINC_ERR_INVALID_ARG, "JincResize: no such knob.");
     if (knob == JINC_KNOB_DIRECT_SHAPE) return jinc_debug_set_direct_shape(static_cast<int>(value));

@@ -214,6 +214,13 @@ struct jinc_filter {
     uint32_t* finite_flags = nullptr;  // [kForkEvents sets][4 planes][finite_flags_frames]: kernel_scan.hip's verdict per plane and frame (float planes)
     int finite_flags_frames = 0;
     unsigned finite_flags_turn = 0;  // which of the kForkEvents flag sets the current call uses (advanced once per call: dispatch.cpp enqueue)
+    // test hook (jinc_filter_last_finite_flags): where in finite_flags the most recent call's flags of each plane lie (words from its
+    // start) and how many frames they cover; frames 0: that plane's last launch did not take the flagged path
+    struct LastFlags {
+        size_t first = 0;
+        int frames = 0;
+    };
+    LastFlags last_flags[4];
     int border_strips = -1;  // border frame of exactly periodic plans: -1 by call size (dispatch.cpp Rules), 1 strip kernels, 2 rows only, 0 gather kernel
     bool direct_premise = false;  // buffer_range_check_covers_soffset(device) == 1
     int simd_order = 0;  // 0: opt=0 results (default); 1 / 2 / 3: summation order of the reference's SSE4.1 / AVX2 / AVX-512 path

@@ -101,6 +101,14 @@ typedef enum jinc_kernel_mode {
  * kernel name for the others.  bench.py reports it as roofline.kernel and the parity tests assert it, so that the
  * instantiation a benchmark times is one the parity tests have checked. */
 JINC_API const char *jinc_filter_last_instance(const jinc_filter *f, int table);
+/* Float planes (fp32, binary16) on the trimmed support: the per-frame flags the most recent frame call raised for `plane` -- 1 where
+ * the trimmed launch (or the scan of the rim no tile stages, or the scan pass of knob FLOAT_SCAN) met an infinity or a NaN in that
+ * frame's plane, so that the full-window launch behind it computed the frame again; 0 where the trimmed result stands.  Waits for the
+ * device, copies up to `capacity` words (one per frame of that call, in order) to `flags` and returns the call's frame count.
+ * Returns 0 when that plane's last launch did not take the flagged path (an integer plane, the full window, a plan without a
+ * periodic interior, a host-only instance), a negative status when the copy failed.  A missed flag shows as wrong samples; a false
+ * one only as a slower call, which is why tests read them. */
+JINC_API int jinc_filter_last_finite_flags(const jinc_filter *f, int plane, uint32_t *flags, int capacity);
 
 /* ---- A/B and tuning knobs ---------------------------------------------------------------------
  * Process-wide; every knob is UNSET by default and the library never reads the environment for them (bench.py translates the

@@ -5,6 +5,7 @@ own opt=0 crc32 known answers at BASELINE.json's full sizes."""
 import hashlib
 import json
 import os
+import re
 import zlib
 
 import numpy as np
@@ -968,6 +969,27 @@ def test_float_planes_take_the_trimmed_support_only_where_every_sample_is_finite
         srcs.append(src)
     f.set_kernel_mode(mode)
     got = _run_batch(torch, gpu_pkg, f, gfmt, srcs, frames, mode)
+    # Which launch ran, and what it flagged.  Mode 0 at this size: the full window, no flags.  Forced modes: the first table on its
+    # trimmed support (6 / 8 in the instance's name or arguments), its planes' flags exactly the frames with a non-finite sample in
+    # THAT plane; the chroma table of the 4:2:0 case (six rows of seven taps, which only the quad form of mode 13 has) as well, or the
+    # full window and no flags.
+    full, side = f.plan_info(0).filter_size, f.plan_info(0).filter_size - 1
+    if mode == 0:
+        assert f.last_instance(0).startswith("ewa_periodic_") and "<float, " in f.last_instance(0), f.last_instance(0)
+        assert all(f.last_finite_flags(i) is None for i in range(gfmt.planes))
+    else:
+        inst = {2: rf"ewa_periodic_kernel<float, {side}, \d+>", 3: rf"ewa_periodic_rows_kernel<float, {side}, \d+>",
+                13: r"ewa_periodic_quad2_kernel<float, \d+, \d+u, 6>" if side == 6 else r"ewa_periodic_quad8_kernel<float, \d+, \d+u>"}[mode]
+        assert re.fullmatch(inst, f.last_instance(0)), f.last_instance(0)
+        assert f.periodic_support(0) == side
+        for i in range(gfmt.planes):
+            flags = f.last_finite_flags(i)
+            chroma = f.num_tables > 1 and i in (1, 2)
+            if chroma and mode != 13 and flags is None:
+                assert re.fullmatch(rf"ewa_periodic\w*_kernel<float, {full}, \d+>", f.last_instance(1)), f.last_instance(1)
+                continue
+            expect = [0 if np.isfinite(srcs[k][i]).all() else 1 for k in range(frames)]
+            assert flags is not None and flags.tolist() == expect, (i, flags)
     for k in range(frames):
         want = of.get_frame(srcs[k], threads=8)
         for i, (w, h) in enumerate(f.out_dims()):
@@ -1009,6 +1031,16 @@ def test_one_non_finite_sample_anywhere_in_a_float_plane(gpu_pkg, O, tap, mode):
             marks.append(k)
         srcs.append(src)
     got = _run_batch(torch, gpu_pkg, f, gfmt, srcs, len(srcs), mode)
+    # the trimmed launch ran (a fall-back to the full window would give the same samples) and flagged the marked frames, no others
+    n = fs - 1
+    inst = {2: rf"ewa_periodic_kernel<float, {n}, \d+>" if n < 10 else rf"ewa_periodic_rowpair_kernel<float, {n}, \d+, \d+>",
+            3: rf"ewa_periodic_rows_kernel<float, {n}, \d+>",
+            13: {6: r"ewa_periodic_quad2_kernel<float, \d+, \d+u, 6>", 8: r"ewa_periodic_quad8_kernel<float, \d+, \d+u>",
+                 16: r"ewa_periodic_rowpair_kernel<float, 16, \d+, \d+>"}[n]}[mode]
+    assert re.fullmatch(inst, f.last_instance(0)), f.last_instance(0)
+    assert f.periodic_support(0) == n
+    flags = f.last_finite_flags(0)
+    assert flags is not None and flags.tolist() == [1 if k in marks else 0 for k in range(len(srcs))], flags
     for k in range(len(srcs)):
         want = of.get_frame(srcs[k], threads=8)
         w, h = f.out_dims()[0]

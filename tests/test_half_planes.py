@@ -2,6 +2,8 @@
 JINC_SAMPLE_FLOAT16): widen every sample to fp32, compute what the library computes for the fp32 plane, narrow the result to
 binary16 with round-to-nearest-even.  Expected value: oracle_fp32(src.astype(float32)).astype(float16), bit for bit, NaN
 positions compared but not NaN payloads."""
+import re
+
 import numpy as np
 import pytest
 
@@ -164,7 +166,8 @@ def test_batches_take_the_fp32_kernels(gpu_pkg, O, case, n):
 @pytest.mark.parametrize("mode", [0, 15], ids=["auto", "full_window"])
 def test_non_finite_frames_in_a_batch(gpu_pkg, O, mode):
     """Infinities and NaNs at interior, border and corner positions in some frames of a batch: those frames take the full support
-    (their result matches the definition, NaNs included) and the finite frames keep the trimmed support's bits."""
+    (their result matches the definition, NaNs included) and the finite frames keep the trimmed support's bits: the automatic choice
+    runs the trimmed launch and flags exactly the frames that hold a non-finite sample; kernel mode 15 flags nothing."""
     torch = pytest.importorskip("torch")
     hname, sw, sh, tw, th, kw = "YH", 320, 180, 640, 360, {}
     f = gpu_pkg.Filter(gpu_pkg.FORMATS[hname], sw, sh, tw, th, device=0, **kw)
@@ -175,7 +178,18 @@ def test_non_finite_frames_in_a_batch(gpu_pkg, O, mode):
     for k, s in spots.items():
         for (y, x, v) in s:
             frames[k][0][y, x] = v
-    got = _run_device(torch, f, frames, dims)
+    if mode == 0:   # (the automatic choice trims float planes from 1e9 taps per plane and call on: here by the knob)
+        with gpu_pkg.knobs(float_trim_min_taps=0):
+            got = _run_device(torch, f, frames, dims)
+        # 3 x 8 tiles of 128 x 24 periods x 16 frames fill the chip: two periods per lane on the 6 x 6 support
+        assert re.fullmatch(r"ewa_periodic_quad2_kernel<_Float16, \d+, \d+u, 6>", f.last_instance(0)), f.last_instance(0)
+        assert f.periodic_support(0) == 6 < f.plan_info(0).filter_size
+        flags = f.last_finite_flags(0)
+        assert flags is not None and flags.tolist() == [1 if k in spots else 0 for k in range(16)], flags
+    else:
+        got = _run_device(torch, f, frames, dims)
+        assert re.fullmatch(r"ewa_periodic_kernel<_Float16, 7, \d+>", f.last_instance(0)), f.last_instance(0)
+        assert f.periodic_support(0) == 7 and f.last_finite_flags(0) is None
     for k in range(16):
         want = definition(O, hname, sw, sh, tw, th, kw, frames[k])
         assert_half_equal(got[k], want, dims, what=f"frame {k}")
