@@ -27,7 +27,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JINC_LIB") or os.path.join(_HERE, "lib", "libjincresize_hip.so")  # JINC_LIB: A/B runs against another build
 SIMD_ORDER_ISA_PATH = os.path.join(_HERE, "lib", "kernel_simdorder-gfx950.s")  # the one unit with (explicit) fused multiply-adds
-ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
+ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_interleave", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
                        "kernel_quasi_exact_fs9", "kernel_quasi_lane_fs7", "kernel_quasi_lane_fs9")]
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip.h")
 TEST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip_test.h")  # introspection, knobs, hooks
@@ -85,7 +85,8 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_set_pipeline_group", "jinc_filter_pipeline_group", "jinc_filter_flush", "jinc_filter_adopt_host_range", "jinc_filter_release_host_range", "jinc_batch_set_affinity", "jinc_batch_device_cpus", "jinc_debug_numa_cpus", "jinc_debug_batch_set_registrars", "jinc_debug_batch_refused", "jinc_debug_host_registrations", "jinc_debug_last_call", "jinc_filter_direct_premise", "jinc_debug_valu_pair_probe", "jinc_debug_clock_sampler_start", "jinc_debug_clock_sampler_stop",
            "jinc_filter_submit", "jinc_filter_wait", "jinc_shard_device", "jinc_batch_create", "jinc_batch_devices",
            "jinc_batch_device_of_frame", "jinc_batch_process", "jinc_batch_free", "jinc_batch_last_error",
-           "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share"]
+           "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share",
+           "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -115,6 +116,10 @@ def lib():
         L.jinc_filter_set_chroma_location_mode.argtypes = [C.c_void_p, C.c_int]
         L.jinc_filter_get_frame.argtypes = [C.c_void_p, _P4, _I4, _P4, _I4]
         L.jinc_filter_process_device.argtypes = [C.c_void_p, _P4, _I4, _S4, _P4, _I4, _S4, C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_strided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
+        L.jinc_debug_last_strided.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         L.jinc_filter_sync.argtypes = [C.c_void_p]
         L.jinc_filter_set_pipeline.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.jinc_filter_set_pipeline_group.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
@@ -273,6 +278,34 @@ def last_call() -> Tuple[str, int]:
     n = C.c_int()
     name = lib().jinc_debug_last_call(C.byref(n))
     return (name or b"").decode(), n.value
+
+
+def strided_groups(bases, pitches, steps, frame_strides, widths, heights, component_size: int) -> Tuple[int, List[int], List[int]]:
+    """Channel groups of one side's planes for Filter.process_device_strided (test header, no device needed): planes with the same
+    step N > 1, pitch, frame stride and dimensions whose bases lie in one N-sample pixel on distinct channels move in one pass.
+    `steps` / `frame_strides` may be None (all ones / all zero).  Returns (groups, group of each plane, channel of each plane); dense
+    planes have group and channel -1."""
+    n = len(bases)
+    b, p, w, h, g, c = _P4(), _I4(), _I4(), _I4(), _I4(), _I4()
+    st, fs = (_I4() if steps is not None else None), (_S4() if frame_strides is not None else None)
+    for i in range(n):
+        b[i], p[i], w[i], h[i] = bases[i], pitches[i], widths[i], heights[i]
+        if st is not None:
+            st[i] = steps[i]
+        if fs is not None:
+            fs[i] = frame_strides[i]
+    rc = int(lib().jinc_debug_strided_groups(b, p, st, fs, w, h, int(component_size), n, g, c))
+    if rc < 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return rc, [int(g[i]) for i in range(n)], [int(c[i]) for i in range(n)]
+
+
+def last_strided() -> Tuple[int, int, int, int]:
+    """(split launches, merge launches, slices, bytes of dense planes held) of the calling thread's most recent
+    process_device_strided call (test header); launches and slices are 0 when every step was 1."""
+    a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+    lib().jinc_debug_last_strided(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    return a.value, b.value, c.value, d.value
 
 
 class KernelMode(enum.IntEnum):
@@ -738,6 +771,28 @@ class Filter:
             dp[i], dpitch[i], ds[i] = dst_ptrs[i], dst_pitches[i], dst_strides[i]
         self._check(lib().jinc_filter_process_device(self._h, sp, spitch, ss, dp, dpitch, ds, int(nframes),
                                                      C.c_void_p(stream)))
+
+    def process_device_strided(self, src_ptrs, src_pitches, src_steps, src_strides, dst_ptrs, dst_pitches, dst_steps, dst_strides,
+                               nframes: int, stream: int = 0) -> None:
+        """process_device on planes with a sample step (jinc_filter_process_device_strided): sample x of plane i lies x * step[i]
+        samples behind the row's start.  NV12: U = uv, V = uv + 1 sample, both step 2; BGRA: B = p, G = p + 1, R = p + 2, A = p + 3, all
+        step 4 (planes in the library's order G, B, R, A).  Steps and frame strides may be None (all ones; one frame).  The dense
+        planes behind a call are capped by the knob strided_scratch_bytes."""
+        n = self.fmt.planes
+
+        def arr(kind, values):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(n):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_strided(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_S4, src_strides), arr(_P4, dst_ptrs),
+            arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
+
+    last_strided = staticmethod(last_strided)
+    strided_groups = staticmethod(strided_groups)
 
     def periodic_support(self, table: int = 0) -> int:
         """Taps per axis the periodic interior kernels execute (trimmed support on integer planes), 0: no periodic interior."""

@@ -1,7 +1,8 @@
 // dispatch.cpp -- the kernel launches of one frame call: per plane, which interior kernel and which border kernels run,
 // on which stream (the body of the process_frame call, ref /root/reference/src/JincResize.cpp:615, on device planes).
 // Layout: Rules (the measured cross-over constants) -> Choice (the rules applied to one call: no launches) -> launch_plane (the
-// launches of one plane under a Choice) -> enqueue_run (batch split, fork / join of the side stream, the plane loop).
+// launches of one plane under a Choice) -> enqueue_run (batch split, fork / join of the side stream, the plane loop); at the end
+// enqueue_strided: planes with a sample step, split -> enqueue -> merge.
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -852,6 +853,224 @@ void enqueue_run(jinc_filter& f, const void* const src[4], const int src_pitch[4
     }
 }
 }  // namespace
+
+// ---- jinc_filter_process_device_strided: device frames whose samples do not lie side by side (NV12 / P010 / P016, packed RGB(A)) ----
+// The resampling kernels keep their dense planes: a strided plane is SPLIT into a dense plane of the filter's own, the call runs
+// through enqueue as any other, and dense results are MERGED into the strided destination (kernel_interleave.hip).  Planes with
+// step 1 inside such a call go to the kernels where they lie.
+
+namespace {
+thread_local StridedReport t_last_strided;
+
+// Dense planes behind a call: 1 GiB unless the knob says otherwise.  Derived, not measured: a 1080p -> 4K 4:2:0 frame has
+// 2 x 960 x 540 source and 2 x 1920 x 1080 result chroma samples, with rows padded to 256 bytes 2 x (1024 x 540 + 2048 x 1080)
+// = 5.5 MB of dense planes per frame (5.2 MB unpadded), 0.66 - 0.71 GB for the 128 frames the full-group batch kernels want in one
+// call: the default keeps such a call in one slice.
+constexpr size_t kStridedScratchDefaultBytes = size_t(1) << 30;
+constexpr int kSliceFrames = 128;  // slices are multiples of this where the cap allows (kFrameLanePairFrames: whole groups of the batch kernels)
+
+struct Side {
+    int group_of[4], channel_of[4], ngroups = 0;
+    int w[4], h[4];
+    size_t dense_pitch[4] = {0, 0, 0, 0}, dense_fs[4] = {0, 0, 0, 0};  // of the strided planes (0: the plane is dense where it lies)
+    size_t offset[4] = {0, 0, 0, 0};                                    // of a strided plane's dense frames in the scratch, per frame of a slice
+};
+
+int step_of(const int* step, int i) { return step ? step[i] : 1; }
+
+void check_strided_planes(const jinc_filter& f, const void* const base[4], const int pitch[4], const int* step, const size_t* fs,
+                          const Side& s, int nframes) {
+    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
+    for (int i = 0; i < f.planecount; ++i) {
+        if (step_of(step, i) == 1) continue;  // (dense planes: validate_planes)
+        if (!base[i]) throw ArgError("JincResize: null plane pointer.");
+        if (pitch[i] <= 0 || pitch[i] % sb) throw ArgError("JincResize: plane pitch is not a multiple of the sample size.");
+        if (reinterpret_cast<uintptr_t>(base[i]) % sb) throw ArgError("JincResize: plane pointer is not aligned to the sample size.");
+        if (fs && nframes > 1 && fs[i] % sb) throw ArgError("JincResize: frame stride is not a multiple of the sample size.");
+        if (static_cast<size_t>(pitch[i]) < (static_cast<size_t>(s.w[i] - 1) * step_of(step, i) + 1) * sb)
+            throw ArgError("JincResize: plane pitch is smaller than the row size at this sample step.");
+    }
+}
+
+// The groups of one side as launch arguments, one InterleaveArgs per step (a call's groups normally share one).
+void fill_args(const jinc_filter& f, const Side& s, const void* const base[4], const int pitch[4], const int* step, const size_t* fs,
+               char* scratch, int first_frame, int slice_frames, int nframes, bool merge, InterleaveArgs by_step[5]) {
+    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
+    for (int g = 0; g < s.ngroups; ++g) {
+        InterleaveGroup e;
+        int n = 0, members = 0, first = -1;
+        uintptr_t lo = 0;
+        for (int i = 0; i < f.planecount; ++i) {
+            if (s.group_of[i] != g) continue;
+            if (first < 0) first = i;
+            const uintptr_t b = reinterpret_cast<uintptr_t>(base[i]);
+            lo = members ? std::min(lo, b) : b;
+            ++members;
+            e.plane[s.channel_of[i]] = scratch + s.offset[i] * static_cast<size_t>(slice_frames);
+        }
+        n = step_of(step, first);
+        const size_t frame_stride = (fs && nframes > 1) ? fs[first] : 0;
+        e.packed = reinterpret_cast<char*>(lo) + static_cast<size_t>(first_frame) * frame_stride;
+        e.packed_frame_stride = frame_stride;
+        e.plane_frame_stride = s.dense_fs[first];
+        e.packed_pitch = static_cast<uint32_t>(pitch[first]);
+        e.plane_pitch = static_cast<uint32_t>(s.dense_pitch[first]);
+        e.width = static_cast<uint32_t>(s.w[first]);
+        e.rows = static_cast<uint32_t>(s.h[first]);
+        const uintptr_t a = lo | static_cast<uintptr_t>(pitch[first]) | static_cast<uintptr_t>(frame_stride);
+        e.unit = a % 16 == 0 ? 16u : a % 4 == 0 ? 4u : 0u;
+        const bool complete = members == n;
+        const uint32_t lane_pixels = static_cast<uint32_t>(16 / sb);
+        // (kernels.h: the merge of an incomplete group stores sample by sample; the split of one leaves the row's last pixel to the tail)
+        const uint32_t vec_from = complete ? e.width : merge ? 0u : e.width - 1;
+        e.vec_pixels = e.unit ? vec_from / lane_pixels * lane_pixels : 0u;
+        InterleaveArgs& a_n = by_step[n];
+        a_n.g[a_n.ngroups++] = e;
+    }
+}
+
+}  // namespace
+
+int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
+                   const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
+    int ngroups = 0, first[4] = {0, 0, 0, 0};
+    uintptr_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
+    const uintptr_t sb = static_cast<uintptr_t>(component_size);
+    auto fs_of = [&](int i) { return frame_stride ? frame_stride[i] : size_t(0); };
+    for (int i = 0; i < nplanes; ++i) {
+        group_of[i] = channel_of[i] = -1;
+        const int n = step_of(step, i);
+        if (n <= 1) continue;
+        const uintptr_t b = reinterpret_cast<uintptr_t>(base[i]);
+        for (int g = 0; g < ngroups && group_of[i] < 0; ++g) {
+            const int j = first[g];
+            if (step_of(step, j) != n || pitch[j] != pitch[i] || fs_of(j) != fs_of(i) || width[j] != width[i] || height[j] != height[i]) continue;
+            const uintptr_t nlo = std::min(lo[g], b), nhi = std::max(hi[g], b);
+            if (nhi - nlo >= static_cast<uintptr_t>(n) * sb || (b - nlo) % sb || (lo[g] - nlo) % sb) continue;  // not one pixel
+            bool distinct = true;
+            for (int k = 0; k < i; ++k) distinct &= !(group_of[k] == g && base[k] == base[i]);
+            if (!distinct) continue;
+            group_of[i] = g, lo[g] = nlo, hi[g] = nhi;
+        }
+        if (group_of[i] < 0) group_of[i] = ngroups, first[ngroups] = i, lo[ngroups] = hi[ngroups] = b, ++ngroups;
+    }
+    for (int i = 0; i < nplanes; ++i)
+        if (group_of[i] >= 0) channel_of[i] = static_cast<int>((reinterpret_cast<uintptr_t>(base[i]) - lo[group_of[i]]) / sb);
+    return ngroups;
+}
+
+const StridedReport& last_strided_report() { return t_last_strided; }
+
+void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
+                     void* const dst[4], const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes,
+                     hipStream_t stream) {
+    bool dense = true;
+    for (int i = 0; i < f.planecount; ++i) dense &= step_of(src_step, i) == 1 && step_of(dst_step, i) == 1;
+    if (dense) {  // the call IS jinc_filter_process_device
+        enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
+        t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};
+        return;
+    }
+    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
+    Side in, out;
+    for (int i = 0; i < f.planecount; ++i) {
+        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
+        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
+    }
+    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
+    in.ngroups = strided_groups(src, src_pitch, src_step, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
+    out.ngroups = strided_groups(dst_c, dst_pitch, dst_step, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(sb), f.planecount, out.group_of, out.channel_of);
+    check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
+    check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
+
+    // Dense planes of the strided ones: pitch and frame stride multiples of 256 bytes, like the look-ahead pipeline's group buffers.
+    size_t per_frame = 0;
+    for (Side* s : {&in, &out})
+        for (int i = 0; i < f.planecount; ++i) {
+            if (s->group_of[i] < 0) continue;
+            s->dense_pitch[i] = align_up(static_cast<size_t>(s->w[i]) * sb, 256);
+            s->dense_fs[i] = s->dense_pitch[i] * static_cast<size_t>(s->h[i]);
+            s->offset[i] = per_frame;
+            per_frame += s->dense_fs[i];
+        }
+    const double cap_knob = knobs::get(JINC_KNOB_STRIDED_SCRATCH_BYTES, static_cast<double>(kStridedScratchDefaultBytes));
+    const size_t cap = cap_knob < 1.0 ? size_t(1) : static_cast<size_t>(cap_knob);
+    int slice = static_cast<int>(std::min<size_t>(static_cast<size_t>(nframes), std::max<size_t>(cap / per_frame, 1)));
+    if (slice < nframes && slice >= kSliceFrames) slice = slice / kSliceFrames * kSliceFrames;
+
+    // The planes as the kernels will get them: dense ones where they lie, strided ones as their dense stand-ins.
+    const void* s_run[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* d_run[4] = {nullptr, nullptr, nullptr, nullptr};
+    int sp_run[4] = {0, 0, 0, 0}, dp_run[4] = {0, 0, 0, 0};
+    size_t sfs_run[4] = {0, 0, 0, 0}, dfs_run[4] = {0, 0, 0, 0};
+    for (int i = 0; i < f.planecount; ++i) {
+        const bool si = in.group_of[i] >= 0, di = out.group_of[i] >= 0;
+        s_run[i] = si ? static_cast<const void*>(nullptr) : src[i];
+        d_run[i] = di ? static_cast<void*>(nullptr) : dst[i];
+        sp_run[i] = si ? static_cast<int>(in.dense_pitch[i]) : src_pitch[i];
+        dp_run[i] = di ? static_cast<int>(out.dense_pitch[i]) : dst_pitch[i];
+        sfs_run[i] = si ? in.dense_fs[i] : (src_fs && nframes > 1 ? src_fs[i] : 0);
+        dfs_run[i] = di ? out.dense_fs[i] : (dst_fs && nframes > 1 ? dst_fs[i] : 0);
+    }
+    const size_t need = per_frame * static_cast<size_t>(slice);
+    if (need > f.strided_scratch_bytes) {
+        if (f.strided_scratch) {
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(strided scratch)");  // launches of earlier calls may still use the old planes
+            (void)hipFree(f.strided_scratch);
+        }
+        f.strided_scratch = nullptr, f.strided_scratch_bytes = 0, f.strided_pending = false;
+        hip_check(hipMalloc(&f.strided_scratch, need), "hipMalloc(strided scratch)");
+        f.strided_scratch_bytes = need;
+    }
+    char* scratch = static_cast<char*>(f.strided_scratch);
+    for (int i = 0; i < f.planecount; ++i) {
+        if (in.group_of[i] >= 0) s_run[i] = scratch + in.offset[i] * static_cast<size_t>(slice);
+        if (out.group_of[i] >= 0) d_run[i] = scratch + out.offset[i] * static_cast<size_t>(slice);
+    }
+    validate_planes(f, s_run, sp_run, sfs_run, d_run, dp_run, dfs_run, nframes);  // (before anything is queued)
+
+    // The dense planes are shared by successive calls: a call on ANOTHER stream than the previous strided call's waits for that
+    // call's last merge (same stream: stream order does it).  A ring of events, one per call in turn, like the fork / join events:
+    // no event is recorded again while a stream may still be waiting on it.
+    const unsigned turn = f.strided_turn % jinc_filter::kForkEvents;
+    if (f.strided_pending && stream != f.strided_last_stream)
+        hip_check(hipStreamWaitEvent(stream, f.ev_strided[(f.strided_turn + jinc_filter::kForkEvents - 1) % jinc_filter::kForkEvents], 0), "hipStreamWaitEvent(strided)");
+    if (!f.ev_strided[turn]) hip_check(hipEventCreateWithFlags(&f.ev_strided[turn], hipEventDisableTiming), "hipEventCreate(strided)");
+
+    StridedReport report{0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};
+    for (int k0 = 0; k0 < nframes; k0 += slice) {
+        const int n = std::min(slice, nframes - k0);
+        const void* s_now[4];
+        void* d_now[4];
+        for (int i = 0; i < 4; ++i) {
+            s_now[i] = (i < f.planecount && in.group_of[i] < 0) ? static_cast<const char*>(src[i]) + static_cast<size_t>(k0) * sfs_run[i] : s_run[i];
+            d_now[i] = (i < f.planecount && out.group_of[i] < 0) ? static_cast<char*>(dst[i]) + static_cast<size_t>(k0) * dfs_run[i] : d_run[i];
+        }
+        InterleaveArgs split[5], merge[5];
+        fill_args(f, in, src, src_pitch, src_step, src_fs, scratch, k0, slice, nframes, false, split);
+        fill_args(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, nframes, true, merge);
+        // Order on the caller's stream: split -> enqueue -> merge.  enqueue's side-stream kernels start behind ev_fork, which it records
+        // on `stream` AFTER the split queued here, and `stream` goes on only behind ev_join, recorded on the side stream after its last
+        // kernel: the merge queued below follows both streams' kernels.
+        for (int step = 2; step <= 4; ++step)
+            if (split[step].ngroups) {
+                hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream)), "split launch");
+                ++report.split_launches;
+            }
+        enqueue(f, s_now, sp_run, sfs_run, d_now, dp_run, dfs_run, n, stream);
+        for (int step = 2; step <= 4; ++step)
+            if (merge[step].ngroups) {
+                hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], static_cast<int>(sb), step, n, stream)), "merge launch");
+                ++report.merge_launches;
+            }
+        ++report.slices;
+    }
+    hip_check(hipEventRecord(f.ev_strided[turn], stream), "hipEventRecord(strided)");
+    ++f.strided_turn;
+    f.strided_pending = true;
+    f.strided_last_stream = stream;
+    t_last_strided = report;
+}
 
 }  // namespace host
 }  // namespace jinc

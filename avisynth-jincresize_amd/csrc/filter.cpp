@@ -225,6 +225,42 @@ int jinc_filter_process_device(jinc_filter* f, const void* const src[4], const i
     });
 }
 
+int jinc_filter_process_device_strided(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                                       const size_t src_frame_stride[4], void* const dst[4], const int dst_pitch[4],
+                                       const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    // null checks and the step range first (they need no device), then the checks of jinc_filter_process_device in its order
+    if (!f || !src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    for (const int* step : {src_sample_step, dst_sample_step})
+        for (int i = 0; step && i < f->planecount; ++i)
+            if (step[i] < 1 || step[i] > 4) return fail(JINC_ERR_INVALID_ARG, "JincResize: sample step must be in 1..4.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_strided(*f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_frame_stride, nframes,
+                        static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int jinc_debug_strided_groups(const void* const base[4], const int pitch[4], const int step[4], const size_t frame_stride[4],
+                              const int width[4], const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
+    if (!base || !pitch || !width || !height || !group_of || !channel_of || nplanes < 0 || nplanes > 4 ||
+        (component_size != 1 && component_size != 2 && component_size != 4))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    return strided_groups(base, pitch, step, frame_stride, width, height, component_size, nplanes, group_of, channel_of);
+}
+
+int jinc_debug_last_strided(int* split_launches, int* merge_launches, int* slices, long long* scratch_bytes) {
+    const StridedReport& r = last_strided_report();
+    if (split_launches) *split_launches = r.split_launches;
+    if (merge_launches) *merge_launches = r.merge_launches;
+    if (slices) *slices = r.slices;
+    if (scratch_bytes) *scratch_bytes = r.scratch_bytes;
+    return JINC_OK;
+}
+
 int jinc_filter_sync(jinc_filter* f) {
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");

@@ -1,7 +1,7 @@
 // filter_internal.h -- types and internal interfaces shared by the host translation units of libjincresize_hip.so:
 //   filter_args.cpp   Create_JincResize's argument handling and geometry derivation (configure)
 //   device_plan.cpp   device-resident plans: upload, launch planning for every kernel family (init_device)
-//   dispatch.cpp      per-call kernel selection and launches (enqueue)
+//   dispatch.cpp      per-call kernel selection and launches (enqueue; enqueue_strided: planes with a sample step)
 //   pipeline.cpp      frames in flight: device staging slots, pinned host ranges, H2D -> kernels -> D2H
 //   filter.cpp        the C ABI of include/jincresize_hip.h
 // Nothing here crosses the C ABI.
@@ -256,6 +256,15 @@ struct jinc_filter {
     static constexpr int kForkEvents = 16;
     hipEvent_t ev_fork[kForkEvents] = {}, ev_join[kForkEvents] = {};
     unsigned fork_turn = 0;
+    // jinc_filter_process_device_strided (dispatch.cpp enqueue_strided): the dense planes strided ones are split into / merged from -- one allocation,
+    // made on first use, grown when a call needs more -- and, because successive calls share them, an event behind each call's last
+    // merge (a ring, as above) for the next call to wait on when it comes on another stream.
+    void* strided_scratch = nullptr;
+    size_t strided_scratch_bytes = 0;
+    hipEvent_t ev_strided[kForkEvents] = {};
+    unsigned strided_turn = 0;
+    bool strided_pending = false;  // ev_strided[(strided_turn - 1) % kForkEvents] has been recorded on strided_last_stream
+    hipStream_t strided_last_stream = nullptr;
 
     ~jinc_filter() {
         if (device >= 0) {
@@ -265,6 +274,9 @@ struct jinc_filter {
                 for (void* b : t.lane_blobs) (void)hipFree(b);
             }
             if (finite_flags) (void)hipFree(finite_flags);
+            if (strided_scratch) (void)hipFree(strided_scratch);  // (hipFree waits for the device)
+            for (hipEvent_t e : ev_strided)
+                if (e) (void)hipEventDestroy(e);
             jinc::host::release_pipeline(*this);  // (also returns this instance's references to pinned host ranges)
             for (auto* v : {&ev_periodic, &ev_gather})
                 for (auto& e : *v) {
@@ -307,6 +319,17 @@ uint32_t direct_src_bytes(const void* base, uint64_t plane_bytes);
 void enqueue(jinc_filter& f, const void* const src[4], const int src_pitch[4], const size_t src_fs[4], void* const dst[4],
              const int dst_pitch[4], const size_t dst_fs[4], int nframes, hipStream_t stream);
 const char* last_interior_kernel_in_process();
+// ... enqueue for planes with a sample step (NULL step array: all ones; every step 1: enqueue itself)
+void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
+                     void* const dst[4], const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream);
+// ... the channel groups of one side's planes (pure: test header jinc_debug_strided_groups); returns their number
+int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
+                   const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]);
+struct StridedReport {  // test header: jinc_debug_last_strided
+    int split_launches = 0, merge_launches = 0, slices = 0;
+    long long scratch_bytes = 0;
+};
+const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided
 int last_call_frames_in_process();
 const char* last_interior_instance_in_process();
 // pipeline.cpp: frames in flight on one instance

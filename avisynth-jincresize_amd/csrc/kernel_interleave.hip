@@ -1,0 +1,160 @@
+// kernel_interleave.hip -- interleaved samples <-> dense planes around jinc_filter_process_device_strided (dispatch.cpp enqueue_strided): the chroma
+// plane of NV12 / P010 / P016 (U and V sample by sample) and packed RGB(A) are SPLIT into the dense planes the resampling kernels
+// read, and the dense results are MERGED into the caller's interleaved destination.  Bytes in, the same bytes out: nothing here
+// looks at a sample's value, so one instantiation per sample size serves integer, fp32 and binary16 planes.
+//
+// Shape, after kernel_blit.hip: ONE launch per direction covers every channel group and frame of a call (grid = row blocks x frames
+// x groups; the groups travel as kernel arguments, kernels.h InterleaveArgs), a wave owns a row, its lanes walk along it, and no
+// access costs a division or a modulo.  A lane owns 16 / B whole pixels per step: N vectors of 16 bytes on the interleaved side
+// (consecutive lanes, consecutive addresses) and one vector of 16 bytes per dense plane, rearranged in registers with shifts whose
+// amounts are compile-time constants.  Every interleaved byte of those pixels is read once (split) or written once (merge).
+// Sample-sized accesses take what is left: a row's tail, groups whose base or pitch is not a multiple of 4 bytes, and the merge of
+// an incomplete group -- there only the given channels' samples are stored, the bytes between them are not touched.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace jinc {
+namespace {
+
+template <int B> struct SampleOf;
+template <> struct SampleOf<1> { using type = uint8_t; };
+template <> struct SampleOf<2> { using type = uint16_t; };
+template <> struct SampleOf<4> { using type = uint32_t; };
+
+// Sample i of a run of B-byte samples held in dwords (i is a constant once the loops around the calls are unrolled).
+template <int B>
+__device__ __forceinline__ uint32_t get_sample(const uint32_t* w, int i) {
+    if constexpr (B == 4) return w[i];
+    else if constexpr (B == 2) return (w[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+    else return (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
+}
+template <int B>
+__device__ __forceinline__ void put_sample(uint32_t* w, int i, uint32_t v) {  // (w starts as zeros)
+    if constexpr (B == 4) w[i] = v;
+    else if constexpr (B == 2) w[i >> 1] |= v << (16 * (i & 1));
+    else w[i >> 2] |= v << (8 * (i & 3));
+}
+
+// 16 N bytes of whole pixels: N 16-byte accesses where the group allows them, else 4 N dwords.
+template <int N>
+__device__ __forceinline__ void load_packed(const char* p, uint32_t unit, uint32_t* w) {
+    if (unit == 16) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const uint4 v = *reinterpret_cast<const uint4*>(p + 16 * k);
+            w[4 * k] = v.x, w[4 * k + 1] = v.y, w[4 * k + 2] = v.z, w[4 * k + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4 * N; ++k) w[k] = *reinterpret_cast<const uint32_t*>(p + 4 * k);
+    }
+}
+template <int N>
+__device__ __forceinline__ void store_packed(char* p, uint32_t unit, const uint32_t* w) {
+    if (unit == 16) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) *reinterpret_cast<uint4*>(p + 16 * k) = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4 * N; ++k) *reinterpret_cast<uint32_t*>(p + 4 * k) = w[k];
+    }
+}
+
+// Row blockIdx.x * 4 + wave of frame blockIdx.y of group blockIdx.z.
+template <int B, int N>
+__global__ __launch_bounds__(256) void split_samples_kernel(const InterleaveArgs a) {
+    using T = typename SampleOf<B>::type;
+    constexpr uint32_t P = 16 / B;  // pixels a lane owns per step
+    const InterleaveGroup& g = a.g[blockIdx.z];
+    const uint32_t lane = threadIdx.x & 63u, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= g.rows) return;
+    const char* __restrict__ packed = g.packed + blockIdx.y * g.packed_frame_stride + static_cast<size_t>(row) * g.packed_pitch;
+    const size_t dense = blockIdx.y * g.plane_frame_stride + static_cast<size_t>(row) * g.plane_pitch;
+    for (uint32_t x = lane * P; x < g.vec_pixels; x += 64 * P) {
+        uint32_t in[4 * N];
+        load_packed<N>(packed + static_cast<size_t>(x) * (N * B), g.unit, in);
+#pragma unroll
+        for (int c = 0; c < N; ++c) {
+            if (!g.plane[c]) continue;
+            uint32_t out[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int p = 0; p < static_cast<int>(P); ++p) put_sample<B>(out, p, get_sample<B>(in, p * N + c));
+            *reinterpret_cast<uint4*>(g.plane[c] + dense + static_cast<size_t>(x) * B) = make_uint4(out[0], out[1], out[2], out[3]);
+        }
+    }
+    for (uint32_t x = g.vec_pixels + lane; x < g.width; x += 64) {
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+            if (g.plane[c]) reinterpret_cast<T*>(g.plane[c] + dense)[x] = reinterpret_cast<const T*>(packed)[static_cast<size_t>(x) * N + c];
+    }
+}
+
+template <int B, int N>
+__global__ __launch_bounds__(256) void merge_samples_kernel(const InterleaveArgs a) {
+    using T = typename SampleOf<B>::type;
+    constexpr uint32_t P = 16 / B;
+    const InterleaveGroup& g = a.g[blockIdx.z];
+    const uint32_t lane = threadIdx.x & 63u, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= g.rows) return;
+    char* __restrict__ packed = g.packed + blockIdx.y * g.packed_frame_stride + static_cast<size_t>(row) * g.packed_pitch;
+    const size_t dense = blockIdx.y * g.plane_frame_stride + static_cast<size_t>(row) * g.plane_pitch;
+    for (uint32_t x = lane * P; x < g.vec_pixels; x += 64 * P) {  // (complete groups only: every byte of these pixels is a given sample)
+        uint32_t out[4 * N];
+#pragma unroll
+        for (int k = 0; k < 4 * N; ++k) out[k] = 0u;
+#pragma unroll
+        for (int c = 0; c < N; ++c) {
+            const uint4 v = *reinterpret_cast<const uint4*>(g.plane[c] + dense + static_cast<size_t>(x) * B);
+            const uint32_t in[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int p = 0; p < static_cast<int>(P); ++p) put_sample<B>(out, p * N + c, get_sample<B>(in, p));
+        }
+        store_packed<N>(packed + static_cast<size_t>(x) * (N * B), g.unit, out);
+    }
+    for (uint32_t x = g.vec_pixels + lane; x < g.width; x += 64) {
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+            if (g.plane[c]) reinterpret_cast<T*>(packed)[static_cast<size_t>(x) * N + c] = reinterpret_cast<const T*>(g.plane[c] + dense)[x];
+    }
+}
+
+template <bool Merge, int B, int N>
+int launch(const InterleaveArgs& a, int nframes, hipStream_t s) {
+    uint32_t rows = 0;
+    for (int k = 0; k < a.ngroups; ++k) rows = a.g[k].rows > rows ? a.g[k].rows : rows;
+    if (a.ngroups <= 0 || nframes <= 0 || rows == 0) return hipSuccess;
+    const dim3 grid((rows + 3) / 4, static_cast<uint32_t>(nframes), static_cast<uint32_t>(a.ngroups));
+    if constexpr (Merge) hipLaunchKernelGGL((merge_samples_kernel<B, N>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((split_samples_kernel<B, N>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+template <bool Merge>
+int launch_by_shape(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (sample_bytes * 8 + step) {
+        case 1 * 8 + 2: return launch<Merge, 1, 2>(a, nframes, s);
+        case 1 * 8 + 3: return launch<Merge, 1, 3>(a, nframes, s);
+        case 1 * 8 + 4: return launch<Merge, 1, 4>(a, nframes, s);
+        case 2 * 8 + 2: return launch<Merge, 2, 2>(a, nframes, s);
+        case 2 * 8 + 3: return launch<Merge, 2, 3>(a, nframes, s);
+        case 2 * 8 + 4: return launch<Merge, 2, 4>(a, nframes, s);
+        case 4 * 8 + 2: return launch<Merge, 4, 2>(a, nframes, s);
+        case 4 * 8 + 3: return launch<Merge, 4, 3>(a, nframes, s);
+        case 4 * 8 + 4: return launch<Merge, 4, 4>(a, nframes, s);
+    }
+    return hipErrorInvalidValue;  // (no kernel for this shape: an error, never a silent skip)
+}
+
+}  // namespace
+
+int launch_split_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream) {
+    return launch_by_shape<false>(a, sample_bytes, step, nframes, stream);
+}
+
+int launch_merge_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream) {
+    return launch_by_shape<true>(a, sample_bytes, step, nframes, stream);
+}
+
+}  // namespace jinc

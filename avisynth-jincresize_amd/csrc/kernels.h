@@ -494,6 +494,32 @@ int blit_unit(const void* src, const void* dst, uint32_t src_pitch, uint32_t dst
 int launch_blit_rows(const BlitEntry* table_device, int first, int count, uint32_t max_rows, uint32_t max_row_bytes, int workgroups,
                      void* stream);
 
+// Interleaved samples <-> dense planes (kernel_interleave.hip; jinc_filter_process_device_strided).  A channel group = the planes
+// whose samples share the pixels of one interleaved buffer: `step` samples per pixel, channel c of pixel x of row y of frame n at
+// packed + n * packed_frame_stride + y * packed_pitch + (x * step + c) * sample_bytes, and in the dense plane of channel c
+// (plane[c]; nullptr: that channel was not given and is neither read nor written) at plane[c] + n * plane_frame_stride +
+// y * plane_pitch + x * sample_bytes.  Channel 0 is always given (the group's lowest base).  The dense planes are the filter's own:
+// bases, pitch and frame stride multiples of 256 bytes.
+// unit: widest access the packed side allows (16 / 4: base, pitch and frame stride are multiples of it; 0: sample-sized accesses
+// only); vec_pixels: the leading pixels of every row that move by such accesses, a multiple of the 16 / sample_bytes pixels a lane
+// owns -- the merge of an incomplete group has none (only the given channels' samples may be stored to), the split of one stops in
+// front of the row's last pixel, whose missing channels may lie behind the end of the caller's buffer.
+struct InterleaveGroup {
+    char* packed = nullptr;
+    char* plane[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t packed_frame_stride = 0, plane_frame_stride = 0;
+    uint32_t packed_pitch = 0, plane_pitch = 0, width = 0, rows = 0, vec_pixels = 0, unit = 0;
+};
+// The groups of ONE launch travel as kernel arguments: a table in memory would have to stay untouched until the launch has run,
+// and the call returns before that.
+struct InterleaveArgs {
+    InterleaveGroup g[4];
+    int ngroups = 0;
+};
+// One launch over every group and frame of `a`: sample_bytes 1, 2 or 4; step 2, 3 or 4 (the same for all groups of a launch).
+int launch_split_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream);
+int launch_merge_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream);
+
 // Measurement hook (kernel_probe.hip): `samplers` single-lane workgroups stamp the shader clock counter and the 100 MHz
 // real-time counter until *stop_flag (device memory) becomes non-zero or max_seconds pass; out[2 k] = shader ticks,
 // out[2 k + 1] = real-time ticks of sampler k.

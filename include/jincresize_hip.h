@@ -248,6 +248,25 @@ JINC_API int jinc_filter_process_device(jinc_filter *f, const void *const src[4]
                                         const int dst_pitch[4], const size_t dst_frame_stride[4],
                                         int nframes, void *hip_stream);
 
+/* jinc_filter_process_device on planes whose samples need not lie side by side: the semi-planar frames of video decoders
+ * (NV12, P010 / P016) and packed RGB(A).  Sample x of row y of frame n of plane i lies at
+ *   base[i] + n * frame_stride[i] + y * pitch[i] + x * sample_step[i] * component_size;
+ * steps are in samples, 1 .. 4 (1: dense), a NULL step array means all ones; planes keep the library's order (Y,U,V,A or
+ * G,B,R,A).  NV12: U = uv, V = uv + 1 sample, both step 2.  BGRA: B = p, G = p + 1, R = p + 2, A = p + 3, all step 4.  Source
+ * and destination layouts are independent.  With every step 1 the call IS jinc_filter_process_device.  Otherwise planes with
+ * step 1 are used where they lie; the others are split into dense planes of the filter's own (device memory, allocated on
+ * first use), resampled by the same kernels, and merged into the destination -- all ordered on `hip_stream`.
+ * A step outside 1 .. 4, a strided plane whose pitch is below ((width - 1) * step + 1) * component_size, and a base that is
+ * not aligned to the sample size are JINC_ERR_INVALID_ARG; nframes and frame strides as for jinc_filter_process_device.
+ * The library stores to no byte of the destination that is not a sample of a plane it was given: the X of BGRX under a
+ * three-component filter, row padding and the bytes between a lone strided plane's samples are not read and written back,
+ * they are not written.  src and dst must not overlap; destination planes may (and normally do) share one buffer.
+ * One strided call at a time uses the filter's dense planes: a later one on another stream waits for the earlier one. */
+JINC_API int jinc_filter_process_device_strided(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                const int src_sample_step[4], const size_t src_frame_stride[4],
+                                                void *const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
+                                                const size_t dst_frame_stride[4], int nframes, void *hip_stream);
+
 /* Block until everything enqueued on the filter's own stream (jinc_filter_get_frame) has finished.
  * Work given to jinc_filter_process_device is synchronised by the caller through its stream. */
 JINC_API int jinc_filter_sync(jinc_filter *f);

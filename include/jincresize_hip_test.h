@@ -158,6 +158,7 @@ typedef enum jinc_knob {
     JINC_KNOB_STAGE_BANDS,            /* row bands a pageable plane is cut into between the CPU's copy and the DMA engine: default 4 (2 MiB each at least), 1 = whole planes (round 6) */
     JINC_KNOB_STAGE_DEFER_KB,         /* pageable frames of up to this many KiB of source in groups of 4 or more are copied to the library's pinned buffer when the group is launched (one job, one DMA copy per plane) instead of at submit: default 1536, 0 = never (round 6) */
     JINC_KNOB_QUAD_SHARE,             /* 0: the 2x tap-3 interior of integer planes without its frame-pair symmetry-class form (the plan's class check fails; tests, A/B) */
+    JINC_KNOB_STRIDED_SCRATCH_BYTES,  /* cap of the dense planes behind jinc_filter_process_device_strided in bytes (default 1 GiB): a call that needs more runs in slices of whole frames */
     JINC_KNOB_COUNT
 } jinc_knob;
 JINC_API int jinc_debug_set_knob(int knob, double value);
@@ -226,6 +227,20 @@ JINC_API long long jinc_debug_staged_frames(void);
 JINC_API int jinc_debug_usable_cpus(void);
 JINC_API int jinc_debug_copy_rows(void *dst, size_t dst_pitch, const void *src, size_t src_pitch, size_t row_bytes, int rows,
                                   int may_use_helpers);
+/* ---- jinc_filter_process_device_strided ---------------------------------------------------------
+ * The grouping of one side's planes (host only, no device call): strided planes (step N > 1) with the same step, pitch, frame
+ * stride and dimensions whose bases fall into the same N-sample pixel on distinct channels form a channel group -- one split or
+ * merge pass moves them together; a strided plane without a partner is a group of one.  base / pitch / step / frame_stride / width /
+ * height describe planes 0 .. nplanes - 1 (a NULL step array: all ones).  group_of[i] receives plane i's group (0, 1, ... in
+ * order of each group's first plane; -1 for a dense plane), channel_of[i] its channel inside the pixel (-1 for a dense plane).
+ * Returns the number of groups, or JINC_ERR_INVALID_ARG. */
+JINC_API int jinc_debug_strided_groups(const void *const base[4], const int pitch[4], const int step[4], const size_t frame_stride[4],
+                                       const int width[4], const int height[4], int component_size, int nplanes, int group_of[4],
+                                       int channel_of[4]);
+/* The most recent jinc_filter_process_device_strided call on the calling thread: split and merge kernel launches, slices (the
+ * call's frames cut into runs that fit the dense planes' cap) and the bytes of dense planes the filter holds.  All zero but the
+ * bytes when every step was 1 (the call was jinc_filter_process_device).  Any pointer may be NULL. */
+JINC_API int jinc_debug_last_strided(int *split_launches, int *merge_launches, int *slices, long long *scratch_bytes);
 /* Border frame of exactly periodic plans: -1 (default) = by call size (strip kernels from ~5e9 taps per call on, one gather
  * launch below); 1 = rows and columns on the round-4 strip kernels (ewa_direct_kernel's row strips, ewa_colstrip_kernel or, in batches,
  * the frame-lane kernel), corners on the gather kernel; 2 = rows on the strip kernel, columns and corners on the gather kernel;
