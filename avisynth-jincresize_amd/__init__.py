@@ -86,7 +86,8 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_submit", "jinc_filter_wait", "jinc_shard_device", "jinc_batch_create", "jinc_batch_devices",
            "jinc_batch_device_of_frame", "jinc_batch_process", "jinc_batch_free", "jinc_batch_last_error",
            "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share",
-           "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided"]
+           "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided",
+           "jinc_filter_process_device_shifted"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -118,6 +119,7 @@ def lib():
         L.jinc_filter_process_device.argtypes = [C.c_void_p, _P4, _I4, _S4, _P4, _I4, _S4, C.c_int, C.c_void_p]
         L.jinc_filter_process_device_strided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_shifted.argtypes = [C.c_void_p] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p]
         L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
         L.jinc_debug_last_strided.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         L.jinc_filter_sync.argtypes = [C.c_void_p]
@@ -790,6 +792,25 @@ class Filter:
         self._check(lib().jinc_filter_process_device_strided(
             self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_S4, src_strides), arr(_P4, dst_ptrs),
             arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
+
+    def process_device_shifted(self, src_ptrs, src_pitches, src_steps, src_shifts, src_strides, dst_ptrs, dst_pitches, dst_steps,
+                               dst_shifts, dst_strides, nframes: int, stream: int = 0) -> None:
+        """process_device_strided on 16-bit words that keep their sample in the high bits (jinc_filter_process_device_shifted): a
+        source sample's value is raw >> shift[i], a result is stored as value << shift[i].  P010: Y step 1, U and V step 2, all
+        shift 6; P012: shift 4; Y210: Y step 2, U and V step 4, shift 6.  Steps, shifts and frame strides may be None."""
+        n = self.fmt.planes
+
+        def arr(kind, values):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(n):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_shifted(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_I4, src_shifts), arr(_S4, src_strides),
+            arr(_P4, dst_ptrs), arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_I4, dst_shifts), arr(_S4, dst_strides), int(nframes),
+            C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
     strided_groups = staticmethod(strided_groups)

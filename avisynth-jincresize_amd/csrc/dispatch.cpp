@@ -854,10 +854,13 @@ void enqueue_run(jinc_filter& f, const void* const src[4], const int src_pitch[4
 }
 }  // namespace
 
-// ---- jinc_filter_process_device_strided: device frames whose samples do not lie side by side (NV12 / P010 / P016, packed RGB(A)) ----
+// ---- jinc_filter_process_device_strided: device frames whose samples do not lie side by side (NV12 / P016, packed RGB(A)) ----
 // The resampling kernels keep their dense planes: a strided plane is SPLIT into a dense plane of the filter's own, the call runs
 // through enqueue as any other, and dense results are MERGED into the strided destination (kernel_interleave.hip).  Planes with
 // step 1 inside such a call go to the kernels where they lie.
+// jinc_filter_process_device_shifted (P010 / P012 / Y210: the sample in the high bits of its 16-bit word) adds a shift per plane
+// and side.  The same two passes apply it, so a plane with a non-zero shift takes a dense stand-in on that side at step 1 too: a
+// channel group of one plane with one sample per pixel.  The arithmetic kernels see low-aligned values, as ever.
 
 namespace {
 thread_local StridedReport t_last_strided;
@@ -866,6 +869,10 @@ thread_local StridedReport t_last_strided;
 // 2 x 960 x 540 source and 2 x 1920 x 1080 result chroma samples, with rows padded to 256 bytes 2 x (1024 x 540 + 2048 x 1080)
 // = 5.5 MB of dense planes per frame (5.2 MB unpadded), 0.66 - 0.71 GB for the 128 frames the full-group batch kernels want in one
 // call: the default keeps such a call in one slice.
+// A SHIFTED call keeps its luma here as well.  16-bit 1080p -> 4K with every plane shifted on both sides: 2 x (2048 x 540 +
+// 4096 x 1080) = 11.1 MB of chroma and 3840 x 1080 + 7680 x 2160 = 20.7 MB of luma, 31.8 MB per frame -- the default holds 33
+// frames, so a call of 128 runs as 33 + 33 + 33 + 29 and no slice fills a whole group of the batch kernels.  Callers that
+// send long shifted calls raise the knob (4.1 GB for 128 frames); the rule below is the same for every call.
 constexpr size_t kStridedScratchDefaultBytes = size_t(1) << 30;
 constexpr int kSliceFrames = 128;  // slices are multiples of this where the cap allows (kFrameLanePairFrames: whole groups of the batch kernels)
 
@@ -877,12 +884,13 @@ struct Side {
 };
 
 int step_of(const int* step, int i) { return step ? step[i] : 1; }
+int shift_of(const int* shift, int i) { return shift ? shift[i] : 0; }
 
 void check_strided_planes(const jinc_filter& f, const void* const base[4], const int pitch[4], const int* step, const size_t* fs,
                           const Side& s, int nframes) {
     const size_t sb = static_cast<size_t>(f.vi_in.component_size);
     for (int i = 0; i < f.planecount; ++i) {
-        if (step_of(step, i) == 1) continue;  // (dense planes: validate_planes)
+        if (s.group_of[i] < 0) continue;  // (planes that go to the kernels where they lie: validate_planes)
         if (!base[i]) throw ArgError("JincResize: null plane pointer.");
         if (pitch[i] <= 0 || pitch[i] % sb) throw ArgError("JincResize: plane pitch is not a multiple of the sample size.");
         if (reinterpret_cast<uintptr_t>(base[i]) % sb) throw ArgError("JincResize: plane pointer is not aligned to the sample size.");
@@ -893,8 +901,8 @@ void check_strided_planes(const jinc_filter& f, const void* const base[4], const
 }
 
 // The groups of one side as launch arguments, one InterleaveArgs per step (a call's groups normally share one).
-void fill_args(const jinc_filter& f, const Side& s, const void* const base[4], const int pitch[4], const int* step, const size_t* fs,
-               char* scratch, int first_frame, int slice_frames, int nframes, bool merge, InterleaveArgs by_step[5]) {
+void fill_args(const jinc_filter& f, const Side& s, const void* const base[4], const int pitch[4], const int* step, const int* shift,
+               const size_t* fs, char* scratch, int first_frame, int slice_frames, int nframes, bool merge, InterleaveArgs by_step[5]) {
     const size_t sb = static_cast<size_t>(f.vi_in.component_size);
     for (int g = 0; g < s.ngroups; ++g) {
         InterleaveGroup e;
@@ -907,6 +915,7 @@ void fill_args(const jinc_filter& f, const Side& s, const void* const base[4], c
             lo = members ? std::min(lo, b) : b;
             ++members;
             e.plane[s.channel_of[i]] = scratch + s.offset[i] * static_cast<size_t>(slice_frames);
+            e.shift[s.channel_of[i]] = static_cast<uint8_t>(shift_of(shift, i));
         }
         n = step_of(step, first);
         const size_t frame_stride = (fs && nframes > 1) ? fs[first] : 0;
@@ -929,10 +938,9 @@ void fill_args(const jinc_filter& f, const Side& s, const void* const base[4], c
     }
 }
 
-}  // namespace
-
-int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
-                   const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
+// strided_groups, and with `shift` also every plane of step 1 with a non-zero shift as a group of its own
+int groups_of_side(const void* const base[4], const int pitch[4], const int* step, const int* shift, const size_t* frame_stride,
+                   const int width[4], const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
     int ngroups = 0, first[4] = {0, 0, 0, 0};
     uintptr_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
     const uintptr_t sb = static_cast<uintptr_t>(component_size);
@@ -940,9 +948,9 @@ int strided_groups(const void* const base[4], const int pitch[4], const int* ste
     for (int i = 0; i < nplanes; ++i) {
         group_of[i] = channel_of[i] = -1;
         const int n = step_of(step, i);
-        if (n <= 1) continue;
+        if (n <= 1 && shift_of(shift, i) == 0) continue;
         const uintptr_t b = reinterpret_cast<uintptr_t>(base[i]);
-        for (int g = 0; g < ngroups && group_of[i] < 0; ++g) {
+        for (int g = 0; g < ngroups && group_of[i] < 0 && n > 1; ++g) {
             const int j = first[g];
             if (step_of(step, j) != n || pitch[j] != pitch[i] || fs_of(j) != fs_of(i) || width[j] != width[i] || height[j] != height[i]) continue;
             const uintptr_t nlo = std::min(lo[g], b), nhi = std::max(hi[g], b);
@@ -959,13 +967,21 @@ int strided_groups(const void* const base[4], const int pitch[4], const int* ste
     return ngroups;
 }
 
+}  // namespace
+
+int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
+                   const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
+    return groups_of_side(base, pitch, step, nullptr, frame_stride, width, height, component_size, nplanes, group_of, channel_of);
+}
+
 const StridedReport& last_strided_report() { return t_last_strided; }
 
-void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
-                     void* const dst[4], const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes,
-                     hipStream_t stream) {
+void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
+                     const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift,
+                     const size_t* dst_fs, int nframes, hipStream_t stream) {
     bool dense = true;
-    for (int i = 0; i < f.planecount; ++i) dense &= step_of(src_step, i) == 1 && step_of(dst_step, i) == 1;
+    for (int i = 0; i < f.planecount; ++i)
+        dense &= step_of(src_step, i) == 1 && step_of(dst_step, i) == 1 && shift_of(src_shift, i) == 0 && shift_of(dst_shift, i) == 0;
     if (dense) {  // the call IS jinc_filter_process_device
         enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
         t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};
@@ -978,8 +994,8 @@ void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pit
         f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
     }
     const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
-    in.ngroups = strided_groups(src, src_pitch, src_step, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
-    out.ngroups = strided_groups(dst_c, dst_pitch, dst_step, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(sb), f.planecount, out.group_of, out.channel_of);
+    in.ngroups = groups_of_side(src, src_pitch, src_step, src_shift, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
+    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, dst_shift, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(sb), f.planecount, out.group_of, out.channel_of);
     check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
     check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
 
@@ -1047,18 +1063,18 @@ void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pit
             d_now[i] = (i < f.planecount && out.group_of[i] < 0) ? static_cast<char*>(dst[i]) + static_cast<size_t>(k0) * dfs_run[i] : d_run[i];
         }
         InterleaveArgs split[5], merge[5];
-        fill_args(f, in, src, src_pitch, src_step, src_fs, scratch, k0, slice, nframes, false, split);
-        fill_args(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, nframes, true, merge);
+        fill_args(f, in, src, src_pitch, src_step, src_shift, src_fs, scratch, k0, slice, nframes, false, split);
+        fill_args(f, out, dst_c, dst_pitch, dst_step, dst_shift, dst_fs, scratch, k0, slice, nframes, true, merge);
         // Order on the caller's stream: split -> enqueue -> merge.  enqueue's side-stream kernels start behind ev_fork, which it records
         // on `stream` AFTER the split queued here, and `stream` goes on only behind ev_join, recorded on the side stream after its last
         // kernel: the merge queued below follows both streams' kernels.
-        for (int step = 2; step <= 4; ++step)
+        for (int step = 1; step <= 4; ++step)  // (step 1: shifted dense planes)
             if (split[step].ngroups) {
                 hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream)), "split launch");
                 ++report.split_launches;
             }
         enqueue(f, s_now, sp_run, sfs_run, d_now, dp_run, dfs_run, n, stream);
-        for (int step = 2; step <= 4; ++step)
+        for (int step = 1; step <= 4; ++step)
             if (merge[step].ngroups) {
                 hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], static_cast<int>(sb), step, n, stream)), "merge launch");
                 ++report.merge_launches;

@@ -228,19 +228,39 @@ int jinc_filter_process_device(jinc_filter* f, const void* const src[4], const i
 int jinc_filter_process_device_strided(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
                                        const size_t src_frame_stride[4], void* const dst[4], const int dst_pitch[4],
                                        const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
-    // null checks and the step range first (they need no device), then the checks of jinc_filter_process_device in its order
+    return jinc_filter_process_device_shifted(f, src, src_pitch, src_sample_step, nullptr, src_frame_stride, dst, dst_pitch, dst_sample_step,
+                                              nullptr, dst_frame_stride, nframes, hip_stream);
+}
+
+int jinc_filter_process_device_shifted(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                                       const int src_sample_shift[4], const size_t src_frame_stride[4], void* const dst[4],
+                                       const int dst_pitch[4], const int dst_sample_step[4], const int dst_sample_shift[4],
+                                       const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    // null checks, the step range and the shift range first (they need no device), then the checks of jinc_filter_process_device in its order
     if (!f || !src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     for (const int* step : {src_sample_step, dst_sample_step})
         for (int i = 0; step && i < f->planecount; ++i)
             if (step[i] < 1 || step[i] > 4) return fail(JINC_ERR_INVALID_ARG, "JincResize: sample step must be in 1..4.");
+    // A shift is the padding below a sample in its word: integer samples narrower than their container (10 / 12 / 14 bits in 16).
+    const bool integer = !f->half && f->vi_in.bits_per_component <= 16;
+    const int spare = integer ? 8 * f->vi_in.component_size - f->vi_in.bits_per_component : 0;
+    for (const int* shift : {src_sample_shift, dst_sample_shift})
+        for (int i = 0; shift && i < f->planecount; ++i) {
+            if (shift[i] < 0) return fail(JINC_ERR_INVALID_ARG, "JincResize: sample shift must not be negative.");
+            if (shift[i] > 0 && spare <= 0)
+                return fail(JINC_ERR_INVALID_ARG, "JincResize: a sample shift needs integer samples narrower than their container (10, 12 or 14 bits in 16).");
+            if (shift[i] > spare)
+                return fail(JINC_ERR_INVALID_ARG, "JincResize: sample shift is larger than the padding of the sample's container (" +
+                                                      std::to_string(spare) + " bits).");
+        }
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
     if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
     if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
         return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
     return guarded([&] {
         hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_strided(*f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_frame_stride, nframes,
-                        static_cast<hipStream_t>(hip_stream));
+        enqueue_strided(*f, src, src_pitch, src_sample_step, src_sample_shift, src_frame_stride, dst, dst_pitch, dst_sample_step,
+                        dst_sample_shift, dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
     });
 }
 

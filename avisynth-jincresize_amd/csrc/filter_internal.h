@@ -256,7 +256,7 @@ struct jinc_filter {
     static constexpr int kForkEvents = 16;
     hipEvent_t ev_fork[kForkEvents] = {}, ev_join[kForkEvents] = {};
     unsigned fork_turn = 0;
-    // jinc_filter_process_device_strided (dispatch.cpp enqueue_strided): the dense planes strided ones are split into / merged from -- one allocation,
+    // jinc_filter_process_device_strided / _shifted (dispatch.cpp enqueue_strided): the dense planes strided or shifted ones are split into / merged from -- one allocation,
     // made on first use, grown when a call needs more -- and, because successive calls share them, an event behind each call's last
     // merge (a ring, as above) for the next call to wait on when it comes on another stream.
     void* strided_scratch = nullptr;
@@ -319,9 +319,11 @@ uint32_t direct_src_bytes(const void* base, uint64_t plane_bytes);
 void enqueue(jinc_filter& f, const void* const src[4], const int src_pitch[4], const size_t src_fs[4], void* const dst[4],
              const int dst_pitch[4], const size_t dst_fs[4], int nframes, hipStream_t stream);
 const char* last_interior_kernel_in_process();
-// ... enqueue for planes with a sample step (NULL step array: all ones; every step 1: enqueue itself)
-void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
-                     void* const dst[4], const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream);
+// ... enqueue for planes with a sample step and / or a sample shift (NULL step array: all ones; NULL shift array: all zeros; every
+// step 1 and every shift 0: enqueue itself).  The shifts have been checked against the format (filter.cpp).
+void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
+                     const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift,
+                     const size_t* dst_fs, int nframes, hipStream_t stream);
 // ... the channel groups of one side's planes (pure: test header jinc_debug_strided_groups); returns their number
 int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
                    const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]);

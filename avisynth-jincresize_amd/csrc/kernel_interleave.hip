@@ -10,6 +10,14 @@
 // amounts are compile-time constants.  Every interleaved byte of those pixels is read once (split) or written once (merge).
 // Sample-sized accesses take what is left: a row's tail, groups whose base or pitch is not a multiple of 4 bytes, and the merge of
 // an incomplete group -- there only the given channels' samples are stored, the bytes between them are not touched.
+//
+// SHIFTED forms (jinc_filter_process_device_shifted; 16-bit samples only): P010 / P012 / Y210 keep a sample in the HIGH bits of its
+// 16-bit word.  The split then stores raw >> shift, the merge (result << shift) & 0xffff -- padding bits are dropped on the way in
+// and written as zeros on the way out.  The shift is a kernel argument per channel (wave-uniform: shift and mask stay in scalar
+// registers) and is applied on the dense side to whole dwords of two samples, (w >> s) & mask or (w << s) & mask, two vector
+// instructions per dword, in all three access classes; tails and incomplete groups shift sample by sample.  Shifted is a template
+// parameter: the unshifted instantiations hold no trace of it.  Only the shifted forms have N = 1, a dense plane to a dense plane
+// (the luma of P010): a lane owns 16 contiguous bytes on both sides, a wave's access is 1 KiB in one piece.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -61,9 +69,15 @@ __device__ __forceinline__ void store_packed(char* p, uint32_t unit, const uint3
     }
 }
 
+// Two 16-bit samples in a dword, both shifted by s (0 .. 15): what crosses from one half into the other is masked away.
+__device__ __forceinline__ uint32_t down_mask(uint32_t s) { return (0xffffu >> s) * 0x10001u; }
+__device__ __forceinline__ uint32_t up_mask(uint32_t s) { return ((0xffffu << s) & 0xffffu) * 0x10001u; }
+
 // Row blockIdx.x * 4 + wave of frame blockIdx.y of group blockIdx.z.
-template <int B, int N>
+template <int B, int N, bool Shifted = false>
 __global__ __launch_bounds__(256) void split_samples_kernel(const InterleaveArgs a) {
+    static_assert(!Shifted || B == 2, "shifted samples are 16-bit words");
+    static_assert(Shifted || N > 1, "a dense plane without a shift needs no pass");
     using T = typename SampleOf<B>::type;
     constexpr uint32_t P = 16 / B;  // pixels a lane owns per step
     const InterleaveGroup& g = a.g[blockIdx.z];
@@ -71,6 +85,11 @@ __global__ __launch_bounds__(256) void split_samples_kernel(const InterleaveArgs
     if (row >= g.rows) return;
     const char* __restrict__ packed = g.packed + blockIdx.y * g.packed_frame_stride + static_cast<size_t>(row) * g.packed_pitch;
     const size_t dense = blockIdx.y * g.plane_frame_stride + static_cast<size_t>(row) * g.plane_pitch;
+    uint32_t sh[N], mask[N];  // (Shifted only; the same in every lane)
+    if constexpr (Shifted) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) sh[c] = g.shift[c], mask[c] = down_mask(sh[c]);
+    }
     for (uint32_t x = lane * P; x < g.vec_pixels; x += 64 * P) {
         uint32_t in[4 * N];
         load_packed<N>(packed + static_cast<size_t>(x) * (N * B), g.unit, in);
@@ -78,20 +97,34 @@ __global__ __launch_bounds__(256) void split_samples_kernel(const InterleaveArgs
         for (int c = 0; c < N; ++c) {
             if (!g.plane[c]) continue;
             uint32_t out[4] = {0u, 0u, 0u, 0u};
+            if constexpr (N == 1) {
+                out[0] = in[0], out[1] = in[1], out[2] = in[2], out[3] = in[3];
+            } else {
 #pragma unroll
-            for (int p = 0; p < static_cast<int>(P); ++p) put_sample<B>(out, p, get_sample<B>(in, p * N + c));
+                for (int p = 0; p < static_cast<int>(P); ++p) put_sample<B>(out, p, get_sample<B>(in, p * N + c));
+            }
+            if constexpr (Shifted) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) out[k] = (out[k] >> sh[c]) & mask[c];
+            }
             *reinterpret_cast<uint4*>(g.plane[c] + dense + static_cast<size_t>(x) * B) = make_uint4(out[0], out[1], out[2], out[3]);
         }
     }
     for (uint32_t x = g.vec_pixels + lane; x < g.width; x += 64) {
 #pragma unroll
-        for (int c = 0; c < N; ++c)
-            if (g.plane[c]) reinterpret_cast<T*>(g.plane[c] + dense)[x] = reinterpret_cast<const T*>(packed)[static_cast<size_t>(x) * N + c];
+        for (int c = 0; c < N; ++c) {
+            if (!g.plane[c]) continue;
+            T v = reinterpret_cast<const T*>(packed)[static_cast<size_t>(x) * N + c];
+            if constexpr (Shifted) v = static_cast<T>(v >> sh[c]);
+            reinterpret_cast<T*>(g.plane[c] + dense)[x] = v;
+        }
     }
 }
 
-template <int B, int N>
+template <int B, int N, bool Shifted = false>
 __global__ __launch_bounds__(256) void merge_samples_kernel(const InterleaveArgs a) {
+    static_assert(!Shifted || B == 2, "shifted samples are 16-bit words");
+    static_assert(Shifted || N > 1, "a dense plane without a shift needs no pass");
     using T = typename SampleOf<B>::type;
     constexpr uint32_t P = 16 / B;
     const InterleaveGroup& g = a.g[blockIdx.z];
@@ -99,6 +132,11 @@ __global__ __launch_bounds__(256) void merge_samples_kernel(const InterleaveArgs
     if (row >= g.rows) return;
     char* __restrict__ packed = g.packed + blockIdx.y * g.packed_frame_stride + static_cast<size_t>(row) * g.packed_pitch;
     const size_t dense = blockIdx.y * g.plane_frame_stride + static_cast<size_t>(row) * g.plane_pitch;
+    uint32_t sh[N], mask[N];  // (Shifted only; the same in every lane)
+    if constexpr (Shifted) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) sh[c] = g.shift[c], mask[c] = up_mask(sh[c]);
+    }
     for (uint32_t x = lane * P; x < g.vec_pixels; x += 64 * P) {  // (complete groups only: every byte of these pixels is a given sample)
         uint32_t out[4 * N];
 #pragma unroll
@@ -106,33 +144,58 @@ __global__ __launch_bounds__(256) void merge_samples_kernel(const InterleaveArgs
 #pragma unroll
         for (int c = 0; c < N; ++c) {
             const uint4 v = *reinterpret_cast<const uint4*>(g.plane[c] + dense + static_cast<size_t>(x) * B);
-            const uint32_t in[4] = {v.x, v.y, v.z, v.w};
+            uint32_t in[4] = {v.x, v.y, v.z, v.w};
+            if constexpr (Shifted) {
 #pragma unroll
-            for (int p = 0; p < static_cast<int>(P); ++p) put_sample<B>(out, p * N + c, get_sample<B>(in, p));
+                for (int k = 0; k < 4; ++k) in[k] = (in[k] << sh[c]) & mask[c];
+            }
+            if constexpr (N == 1) {
+                out[0] = in[0], out[1] = in[1], out[2] = in[2], out[3] = in[3];
+            } else {
+#pragma unroll
+                for (int p = 0; p < static_cast<int>(P); ++p) put_sample<B>(out, p * N + c, get_sample<B>(in, p));
+            }
         }
         store_packed<N>(packed + static_cast<size_t>(x) * (N * B), g.unit, out);
     }
     for (uint32_t x = g.vec_pixels + lane; x < g.width; x += 64) {
 #pragma unroll
-        for (int c = 0; c < N; ++c)
-            if (g.plane[c]) reinterpret_cast<T*>(packed)[static_cast<size_t>(x) * N + c] = reinterpret_cast<const T*>(g.plane[c] + dense)[x];
+        for (int c = 0; c < N; ++c) {
+            if (!g.plane[c]) continue;
+            T v = reinterpret_cast<const T*>(g.plane[c] + dense)[x];
+            if constexpr (Shifted) v = static_cast<T>(static_cast<uint32_t>(v) << sh[c]);  // (the store keeps the low 16 bits)
+            reinterpret_cast<T*>(packed)[static_cast<size_t>(x) * N + c] = v;
+        }
     }
 }
 
-template <bool Merge, int B, int N>
+template <bool Merge, int B, int N, bool Shifted = false>
 int launch(const InterleaveArgs& a, int nframes, hipStream_t s) {
     uint32_t rows = 0;
     for (int k = 0; k < a.ngroups; ++k) rows = a.g[k].rows > rows ? a.g[k].rows : rows;
     if (a.ngroups <= 0 || nframes <= 0 || rows == 0) return hipSuccess;
     const dim3 grid((rows + 3) / 4, static_cast<uint32_t>(nframes), static_cast<uint32_t>(a.ngroups));
-    if constexpr (Merge) hipLaunchKernelGGL((merge_samples_kernel<B, N>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((split_samples_kernel<B, N>), grid, dim3(256), 0, s, a);
+    if constexpr (Merge) hipLaunchKernelGGL((merge_samples_kernel<B, N, Shifted>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((split_samples_kernel<B, N, Shifted>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 template <bool Merge>
 int launch_by_shape(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
+    bool shifted = false;  // one shifted channel makes the launch a shifted one (its other channels shift by 0)
+    for (int k = 0; k < a.ngroups; ++k)
+        for (int c = 0; c < 4; ++c) shifted |= a.g[k].shift[c] != 0;
+    if (shifted) {
+        if (sample_bytes != 2) return hipErrorInvalidValue;
+        switch (step) {
+            case 1: return launch<Merge, 2, 1, true>(a, nframes, s);
+            case 2: return launch<Merge, 2, 2, true>(a, nframes, s);
+            case 3: return launch<Merge, 2, 3, true>(a, nframes, s);
+            case 4: return launch<Merge, 2, 4, true>(a, nframes, s);
+        }
+        return hipErrorInvalidValue;
+    }
     switch (sample_bytes * 8 + step) {
         case 1 * 8 + 2: return launch<Merge, 1, 2>(a, nframes, s);
         case 1 * 8 + 3: return launch<Merge, 1, 3>(a, nframes, s);

@@ -504,11 +504,15 @@ int launch_blit_rows(const BlitEntry* table_device, int first, int count, uint32
 // only); vec_pixels: the leading pixels of every row that move by such accesses, a multiple of the 16 / sample_bytes pixels a lane
 // owns -- the merge of an incomplete group has none (only the given channels' samples may be stored to), the split of one stops in
 // front of the row's last pixel, whose missing channels may lie behind the end of the caller's buffer.
+// shift[c] (jinc_filter_process_device_shifted, 16-bit samples): the packed side keeps channel c's sample in the high bits of its
+// word -- the dense plane holds packed >> shift, the packed side gets (dense << shift) & 0xffff.  A group with a shift may have
+// step 1: one dense plane of the caller's, shifted into / out of its dense stand-in.
 struct InterleaveGroup {
     char* packed = nullptr;
     char* plane[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t packed_frame_stride = 0, plane_frame_stride = 0;
     uint32_t packed_pitch = 0, plane_pitch = 0, width = 0, rows = 0, vec_pixels = 0, unit = 0;
+    uint8_t shift[4] = {0, 0, 0, 0};
 };
 // The groups of ONE launch travel as kernel arguments: a table in memory would have to stay untouched until the launch has run,
 // and the call returns before that.
@@ -517,6 +521,7 @@ struct InterleaveArgs {
     int ngroups = 0;
 };
 // One launch over every group and frame of `a`: sample_bytes 1, 2 or 4; step 2, 3 or 4 (the same for all groups of a launch).
+// With a non-zero shift in any group the launch takes the shifted forms: sample_bytes 2 only, step 1 .. 4.
 int launch_split_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream);
 int launch_merge_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream);
 

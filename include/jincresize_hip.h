@@ -249,7 +249,8 @@ JINC_API int jinc_filter_process_device(jinc_filter *f, const void *const src[4]
                                         int nframes, void *hip_stream);
 
 /* jinc_filter_process_device on planes whose samples need not lie side by side: the semi-planar frames of video decoders
- * (NV12, P010 / P016) and packed RGB(A).  Sample x of row y of frame n of plane i lies at
+ * (NV12, P016; 10-bit samples in the LOW bits of their words -- a decoder's P010 goes through jinc_filter_process_device_shifted
+ * below) and packed RGB(A).  Sample x of row y of frame n of plane i lies at
  *   base[i] + n * frame_stride[i] + y * pitch[i] + x * sample_step[i] * component_size;
  * steps are in samples, 1 .. 4 (1: dense), a NULL step array means all ones; planes keep the library's order (Y,U,V,A or
  * G,B,R,A).  NV12: U = uv, V = uv + 1 sample, both step 2.  BGRA: B = p, G = p + 1, R = p + 2, A = p + 3, all step 4.  Source
@@ -265,6 +266,31 @@ JINC_API int jinc_filter_process_device(jinc_filter *f, const void *const src[4]
 JINC_API int jinc_filter_process_device_strided(jinc_filter *f, const void *const src[4], const int src_pitch[4],
                                                 const int src_sample_step[4], const size_t src_frame_stride[4],
                                                 void *const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
+                                                const size_t dst_frame_stride[4], int nframes, void *hip_stream);
+
+/* jinc_filter_process_device_strided on 16-bit words that hold their sample in the HIGH bits, as hardware decoders and encoders
+ * write them: P010 (10 bits, shift 6), P012 (12 bits, shift 4), Y210 / Y212.  (The strided call reads and writes the sample in
+ * the LOW bits of its word; what it takes as "P010" is semi-planar YUV420P10 with low-aligned samples.)  Everything is as there,
+ * plus a shift in bits per plane and side; a NULL shift array means all zeros.
+ *   The value of a source sample is raw >> shift: the low `shift` bits are discarded whatever they hold.  The call computes
+ *   exactly what jinc_filter_process_device computes for dense planes of those values -- lrintf(clamp(r, 0, peak)) on the 10-bit
+ *   value, not a rounding of the 16-bit word -- and stores result << shift as the whole sample: padding bits are written as zeros.
+ * Source and destination shifts are independent (P010 in, planar low-aligned YUV420P10 out, or the reverse).
+ *   P010:  Y = y, step 1; U = uv, V = uv + 1 sample, step 2; all shift 6.       P012: the same with shift 4.
+ *   Y210:  Y = p, step 2; U = p + 1 sample, V = p + 3 samples, step 4; all shift 6 (filter: 4:2:2, 10 bits).
+ * A shift must lie in 0 .. 8 * component_size - bits_per_component and only integer samples take a non-zero one: in practice
+ * component_size 2 with 10, 12 or 14 bits.  A negative shift, a larger one, and any non-zero shift on an 8-bit, 16-bit, fp32 or
+ * binary16 filter are JINC_ERR_INVALID_ARG, each with a message of its own, before anything is queued.
+ * With every shift 0 the call IS jinc_filter_process_device_strided (the same launches); with every step 1 as well it is
+ * jinc_filter_process_device.  A plane with a non-zero shift on a side takes a dense stand-in of the filter's own on that side
+ * even at step 1, so the luma of a P010 frame lives in those dense planes too: one 1080p -> 4K frame needs about 31 MB of them
+ * instead of 5.5 MB, and the 1 GiB default (knob strided_scratch_bytes, test header) cuts a long call into slices of 33 frames
+ * where the unshifted call runs 128 at once.  The no-overwrite guarantee carries over: no byte of the destination is stored to
+ * unless it belongs to a sample of a given plane; the padding bits inside a sample belong to it. */
+JINC_API int jinc_filter_process_device_shifted(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                const int src_sample_step[4], const int src_sample_shift[4],
+                                                const size_t src_frame_stride[4], void *const dst[4], const int dst_pitch[4],
+                                                const int dst_sample_step[4], const int dst_sample_shift[4],
                                                 const size_t dst_frame_stride[4], int nframes, void *hip_stream);
 
 /* Block until everything enqueued on the filter's own stream (jinc_filter_get_frame) has finished.

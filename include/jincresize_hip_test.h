@@ -158,7 +158,7 @@ typedef enum jinc_knob {
     JINC_KNOB_STAGE_BANDS,            /* row bands a pageable plane is cut into between the CPU's copy and the DMA engine: default 4 (2 MiB each at least), 1 = whole planes (round 6) */
     JINC_KNOB_STAGE_DEFER_KB,         /* pageable frames of up to this many KiB of source in groups of 4 or more are copied to the library's pinned buffer when the group is launched (one job, one DMA copy per plane) instead of at submit: default 1536, 0 = never (round 6) */
     JINC_KNOB_QUAD_SHARE,             /* 0: the 2x tap-3 interior of integer planes without its frame-pair symmetry-class form (the plan's class check fails; tests, A/B) */
-    JINC_KNOB_STRIDED_SCRATCH_BYTES,  /* cap of the dense planes behind jinc_filter_process_device_strided in bytes (default 1 GiB): a call that needs more runs in slices of whole frames */
+    JINC_KNOB_STRIDED_SCRATCH_BYTES,  /* cap of the dense planes behind jinc_filter_process_device_strided / _shifted in bytes (default 1 GiB): a call that needs more runs in slices of whole frames; a shifted call keeps its luma there too */
     JINC_KNOB_COUNT
 } jinc_knob;
 JINC_API int jinc_debug_set_knob(int knob, double value);
