@@ -87,7 +87,7 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_batch_device_of_frame", "jinc_batch_process", "jinc_batch_free", "jinc_batch_last_error",
            "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share",
            "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided",
-           "jinc_filter_process_device_shifted"]
+           "jinc_filter_process_device_shifted", "jinc_filter_process_device_packed10", "jinc_packed10_layout"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -120,6 +120,8 @@ def lib():
         L.jinc_filter_process_device_strided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.jinc_filter_process_device_shifted.argtypes = [C.c_void_p] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_packed10.argtypes = [C.c_void_p] + [C.c_void_p] * 7 + [C.c_uint, C.c_void_p, C.c_int, C.c_void_p]
+        L.jinc_packed10_layout.argtypes = [C.c_char_p, C.c_int * 3, C.POINTER(C.c_uint)]
         L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
         L.jinc_debug_last_strided.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         L.jinc_filter_sync.argtypes = [C.c_void_p]
@@ -308,6 +310,17 @@ def last_strided() -> Tuple[int, int, int, int]:
     a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
     lib().jinc_debug_last_strided(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
     return a.value, b.value, c.value, d.value
+
+
+def packed10_layout(name: str) -> Tuple[List[int], int]:
+    """(field offsets in the library's plane order, the fill with every spare bit set) of a named 10:10:10:2 word for
+    Filter.process_device_packed10 (jinc_packed10_layout; no device needed): Y410, R10G10B10A2, ABGR2101010, XBGR2101010, ARGB2101010,
+    XRGB2101010, RGBA1010102, RGBX1010102, BGRA1010102, BGRX1010102, in either letter case."""
+    o, fill = (C.c_int * 3)(), C.c_uint()
+    rc = int(lib().jinc_packed10_layout(name.encode(), o, C.byref(fill)))
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return [int(o[i]) for i in range(3)], int(fill.value)
 
 
 class KernelMode(enum.IntEnum):
@@ -811,6 +824,26 @@ class Filter:
             self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_I4, src_shifts), arr(_S4, src_strides),
             arr(_P4, dst_ptrs), arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_I4, dst_shifts), arr(_S4, dst_strides), int(nframes),
             C.c_void_p(stream)))
+
+    def process_device_packed10(self, src_ptrs, src_pitches, src_offsets, src_strides, dst_ptrs, dst_pitches, dst_offsets, dst_fill,
+                                dst_strides, nframes: int, stream: int = 0) -> None:
+        """process_device on 10:10:10:2 words (jinc_filter_process_device_packed10): a side whose offsets are given is ONE buffer of
+        32-bit words, one per pixel (element 0 of its pointers, pitches and strides), plane i's value is (word >> offsets[i]) & 1023;
+        a side whose offsets are None is dense planes.  Stored words are the three results | (dst_fill & ~fields).  packed10_layout
+        names the usual words.  Frame strides may be None (one frame)."""
+        n = self.fmt.planes
+
+        def arr(kind, values, count):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(min(count, len(values))):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_packed10(
+            self._h, arr(_P4, src_ptrs, n), arr(_I4, src_pitches, n), arr(C.c_int * 3, src_offsets, 3), arr(_S4, src_strides, n),
+            arr(_P4, dst_ptrs, n), arr(_I4, dst_pitches, n), arr(C.c_int * 3, dst_offsets, 3), C.c_uint(int(dst_fill) & 0xFFFFFFFF),
+            arr(_S4, dst_strides, n), int(nframes), C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
     strided_groups = staticmethod(strided_groups)

@@ -967,37 +967,15 @@ int groups_of_side(const void* const base[4], const int pitch[4], const int* ste
     return ngroups;
 }
 
-}  // namespace
-
-int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
-                   const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
-    return groups_of_side(base, pitch, step, nullptr, frame_stride, width, height, component_size, nplanes, group_of, channel_of);
-}
-
-const StridedReport& last_strided_report() { return t_last_strided; }
-
-void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
-                     const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift,
-                     const size_t* dst_fs, int nframes, hipStream_t stream) {
-    bool dense = true;
-    for (int i = 0; i < f.planecount; ++i)
-        dense &= step_of(src_step, i) == 1 && step_of(dst_step, i) == 1 && shift_of(src_shift, i) == 0 && shift_of(dst_shift, i) == 0;
-    if (dense) {  // the call IS jinc_filter_process_device
-        enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
-        t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};
-        return;
-    }
+// The part every call with stand-ins shares (strided / shifted planes, 10:10:10:2 words): `in` / `out` say which planes of a side
+// take a dense stand-in (group_of >= 0; of those planes base, pitch and frame stride are not read here).  split(scratch, first
+// frame, frames per slice, frames now) queues the passes that fill the source stand-ins of one slice, merge(...) those that empty
+// the result stand-ins; both return their number of launches.
+template <class Split, class Merge>
+void run_on_stand_ins(jinc_filter& f, Side& in, Side& out, const void* const src[4], const int src_pitch[4], const size_t* src_fs,
+                      void* const dst[4], const int dst_pitch[4], const size_t* dst_fs, int nframes, hipStream_t stream, Split split,
+                      Merge merge) {
     const size_t sb = static_cast<size_t>(f.vi_in.component_size);
-    Side in, out;
-    for (int i = 0; i < f.planecount; ++i) {
-        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
-        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
-    }
-    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
-    in.ngroups = groups_of_side(src, src_pitch, src_step, src_shift, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
-    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, dst_shift, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(sb), f.planecount, out.group_of, out.channel_of);
-    check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
-    check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
 
     // Dense planes of the strided ones: pitch and frame stride multiples of 256 bytes, like the look-ahead pipeline's group buffers.
     size_t per_frame = 0;
@@ -1062,23 +1040,12 @@ void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pit
             s_now[i] = (i < f.planecount && in.group_of[i] < 0) ? static_cast<const char*>(src[i]) + static_cast<size_t>(k0) * sfs_run[i] : s_run[i];
             d_now[i] = (i < f.planecount && out.group_of[i] < 0) ? static_cast<char*>(dst[i]) + static_cast<size_t>(k0) * dfs_run[i] : d_run[i];
         }
-        InterleaveArgs split[5], merge[5];
-        fill_args(f, in, src, src_pitch, src_step, src_shift, src_fs, scratch, k0, slice, nframes, false, split);
-        fill_args(f, out, dst_c, dst_pitch, dst_step, dst_shift, dst_fs, scratch, k0, slice, nframes, true, merge);
         // Order on the caller's stream: split -> enqueue -> merge.  enqueue's side-stream kernels start behind ev_fork, which it records
         // on `stream` AFTER the split queued here, and `stream` goes on only behind ev_join, recorded on the side stream after its last
         // kernel: the merge queued below follows both streams' kernels.
-        for (int step = 1; step <= 4; ++step)  // (step 1: shifted dense planes)
-            if (split[step].ngroups) {
-                hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream)), "split launch");
-                ++report.split_launches;
-            }
+        report.split_launches += split(scratch, k0, slice, n);
         enqueue(f, s_now, sp_run, sfs_run, d_now, dp_run, dfs_run, n, stream);
-        for (int step = 1; step <= 4; ++step)
-            if (merge[step].ngroups) {
-                hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], static_cast<int>(sb), step, n, stream)), "merge launch");
-                ++report.merge_launches;
-            }
+        report.merge_launches += merge(scratch, k0, slice, n);
         ++report.slices;
     }
     hip_check(hipEventRecord(f.ev_strided[turn], stream), "hipEventRecord(strided)");
@@ -1086,6 +1053,139 @@ void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pit
     f.strided_pending = true;
     f.strided_last_stream = stream;
     t_last_strided = report;
+}
+
+// One side of a packed10 call as a launch argument.  fields: the three bit offsets (checked: filter.cpp).
+jinc::FieldArgs field_args(const Side& s, const void* base, int pitch, const size_t* fs, const int* fields, unsigned fill, char* scratch,
+                           int first_frame, int slice_frames, int nframes) {
+    jinc::FieldArgs a;
+    const size_t frame_stride = (fs && nframes > 1) ? fs[0] : 0;
+    a.packed = const_cast<char*>(static_cast<const char*>(base)) + static_cast<size_t>(first_frame) * frame_stride;
+    a.packed_frame_stride = frame_stride;
+    a.packed_pitch = static_cast<uint32_t>(pitch);
+    a.plane_pitch = static_cast<uint32_t>(s.dense_pitch[0]);
+    a.plane_frame_stride = s.dense_fs[0];
+    a.width = static_cast<uint32_t>(s.w[0]);
+    a.rows = static_cast<uint32_t>(s.h[0]);
+    const uintptr_t al = reinterpret_cast<uintptr_t>(base) | static_cast<uintptr_t>(pitch) | static_cast<uintptr_t>(frame_stride);
+    a.unit = al % 16 == 0 ? 16u : 4u;
+    a.vec_pixels = a.width / 8 * 8;
+    uint32_t mask = 0;
+    for (int c = 0; c < 3; ++c) {
+        a.plane[c] = scratch + s.offset[c] * static_cast<size_t>(slice_frames);
+        a.offset[c] = static_cast<uint32_t>(fields[c]);
+        mask |= 1023u << fields[c];
+    }
+    a.fill = fill & ~mask;
+    return a;
+}
+
+void check_packed10_side(const void* base, int pitch, const size_t* fs, int width, int nframes) {
+    if (!base) throw ArgError("JincResize: null plane pointer.");
+    if (reinterpret_cast<uintptr_t>(base) % 4) throw ArgError("JincResize: packed 10-bit words are not aligned to 4 bytes.");
+    if (pitch <= 0 || pitch % 4) throw ArgError("JincResize: pitch of packed 10-bit words is not a multiple of 4.");
+    if (fs && nframes > 1 && fs[0] % 4) throw ArgError("JincResize: frame stride of packed 10-bit words is not a multiple of 4.");
+    if (static_cast<size_t>(pitch) < 4 * static_cast<size_t>(width)) throw ArgError("JincResize: pitch of packed 10-bit words is smaller than 4 * width.");
+}
+
+}  // namespace
+
+int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
+                   const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
+    return groups_of_side(base, pitch, step, nullptr, frame_stride, width, height, component_size, nplanes, group_of, channel_of);
+}
+
+const StridedReport& last_strided_report() { return t_last_strided; }
+
+void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
+                     const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift,
+                     const size_t* dst_fs, int nframes, hipStream_t stream) {
+    bool dense = true;
+    for (int i = 0; i < f.planecount; ++i)
+        dense &= step_of(src_step, i) == 1 && step_of(dst_step, i) == 1 && shift_of(src_shift, i) == 0 && shift_of(dst_shift, i) == 0;
+    if (dense) {  // the call IS jinc_filter_process_device
+        enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
+        t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};
+        return;
+    }
+    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
+    Side in, out;
+    for (int i = 0; i < f.planecount; ++i) {
+        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
+        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
+    }
+    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
+    in.ngroups = groups_of_side(src, src_pitch, src_step, src_shift, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
+    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, dst_shift, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(sb), f.planecount, out.group_of, out.channel_of);
+    check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
+    check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
+    run_on_stand_ins(
+        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
+        [&](char* scratch, int k0, int slice, int n) {
+            InterleaveArgs split[5];
+            fill_args(f, in, src, src_pitch, src_step, src_shift, src_fs, scratch, k0, slice, nframes, false, split);
+            int launches = 0;
+            for (int step = 1; step <= 4; ++step)  // (step 1: shifted dense planes)
+                if (split[step].ngroups) {
+                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream)), "split launch");
+                    ++launches;
+                }
+            return launches;
+        },
+        [&](char* scratch, int k0, int slice, int n) {
+            InterleaveArgs merge[5];
+            fill_args(f, out, dst_c, dst_pitch, dst_step, dst_shift, dst_fs, scratch, k0, slice, nframes, true, merge);
+            int launches = 0;
+            for (int step = 1; step <= 4; ++step)
+                if (merge[step].ngroups) {
+                    hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], static_cast<int>(sb), step, n, stream)), "merge launch");
+                    ++launches;
+                }
+            return launches;
+        });
+}
+
+// ---- jinc_filter_process_device_packed10: Y410, R10G10B10A2 and kin -- three 10-bit samples in one 32-bit word per pixel ----
+// A packed side is ONE group of the filter's three planes: unpack_fields_kernel fills their dense stand-ins from the words,
+// pack_fields_kernel builds the words from the result stand-ins (kernel_interleave.hip).  Everything else -- the stand-ins'
+// 256-byte pitches, the slicing under strided_scratch_bytes, the order on the caller's stream, the event ring -- is
+// run_on_stand_ins, as for the strided and shifted calls.  Dense planes per frame: 3 x 2 bytes x the side's pixels (rows padded to
+// 256 bytes).  1080p -> 4K, both sides packed: 3 x (3840 x 1080 + 7680 x 2160) = 62 208 000 bytes, so the 1 GiB default holds
+// floor(1 073 741 824 / 62 208 000) = 17 frames -- below kSliceFrames, so no rounding: a call of 128 runs as 7 x 17 + 9.  Packed
+// source only: 12 441 600 bytes, 86 frames; packed destination only: 49 766 400 bytes, 21 frames.
+void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_fields, const size_t* src_fs,
+                      void* const dst[4], const int dst_pitch[4], const int* dst_fields, unsigned dst_fill, const size_t* dst_fs,
+                      int nframes, hipStream_t stream) {
+    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    if (!src_fields && !dst_fields) {  // the call IS jinc_filter_process_device
+        enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
+        return;
+    }
+    Side in, out;
+    for (int i = 0; i < f.planecount; ++i) {
+        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
+        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
+        in.group_of[i] = in.channel_of[i] = src_fields ? 0 : -1;
+        out.group_of[i] = out.channel_of[i] = dst_fields ? 0 : -1;
+    }
+    in.ngroups = src_fields ? 1 : 0;
+    out.ngroups = dst_fields ? 1 : 0;
+    if (src_fields) check_packed10_side(src[0], src_pitch[0], src_fs, in.w[0], nframes);
+    if (dst_fields) check_packed10_side(dst[0], dst_pitch[0], dst_fs, out.w[0], nframes);
+    run_on_stand_ins(
+        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
+        [&](char* scratch, int k0, int slice, int n) {
+            if (!src_fields) return 0;
+            const jinc::FieldArgs a = field_args(in, src[0], src_pitch[0], src_fs, src_fields, 0u, scratch, k0, slice, nframes);
+            hip_check(static_cast<hipError_t>(jinc::launch_unpack_fields(a, n, stream)), "unpack launch");
+            return 1;
+        },
+        [&](char* scratch, int k0, int slice, int n) {
+            if (!dst_fields) return 0;
+            const jinc::FieldArgs a = field_args(out, dst[0], dst_pitch[0], dst_fs, dst_fields, dst_fill, scratch, k0, slice, nframes);
+            hip_check(static_cast<hipError_t>(jinc::launch_pack_fields(a, n, stream)), "pack launch");
+            return 1;
+        });
 }
 
 }  // namespace host

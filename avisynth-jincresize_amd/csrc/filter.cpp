@@ -8,6 +8,8 @@
 //   jinc_filter_free        <- free_JincResize         (ref :632-647)
 //   jinc_alias_args         <- resizer()/resizer_jincresize<taps> (ref :1007-1040)
 // There is no CPU fallback: without a HIP device every frame call fails loudly.
+#include <cctype>
+
 #include "filter_internal.h"
 #include "knobs.h"
 
@@ -262,6 +264,67 @@ int jinc_filter_process_device_shifted(jinc_filter* f, const void* const src[4],
         enqueue_strided(*f, src, src_pitch, src_sample_step, src_sample_shift, src_frame_stride, dst, dst_pitch, dst_sample_step,
                         dst_sample_shift, dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
     });
+}
+
+int jinc_filter_process_device_packed10(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_field_offset[3],
+                                        const size_t src_frame_stride[4], void* const dst[4], const int dst_pitch[4],
+                                        const int dst_field_offset[3], unsigned dst_fill, const size_t dst_frame_stride[4], int nframes,
+                                        void* hip_stream) {
+    // the filter and the offsets first (they need no device), then the checks of jinc_filter_process_device_shifted in its order
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (src_field_offset || dst_field_offset) {
+        if (f->planecount != 3 || f->subsampled || f->half || f->vi_in.component_size != 2 || f->vi_in.bits_per_component != 10)
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: packed 10:10:10:2 words need a filter with three 10-bit components in 16-bit samples and no "
+                                              "sub-sampling (YUV444P10, RGBP10).");
+        for (const int* o : {src_field_offset, dst_field_offset}) {
+            for (int i = 0; o && i < 3; ++i)
+                if (o[i] < 0 || o[i] > 22) return fail(JINC_ERR_INVALID_ARG, "JincResize: a field offset of a packed 10:10:10:2 word must be in 0..22.");
+            for (int i = 0; o && i < 3; ++i)
+                for (int j = i + 1; j < 3; ++j)
+                    if (o[i] - o[j] < 10 && o[j] - o[i] < 10)
+                        return fail(JINC_ERR_INVALID_ARG, "JincResize: two fields of a packed 10:10:10:2 word overlap.");
+        }
+    }
+    if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_packed10(*f, src, src_pitch, src_field_offset, src_frame_stride, dst, dst_pitch, dst_field_offset, dst_fill, dst_frame_stride,
+                         nframes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int jinc_packed10_layout(const char* name, int field_offset[3], unsigned* opaque_fill) {
+    // offsets of the library's planes (Y, U, V or G, B, R) in the word
+    static const struct {
+        const char* name;
+        int offset[3];
+    } kLayouts[] = {
+        {"Y410", {10, 0, 20}},         // U 0, Y 10, V 20, A 30
+        {"R10G10B10A2", {10, 20, 0}},  // DXGI: R 0, G 10, B 20, A 30
+        {"ABGR2101010", {10, 20, 0}},  // DRM names list the components from the high bits down
+        {"XBGR2101010", {10, 20, 0}},
+        {"ARGB2101010", {10, 0, 20}},
+        {"XRGB2101010", {10, 0, 20}},
+        {"RGBA1010102", {12, 2, 22}},
+        {"RGBX1010102", {12, 2, 22}},
+        {"BGRA1010102", {12, 22, 2}},
+        {"BGRX1010102", {12, 22, 2}},
+    };
+    if (!name || !field_offset) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    for (const auto& l : kLayouts) {
+        size_t k = 0;
+        while (name[k] && l.name[k] && std::toupper(static_cast<unsigned char>(name[k])) == l.name[k]) ++k;
+        if (name[k] || l.name[k]) continue;
+        unsigned fields = 0;
+        for (int i = 0; i < 3; ++i) field_offset[i] = l.offset[i], fields |= 1023u << l.offset[i];
+        if (opaque_fill) *opaque_fill = ~fields;
+        return JINC_OK;
+    }
+    return fail(JINC_ERR_INVALID_ARG, std::string("JincResize: unknown packed 10:10:10:2 layout \"") + name + "\".");
 }
 
 int jinc_debug_strided_groups(const void* const base[4], const int pitch[4], const int step[4], const size_t frame_stride[4],

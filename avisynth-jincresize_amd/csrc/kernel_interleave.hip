@@ -18,6 +18,14 @@
 // instructions per dword, in all three access classes; tails and incomplete groups shift sample by sample.  Shifted is a template
 // parameter: the unshifted instantiations hold no trace of it.  Only the shifted forms have N = 1, a dense plane to a dense plane
 // (the luma of P010): a lane owns 16 contiguous bytes on both sides, a wave's access is 1 KiB in one piece.
+//
+// FIELD forms (jinc_filter_process_device_packed10): Y410 and R10G10B10A2-style frames keep three 10-bit samples in ONE 32-bit word
+// per pixel, at bit offsets that are no byte offsets.  unpack_fields_kernel stores (word >> offset[c]) & 1023 into three dense 16-bit
+// planes, pack_fields_kernel builds (r0 << o0) | (r1 << o1) | (r2 << o2) | fill in registers and stores the whole word once; it never
+// reads the destination.  Same shape: grid = row blocks x frames, a wave owns a row.  A lane owns 8 pixels per step: two 16-byte
+// accesses on the word side (consecutive lanes at consecutive 32-byte pieces, 2 KiB per wave in one piece; eight dwords where base,
+// pitch or frame stride is a multiple of 4 only) and one 16-byte access per dense plane.  The offsets and the fill are kernel
+// arguments: wave-uniform, in scalar registers.  The rest of a row moves word by word.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -210,7 +218,110 @@ int launch_by_shape(const InterleaveArgs& a, int sample_bytes, int step, int nfr
     return hipErrorInvalidValue;  // (no kernel for this shape: an error, never a silent skip)
 }
 
+// ---- 10:10:10:2 words (kernels.h FieldArgs) ----
+// 16 bytes as ONE access (a vector type of the compiler's: the access is not taken apart into its elements).
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__host__ __device__ __forceinline__ void load16(const char* p, uint32_t* w) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(p);
+    w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+}
+__host__ __device__ __forceinline__ void store16(char* p, const uint32_t* w) {
+    u32x4 v;
+    v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
+    *reinterpret_cast<u32x4*>(p) = v;
+}
+// The 8 words of a lane's pixels: two 16-byte accesses, or eight dwords.
+__host__ __device__ __forceinline__ void load_words(const char* p, uint32_t unit, uint32_t* w) {
+    if (unit == 16) {
+        load16(p, w), load16(p + 16, w + 4);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[k] = *reinterpret_cast<const uint32_t*>(p + 4 * k);
+    }
+}
+__host__ __device__ __forceinline__ void store_words(char* p, uint32_t unit, const uint32_t* w) {
+    if (unit == 16) {
+        store16(p, w), store16(p + 16, w + 4);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) *reinterpret_cast<uint32_t*>(p + 4 * k) = w[k];
+    }
+}
+
+// One lane's share of one row.  __host__ too: the index arithmetic can be run lane by lane on the CPU against exactly sized buffers.
+__host__ __device__ inline void unpack_fields_row(const FieldArgs& a, uint32_t frame, uint32_t row, uint32_t lane) {
+    const char* __restrict__ packed = a.packed + frame * a.packed_frame_stride + static_cast<size_t>(row) * a.packed_pitch;
+    const size_t dense = frame * a.plane_frame_stride + static_cast<size_t>(row) * a.plane_pitch;
+    for (uint32_t x = lane * 8; x < a.vec_pixels; x += 64 * 8) {
+        uint32_t w[8];
+        load_words(packed + static_cast<size_t>(x) * 4, a.unit, w);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            uint32_t out[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) out[k] = ((w[2 * k] >> a.offset[c]) & 1023u) | (((w[2 * k + 1] >> a.offset[c]) & 1023u) << 16);
+            store16(a.plane[c] + dense + static_cast<size_t>(x) * 2, out);
+        }
+    }
+    for (uint32_t x = a.vec_pixels + lane; x < a.width; x += 64) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(packed)[x];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) reinterpret_cast<uint16_t*>(a.plane[c] + dense)[x] = static_cast<uint16_t>((w >> a.offset[c]) & 1023u);
+    }
+}
+
+__host__ __device__ inline void pack_fields_row(const FieldArgs& a, uint32_t frame, uint32_t row, uint32_t lane) {
+    char* __restrict__ packed = a.packed + frame * a.packed_frame_stride + static_cast<size_t>(row) * a.packed_pitch;
+    const size_t dense = frame * a.plane_frame_stride + static_cast<size_t>(row) * a.plane_pitch;
+    for (uint32_t x = lane * 8; x < a.vec_pixels; x += 64 * 8) {
+        uint32_t w[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[k] = a.fill;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            uint32_t in[4];
+            load16(a.plane[c] + dense + static_cast<size_t>(x) * 2, in);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {  // (results are at most 1023; the mask keeps a field inside its bits whatever the plane holds)
+                w[2 * k] |= (in[k] & 1023u) << a.offset[c];
+                w[2 * k + 1] |= ((in[k] >> 16) & 1023u) << a.offset[c];
+            }
+        }
+        store_words(packed + static_cast<size_t>(x) * 4, a.unit, w);
+    }
+    for (uint32_t x = a.vec_pixels + lane; x < a.width; x += 64) {
+        uint32_t w = a.fill;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) w |= (static_cast<uint32_t>(reinterpret_cast<const uint16_t*>(a.plane[c] + dense)[x]) & 1023u) << a.offset[c];
+        reinterpret_cast<uint32_t*>(packed)[x] = w;
+    }
+}
+
+// Row blockIdx.x * 4 + wave of frame blockIdx.y.
+__global__ __launch_bounds__(256) void unpack_fields_kernel(const FieldArgs a) {
+    const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row < a.rows) unpack_fields_row(a, blockIdx.y, row, threadIdx.x & 63u);
+}
+__global__ __launch_bounds__(256) void pack_fields_kernel(const FieldArgs a) {
+    const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row < a.rows) pack_fields_row(a, blockIdx.y, row, threadIdx.x & 63u);
+}
+
+template <bool Pack>
+int launch_fields(const FieldArgs& a, int nframes, void* stream) {
+    if (nframes <= 0 || a.rows == 0 || a.width == 0) return hipSuccess;
+    if (a.unit != 16 && a.unit != 4) return hipErrorInvalidValue;  // (no sample-sized form: a word is the smallest access)
+    const dim3 grid((a.rows + 3) / 4, static_cast<uint32_t>(nframes));
+    if constexpr (Pack) hipLaunchKernelGGL(pack_fields_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL(unpack_fields_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+int launch_unpack_fields(const FieldArgs& a, int nframes, void* stream) { return launch_fields<false>(a, nframes, stream); }
+
+int launch_pack_fields(const FieldArgs& a, int nframes, void* stream) { return launch_fields<true>(a, nframes, stream); }
 
 int launch_split_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream) {
     return launch_by_shape<false>(a, sample_bytes, step, nframes, stream);

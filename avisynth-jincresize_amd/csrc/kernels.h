@@ -525,6 +525,26 @@ struct InterleaveArgs {
 int launch_split_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream);
 int launch_merge_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream);
 
+// 10:10:10:2 words <-> three dense 16-bit planes (kernel_interleave.hip; jinc_filter_process_device_packed10).  One little-endian
+// 32-bit word per pixel: pixel x of row y of frame n at packed + n * packed_frame_stride + y * packed_pitch + 4 * x, its value of
+// plane c in bits offset[c] .. offset[c] + 9; the dense plane of c holds that value in a 16-bit sample at plane[c] +
+// n * plane_frame_stride + y * plane_pitch + 2 * x.  The three planes have one size; they are the filter's own (bases, pitch and
+// frame stride multiples of 256 bytes).  packed base, pitch and frame stride are multiples of 4 (dispatch.cpp refuses others).
+// unit: 16 where they are multiples of 16 as well (16-byte accesses on the word side), else 4 (dwords); vec_pixels: the leading
+// pixels of a row that move 8 per lane, a multiple of 8; the rest of the row moves word by word.
+// fill (pack only): the bits of every stored word outside the three fields -- the caller's dst_fill with the fields cleared.
+struct FieldArgs {
+    char* packed = nullptr;
+    char* plane[3] = {nullptr, nullptr, nullptr};
+    size_t packed_frame_stride = 0, plane_frame_stride = 0;
+    uint32_t packed_pitch = 0, plane_pitch = 0, width = 0, rows = 0, vec_pixels = 0, unit = 4;
+    uint32_t offset[3] = {0, 0, 0};
+    uint32_t fill = 0;
+};
+// One launch over every row and frame of `a`.
+int launch_unpack_fields(const FieldArgs& a, int nframes, void* stream);
+int launch_pack_fields(const FieldArgs& a, int nframes, void* stream);
+
 // Measurement hook (kernel_probe.hip): `samplers` single-lane workgroups stamp the shader clock counter and the 100 MHz
 // real-time counter until *stop_flag (device memory) becomes non-zero or max_seconds pass; out[2 k] = shader ticks,
 // out[2 k + 1] = real-time ticks of sampler k.

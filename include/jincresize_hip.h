@@ -293,6 +293,48 @@ JINC_API int jinc_filter_process_device_shifted(jinc_filter *f, const void *cons
                                                 const int dst_sample_step[4], const int dst_sample_shift[4],
                                                 const size_t dst_frame_stride[4], int nframes, void *hip_stream);
 
+/* jinc_filter_process_device on frames that keep three 10-bit samples in ONE 32-bit word per pixel (10:10:10:2): Y410 (4:4:4
+ * 10-bit as decoders and VA-API / DXGI surfaces carry it), R10G10B10A2 / A2B10G10R10 and the DRM XRGB2101010, XBGR2101010,
+ * RGBX1010102, BGRX1010102 orders (HDR10 swap chains and scan-out).  Neither a sample step nor a shift describes them: the
+ * samples sit at bit offsets that are no byte offsets.
+ *   A side whose field_offset array is NULL is dense planes, exactly as in jinc_filter_process_device; with both NULL the call
+ *   IS that call (the same launches, on any filter).  A side with an array is ONE buffer of little-endian 32-bit words, one per
+ *   pixel: only element [0] of its base, pitch and frame stride arrays is read.  Pixel x of row y of frame n is the word at
+ *   base[0] + n * frame_stride[0] + y * pitch[0] + 4 * x, and its value of plane i (library order Y,U,V or G,B,R) is
+ *   (word >> field_offset[i]) & 1023.  Source and destination are independent: Y410 in and planar YUV444P10 out, the reverse,
+ *   or different words on the two sides.
+ *   The call computes exactly what jinc_filter_process_device computes for dense low-aligned 10-bit planes of those values.
+ *   Source bits outside the three fields are ignored whatever they hold (the 2-bit alpha is not resampled).  A destination word
+ *   is stored whole, (r0 << o0) | (r1 << o1) | (r2 << o2) | (dst_fill & ~fields): the spare bits belong to the pixel, so
+ *   dst_fill 0xC0000000 makes an opaque Y410 / A2.. word.  No byte outside the `width` words of each row of each frame is
+ *   stored to: row padding and the gaps between frames stay as they are.  The destination is never read.
+ * Accepted only on a filter with three components, no sub-sampling, component_size 2 and bits_per_component 10 (YUV444P10,
+ * RGBP10).  Any other filter (four components, fp32 and binary16 included), an offset outside 0 .. 22, and two fields that
+ * overlap are JINC_ERR_INVALID_ARG, each with a message of its own, before the device check and before anything is queued;
+ * then null arguments, nframes and frame strides as for jinc_filter_process_device_shifted.  A packed base, pitch or frame
+ * stride that is no multiple of 4 and a pitch below 4 * width are JINC_ERR_INVALID_ARG with nothing written.  Base, pitch and
+ * frame stride that are multiples of 16 get 16-byte accesses, others dwords.
+ * A packed side takes dense stand-ins of the filter's own for its three planes (the scratch of the strided call, same knob
+ * strided_scratch_bytes, same ordering between calls): 3 x 2 bytes per pixel of that side, rows padded to 256 bytes.  1080p ->
+ * 4K with both sides packed is 3 x 2 x (1920 x 1080 + 3840 x 2160) = 62 208 000 bytes per frame, so the 1 GiB default runs a
+ * long call in slices of 17 frames (128 frames: 7 x 17 + 9); with only the source packed 86 frames fit, with only the
+ * destination 21.  Callers that send long calls raise the knob. */
+JINC_API int jinc_filter_process_device_packed10(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                 const int src_field_offset[3], const size_t src_frame_stride[4],
+                                                 void *const dst[4], const int dst_pitch[4], const int dst_field_offset[3],
+                                                 unsigned dst_fill, const size_t dst_frame_stride[4], int nframes,
+                                                 void *hip_stream);
+
+/* The field offsets of a named 10:10:10:2 word in the library's plane order, and the fill that sets every spare bit (an opaque
+ * pixel); opaque_fill may be NULL.  Needs no device.  Names match without regard to case; an unknown one is
+ * JINC_ERR_INVALID_ARG.
+ *   Y410                                                  {10,  0, 20}   U 0, Y 10, V 20, A 30
+ *   R10G10B10A2 (DXGI) = DRM ABGR2101010 / XBGR2101010    {10, 20,  0}   R 0, G 10, B 20       (planes G, B, R)
+ *   XRGB2101010 / ARGB2101010                             {10,  0, 20}   B 0, G 10, R 20
+ *   RGBX1010102 / RGBA1010102                             {12,  2, 22}   B 2, G 12, R 22
+ *   BGRX1010102 / BGRA1010102                             {12, 22,  2}   R 2, G 12, B 22 */
+JINC_API int jinc_packed10_layout(const char *name, int field_offset[3], unsigned *opaque_fill);
+
 /* Block until everything enqueued on the filter's own stream (jinc_filter_get_frame) has finished.
  * Work given to jinc_filter_process_device is synchronised by the caller through its stream. */
 JINC_API int jinc_filter_sync(jinc_filter *f);
