@@ -527,190 +527,6 @@ __device__ __forceinline__ void quad_pixel7(f32x2& acc0, f32x2& acc1, const f32x
 #undef JINC_QUAD_STEP
 }
 
-template <typename T, int RG>
-__global__ __launch_bounds__(256, 6) void ewa_periodic_quad_kernel(const PeriodicArgs a, const PlaneIO io) {
-    constexpr int FS = 7;
-    using Cfg = PeriodicCfg<FS, RG>;
-    static_assert(RG % 4 == 0, "the four waves of a workgroup take RG / 4 row groups each");
-    __shared__ float tile[Cfg::kLdsRows * Cfg::kLdsPitch];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int tile_x, tile_y;
-    swizzled_tile(tile_x, tile_y);
-    const int i0 = tile_x * kTileCols;
-    const int j0 = tile_y * Cfg::kTileRows;
-    const size_t frame = blockIdx.z;
-    if (skips_frame(a, frame)) return;  // float planes: the other launch's frame
-    {   // stage the source tile as fp32, all loads in front of the LDS writes (see ewa_periodic_kernel)
-        const int gx0 = a.min_sx + i0;
-        const int gy0 = a.min_sy + j0;
-        const char* sbase = static_cast<const char*>(io.src) + frame * io.src_frame_stride;
-        constexpr int kRowsPerWave = (Cfg::kLdsRows + 3) / 4;
-        constexpr int kColsPerLane = (Cfg::kLdsCols + 63) / 64;
-        T staged[kRowsPerWave][kColsPerLane];
-        NonFinite<T> nonfinite(a, frame);
-#pragma unroll
-        for (int i = 0; i < kRowsPerWave; ++i) {
-            int gy = gy0 + wave + 4 * i;
-            gy = gy < a.src_h ? gy : a.src_h - 1;
-            const T* srow = reinterpret_cast<const T*>(sbase + static_cast<size_t>(gy) * io.src_pitch);
-#pragma unroll
-            for (int k = 0; k < kColsPerLane; ++k) {
-                int gx = gx0 + lane + 64 * k;
-                gx = gx < a.src_w ? gx : a.src_w - 1;
-                staged[i][k] = srow[gx];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < kRowsPerWave; ++i) {
-            const int r = wave + 4 * i;
-#pragma unroll
-            for (int k = 0; k < kColsPerLane; ++k) {
-                const int c = lane + 64 * k;
-                if (r < Cfg::kLdsRows && c < Cfg::kLdsCols) tile[r * Cfg::kLdsPitch + c] = nonfinite.take(staged[i][k]);
-            }
-        }
-    }
-    __syncthreads();
-    if ((i0 + lane) >= a.ni) return;  // no barrier below
-
-    const JINC_CONSTANT f32x2* quad = (const JINC_CONSTANT f32x2*)(a.quad);
-    // both phases of an axis share the window origin (host: quad != nullptr only then)
-    const float* base = tile + (a.start_y[0] - a.min_sy) * Cfg::kLdsPitch + (a.start_x[0] - a.min_sx) + lane;
-    const BufferRsrc drsrc = make_rsrc(static_cast<char*>(io.dst) + frame * io.dst_frame_stride,
-                                       static_cast<uint32_t>(io.dst_pitch) * a.dst_h);  // wave-uniform
-    const uint32_t xoff = static_cast<uint32_t>(a.ix0 + 2 * (i0 + lane)) * static_cast<uint32_t>(sizeof(T));
-
-    constexpr int kGroupsPerWave = RG / 4;
-    const int g_first = wave * kGroupsPerWave;
-    if (j0 + g_first * FS >= a.nj) return;  // wave-uniform: bottom tiles
-    f32x2 win[25];
-    {
-        const float* wb = base + (g_first * FS) * Cfg::kLdsPitch;
-        quad_load_row7<0>(win, wb + 0 * Cfg::kLdsPitch);
-        quad_load_row7<1>(win, wb + 1 * Cfg::kLdsPitch);
-        quad_load_row7<2>(win, wb + 2 * Cfg::kLdsPitch);
-        quad_load_row7<3>(win, wb + 3 * Cfg::kLdsPitch);
-        quad_load_row7<4>(win, wb + 4 * Cfg::kLdsPitch);
-        quad_load_row7<5>(win, wb + 5 * Cfg::kLdsPitch);
-    }
-    for (int g = g_first; g < g_first + kGroupsPerWave; ++g) {
-        if (j0 + g * FS >= a.nj) break;  // wave-uniform
-        const float* gbase = base + (g * FS) * Cfg::kLdsPitch;
-#define JINC_QUAD_ROW(U)                                                                                          \
-    {                                                                                                             \
-        quad_load_row7<(U + FS - 1) % FS>(win, gbase + (U + FS - 1) * Cfg::kLdsPitch);                             \
-        f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};                                                                \
-        uint32_t zero;                                                                                             \
-        asm volatile("s_mov_b32 %0, 0" : "=s"(zero)); /* opaque: keeps the coefficient loads inside the row loop */ \
-        quad_pixel7<U>(acc0, acc1, win, quad + zero);                                                              \
-        const int j = j0 + g * FS + U;                                                                             \
-        if (j < a.nj) {                                                                                            \
-            const uint32_t so = static_cast<uint32_t>(a.iy0 + 2 * j) * io.dst_pitch;                               \
-            store_pair_buf<T>(drsrc, xoff, so, acc0, io.peak);                                                     \
-            store_pair_buf<T>(drsrc, xoff, so + static_cast<uint32_t>(io.dst_pitch), acc1, io.peak);               \
-        }                                                                                                          \
-    }
-        JINC_QUAD_ROW(0) JINC_QUAD_ROW(1) JINC_QUAD_ROW(2) JINC_QUAD_ROW(3) JINC_QUAD_ROW(4) JINC_QUAD_ROW(5) JINC_QUAD_ROW(6)
-#undef JINC_QUAD_ROW
-    }
-}
-
-// fs 9 (tap 4 at 2x: C4): the same kernel with a 9 x 9 window (41 register pairs: 5 waves per SIMD, as the window kernel of
-// fs 9) and the coefficient pairs of the two phase rows taken alternately (quad_pixel9).
-template <typename T, int RG>
-__global__ __launch_bounds__(256, 5) void ewa_periodic_quad9_kernel(const PeriodicArgs a, const PlaneIO io) {
-    constexpr int FS = 9;
-    using Cfg = PeriodicCfg<FS, RG>;
-    static_assert(RG % 4 == 0, "the four waves of a workgroup take RG / 4 row groups each");
-    __shared__ float tile[Cfg::kLdsRows * Cfg::kLdsPitch];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int tile_x, tile_y;
-    swizzled_tile(tile_x, tile_y);
-    const int i0 = tile_x * kTileCols;
-    const int j0 = tile_y * Cfg::kTileRows;
-    const size_t frame = blockIdx.z;
-    if (skips_frame(a, frame)) return;  // float planes: the other launch's frame
-    {   // stage the source tile as fp32, all loads in front of the LDS writes (see ewa_periodic_kernel)
-        const int gx0 = a.min_sx + i0;
-        const int gy0 = a.min_sy + j0;
-        const char* sbase = static_cast<const char*>(io.src) + frame * io.src_frame_stride;
-        constexpr int kRowsPerWave = (Cfg::kLdsRows + 3) / 4;
-        constexpr int kColsPerLane = (Cfg::kLdsCols + 63) / 64;
-        T staged[kRowsPerWave][kColsPerLane];
-        NonFinite<T> nonfinite(a, frame);
-#pragma unroll
-        for (int i = 0; i < kRowsPerWave; ++i) {
-            int gy = gy0 + wave + 4 * i;
-            gy = gy < a.src_h ? gy : a.src_h - 1;
-            const T* srow = reinterpret_cast<const T*>(sbase + static_cast<size_t>(gy) * io.src_pitch);
-#pragma unroll
-            for (int k = 0; k < kColsPerLane; ++k) {
-                int gx = gx0 + lane + 64 * k;
-                gx = gx < a.src_w ? gx : a.src_w - 1;
-                staged[i][k] = srow[gx];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < kRowsPerWave; ++i) {
-            const int r = wave + 4 * i;
-#pragma unroll
-            for (int k = 0; k < kColsPerLane; ++k) {
-                const int c = lane + 64 * k;
-                if (r < Cfg::kLdsRows && c < Cfg::kLdsCols) tile[r * Cfg::kLdsPitch + c] = nonfinite.take(staged[i][k]);
-            }
-        }
-    }
-    __syncthreads();
-    if ((i0 + lane) >= a.ni) return;  // no barrier below
-
-    const JINC_CONSTANT f32x2* quad = (const JINC_CONSTANT f32x2*)(a.quad);
-    // both phases of an axis share the window origin (host: quad != nullptr only then)
-    const float* base = tile + (a.start_y[0] - a.min_sy) * Cfg::kLdsPitch + (a.start_x[0] - a.min_sx) + lane;
-    const BufferRsrc drsrc = make_rsrc(static_cast<char*>(io.dst) + frame * io.dst_frame_stride,
-                                       static_cast<uint32_t>(io.dst_pitch) * a.dst_h);  // wave-uniform
-    const uint32_t xoff = static_cast<uint32_t>(a.ix0 + 2 * (i0 + lane)) * static_cast<uint32_t>(sizeof(T));
-
-    constexpr int kGroupsPerWave = RG / 4;
-    const int g_first = wave * kGroupsPerWave;
-    if (j0 + g_first * FS >= a.nj) return;  // wave-uniform: bottom tiles
-    f32x2 win[41];
-    {
-        const float* wb = base + (g_first * FS) * Cfg::kLdsPitch;
-        quad_load_row9<0>(win, wb + 0 * Cfg::kLdsPitch);
-        quad_load_row9<1>(win, wb + 1 * Cfg::kLdsPitch);
-        quad_load_row9<2>(win, wb + 2 * Cfg::kLdsPitch);
-        quad_load_row9<3>(win, wb + 3 * Cfg::kLdsPitch);
-        quad_load_row9<4>(win, wb + 4 * Cfg::kLdsPitch);
-        quad_load_row9<5>(win, wb + 5 * Cfg::kLdsPitch);
-        quad_load_row9<6>(win, wb + 6 * Cfg::kLdsPitch);
-        quad_load_row9<7>(win, wb + 7 * Cfg::kLdsPitch);
-    }
-    for (int g = g_first; g < g_first + kGroupsPerWave; ++g) {
-        if (j0 + g * FS >= a.nj) break;  // wave-uniform
-        const float* gbase = base + (g * FS) * Cfg::kLdsPitch;
-#define JINC_QUAD_ROW(U)                                                                                          \
-    {                                                                                                             \
-        quad_load_row9<(U + FS - 1) % FS>(win, gbase + (U + FS - 1) * Cfg::kLdsPitch);                             \
-        f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};                                                                \
-        uint32_t zero;                                                                                             \
-        asm volatile("s_mov_b32 %0, 0" : "=s"(zero)); /* opaque: keeps the coefficient loads inside the row loop */ \
-        quad_pixel9<U>(acc0, acc1, win, quad + zero);                                                              \
-        const int j = j0 + g * FS + U;                                                                             \
-        if (j < a.nj) {                                                                                            \
-            const uint32_t so = static_cast<uint32_t>(a.iy0 + 2 * j) * io.dst_pitch;                               \
-            store_pair_buf<T>(drsrc, xoff, so, acc0, io.peak);                                                     \
-            store_pair_buf<T>(drsrc, xoff, so + static_cast<uint32_t>(io.dst_pitch), acc1, io.peak);               \
-        }                                                                                                          \
-    }
-        JINC_QUAD_ROW(0) JINC_QUAD_ROW(1) JINC_QUAD_ROW(2) JINC_QUAD_ROW(3) JINC_QUAD_ROW(4) JINC_QUAD_ROW(5) JINC_QUAD_ROW(6) JINC_QUAD_ROW(7) JINC_QUAD_ROW(8)
-#undef JINC_QUAD_ROW
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Periodic interior kernel, quad form on a trimmed 8 x 8 support (tap 4 at 2x: Jinc64Resize, C4)
 // ------------------------------------------------------------------------------------------------
@@ -865,12 +681,52 @@ __device__ __forceinline__ void quad_pixel8(f32x2& acc0, f32x2& acc1, const f32x
 #undef JINC_QUAD8_STEP
 }
 
-template <typename T, int RG, uint32_t TR8>
-__global__ __launch_bounds__(256, 6) void ewa_periodic_quad8_kernel(const PeriodicArgs a, const PlaneIO io) {
-    constexpr int FS = 8;
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order: a loop whose index is a compile-time constant.
+template <typename F, int... I>
+__device__ __forceinline__ void for_each_index_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void for_each_index(F&& f) {
+    for_each_index_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// The three one-period quad kernels are one body (quad_body).  Form: the filter size, the register pairs of the FS x FS window,
+// the loader of window slot SLOT and the chains of one output row pair at window rotation U.
+struct QuadForm7 {
+    static constexpr int FS = 7, kWinPairs = 25;
+    template <int SLOT>
+    static __device__ __forceinline__ void load_row(f32x2 (&w)[kWinPairs], const float* p) { quad_load_row7<SLOT>(w, p); }
+    template <int U>
+    static __device__ __forceinline__ void pixel(f32x2& acc0, f32x2& acc1, const f32x2 (&w)[kWinPairs], const JINC_CONSTANT f32x2* quad) {
+        quad_pixel7<U>(acc0, acc1, w, quad);
+    }
+};
+struct QuadForm9 {
+    static constexpr int FS = 9, kWinPairs = 41;
+    template <int SLOT>
+    static __device__ __forceinline__ void load_row(f32x2 (&w)[kWinPairs], const float* p) { quad_load_row9<SLOT>(w, p); }
+    template <int U>
+    static __device__ __forceinline__ void pixel(f32x2& acc0, f32x2& acc1, const f32x2 (&w)[kWinPairs], const JINC_CONSTANT f32x2* quad) {
+        quad_pixel9<U>(acc0, acc1, w, quad);
+    }
+};
+template <uint32_t TR8>
+struct QuadForm8 {
+    static constexpr int FS = 8, kWinPairs = 32;
+    template <int SLOT>
+    static __device__ __forceinline__ void load_row(f32x2 (&w)[kWinPairs], const float* p) { quad_load_row8<SLOT>(w, p); }
+    template <int U>
+    static __device__ __forceinline__ void pixel(f32x2& acc0, f32x2& acc1, const f32x2 (&w)[kWinPairs], const JINC_CONSTANT f32x2* quad) {
+        quad_pixel8<U, TR8>(acc0, acc1, w, quad);
+    }
+};
+
+template <typename T, int RG, typename Form>
+__device__ __forceinline__ void quad_body(const PeriodicArgs& a, const PlaneIO& io, float* tile) {
+    constexpr int FS = Form::FS;
     using Cfg = PeriodicCfg<FS, RG>;
     static_assert(RG % 4 == 0, "the four waves of a workgroup take RG / 4 row groups each");
-    __shared__ float tile[Cfg::kLdsRows * Cfg::kLdsPitch];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -914,6 +770,7 @@ __global__ __launch_bounds__(256, 6) void ewa_periodic_quad8_kernel(const Period
     if ((i0 + lane) >= a.ni) return;  // no barrier below
 
     const JINC_CONSTANT f32x2* quad = (const JINC_CONSTANT f32x2*)(a.quad);
+    // both phases of an axis share the window origin (host: quad != nullptr only then)
     const float* base = tile + (a.start_y[0] - a.min_sy) * Cfg::kLdsPitch + (a.start_x[0] - a.min_sx) + lane;
     const BufferRsrc drsrc = make_rsrc(static_cast<char*>(io.dst) + frame * io.dst_frame_stride,
                                        static_cast<uint32_t>(io.dst_pitch) * a.dst_h);  // wave-uniform
@@ -922,37 +779,54 @@ __global__ __launch_bounds__(256, 6) void ewa_periodic_quad8_kernel(const Period
     constexpr int kGroupsPerWave = RG / 4;
     const int g_first = wave * kGroupsPerWave;
     if (j0 + g_first * FS >= a.nj) return;  // wave-uniform: bottom tiles
-    f32x2 win[32];
-    {
-        const float* wb = base + (g_first * FS) * Cfg::kLdsPitch;
-        quad_load_row8<0>(win, wb + 0 * Cfg::kLdsPitch);
-        quad_load_row8<1>(win, wb + 1 * Cfg::kLdsPitch);
-        quad_load_row8<2>(win, wb + 2 * Cfg::kLdsPitch);
-        quad_load_row8<3>(win, wb + 3 * Cfg::kLdsPitch);
-        quad_load_row8<4>(win, wb + 4 * Cfg::kLdsPitch);
-        quad_load_row8<5>(win, wb + 5 * Cfg::kLdsPitch);
-        quad_load_row8<6>(win, wb + 6 * Cfg::kLdsPitch);
-    }
+    f32x2 win[Form::kWinPairs];
+    const float* wb = base + (g_first * FS) * Cfg::kLdsPitch;
+    for_each_index<FS - 1>([&](auto SLOT) __attribute__((always_inline)) {
+        constexpr int S = decltype(SLOT)::value;
+        Form::template load_row<S>(win, wb + S * Cfg::kLdsPitch);
+    });
     for (int g = g_first; g < g_first + kGroupsPerWave; ++g) {
         if (j0 + g * FS >= a.nj) break;  // wave-uniform
         const float* gbase = base + (g * FS) * Cfg::kLdsPitch;
-#define JINC_QUAD8_ROW(U)                                                                                          \
-    {                                                                                                              \
-        quad_load_row8<(U + FS - 1) % FS>(win, gbase + (U + FS - 1) * Cfg::kLdsPitch);                              \
-        f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};                                                                 \
-        uint32_t zero;                                                                                              \
-        asm volatile("s_mov_b32 %0, 0" : "=s"(zero)); /* opaque: keeps the coefficient loads inside the row loop */ \
-        quad_pixel8<U, TR8>(acc0, acc1, win, quad + zero);                                                          \
-        const int j = j0 + g * FS + U;                                                                              \
-        if (j < a.nj) {                                                                                             \
-            const uint32_t so = static_cast<uint32_t>(a.iy0 + 2 * j) * io.dst_pitch;                                \
-            store_pair_buf<T>(drsrc, xoff, so, acc0, io.peak);                                                      \
-            store_pair_buf<T>(drsrc, xoff, so + static_cast<uint32_t>(io.dst_pitch), acc1, io.peak);                \
-        }                                                                                                           \
+        for_each_index<FS>([&](auto ROW) __attribute__((always_inline)) {  // the group's FS output row pairs, unrolled: the window's rotation is a compile-time constant
+            constexpr int U = decltype(ROW)::value;
+            Form::template load_row<(U + FS - 1) % FS>(win, gbase + (U + FS - 1) * Cfg::kLdsPitch);
+            f32x2 acc0 = {0.f, 0.f}, acc1 = {0.f, 0.f};
+            uint32_t zero;
+            asm volatile("s_mov_b32 %0, 0" : "=s"(zero));  // opaque: keeps the coefficient loads inside the row loop
+            Form::template pixel<U>(acc0, acc1, win, quad + zero);
+            const int j = j0 + g * FS + U;
+            if (j < a.nj) {
+                const uint32_t so = static_cast<uint32_t>(a.iy0 + 2 * j) * io.dst_pitch;
+                store_pair_buf<T>(drsrc, xoff, so, acc0, io.peak);
+                store_pair_buf<T>(drsrc, xoff, so + static_cast<uint32_t>(io.dst_pitch), acc1, io.peak);
+            }
+        });
     }
-        JINC_QUAD8_ROW(0) JINC_QUAD8_ROW(1) JINC_QUAD8_ROW(2) JINC_QUAD8_ROW(3) JINC_QUAD8_ROW(4) JINC_QUAD8_ROW(5) JINC_QUAD8_ROW(6) JINC_QUAD8_ROW(7)
-#undef JINC_QUAD8_ROW
-    }
+}
+
+template <typename T, int RG>
+__global__ __launch_bounds__(256, 6) void ewa_periodic_quad_kernel(const PeriodicArgs a, const PlaneIO io) {
+    using Cfg = PeriodicCfg<7, RG>;
+    __shared__ float tile[Cfg::kLdsRows * Cfg::kLdsPitch];
+    quad_body<T, RG, QuadForm7>(a, io, tile);
+}
+
+// fs 9 (tap 4 at 2x: C4): the same kernel with a 9 x 9 window (41 register pairs: 5 waves per SIMD, as the window kernel of
+// fs 9) and the coefficient pairs of the two phase rows taken alternately (quad_pixel9).
+template <typename T, int RG>
+__global__ __launch_bounds__(256, 5) void ewa_periodic_quad9_kernel(const PeriodicArgs a, const PlaneIO io) {
+    using Cfg = PeriodicCfg<9, RG>;
+    __shared__ float tile[Cfg::kLdsRows * Cfg::kLdsPitch];
+    quad_body<T, RG, QuadForm9>(a, io, tile);
+}
+
+// The trimmed 8 x 8 support (above): TR8 = the compile-time pattern of its shortened kernel rows.
+template <typename T, int RG, uint32_t TR8>
+__global__ __launch_bounds__(256, 6) void ewa_periodic_quad8_kernel(const PeriodicArgs a, const PlaneIO io) {
+    using Cfg = PeriodicCfg<8, RG>;
+    __shared__ float tile[Cfg::kLdsRows * Cfg::kLdsPitch];
+    quad_body<T, RG, QuadForm8<TR8>>(a, io, tile);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -981,14 +855,16 @@ struct Quad2Cfg {
     static constexpr int kLdsRows = kTileRows + FS - 1;
 };
 
+// The two-periods-per-lane rows (quad2_row6, quad2_row6_inner, quad2_row8) spell their taps with these: the product of a coefficient
+// pair with one sample of a window pair, and the adds of the lane's two periods.  (Undefined after the last use.)
+#define JINC_LO(T, W, C) "v_pk_mul_f32 " T ", " W ", " C " op_sel_hi:[0,1]\n\t"                 /* sample = low half of the pair */
+#define JINC_HI(T, W, C) "v_pk_mul_f32 " T ", " W ", " C " op_sel:[1,0] op_sel_hi:[1,1]\n\t"   /* sample = high half */
+#define JINC_ADD2 "v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %3\n\t"
 // One kernel row of one q for both periods of a lane: window pairs w0..w3 = source columns 0..7 of the row (period A
 // reads columns 0..5, period B columns 1..6), coefficient pairs c0..c5 = (p = 0, p = 1) of taps 0..5.
 __device__ __forceinline__ void quad2_row6(f32x2& acc_a, f32x2& acc_b, f32x2 w0, f32x2 w1, f32x2 w2, f32x2 w3, f32x2 c0, f32x2 c1, f32x2 c2,
                                            f32x2 c3, f32x2 c4, f32x2 c5) {
     f32x2 ta, tb;
-#define JINC_LO(T, W, C) "v_pk_mul_f32 " T ", " W ", " C " op_sel_hi:[0,1]\n\t"                 /* sample = low half of the pair */
-#define JINC_HI(T, W, C) "v_pk_mul_f32 " T ", " W ", " C " op_sel:[1,0] op_sel_hi:[1,1]\n\t"   /* sample = high half */
-#define JINC_ADD2 "v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %3\n\t"
     asm(JINC_LO("%2", "%4", "%8") JINC_HI("%3", "%4", "%8") JINC_ADD2      // tap 0: A column 0, B column 1
         JINC_HI("%2", "%4", "%9") JINC_LO("%3", "%5", "%9") JINC_ADD2      // tap 1: A 1, B 2
         JINC_LO("%2", "%5", "%10") JINC_HI("%3", "%5", "%10") JINC_ADD2    // tap 2: A 2, B 3
@@ -998,9 +874,6 @@ __device__ __forceinline__ void quad2_row6(f32x2& acc_a, f32x2& acc_b, f32x2 w0,
         "v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %3"
         : "+v"(acc_a), "+v"(acc_b), "=&v"(ta), "=&v"(tb)
         : "v"(w0), "v"(w1), "v"(w2), "v"(w3), "s"(c0), "s"(c1), "s"(c2), "s"(c3), "s"(c4), "s"(c5));
-#undef JINC_LO
-#undef JINC_HI
-#undef JINC_ADD2
 }
 
 // Seven taps per kernel row for both periods of a lane (the 6-row x 7-column support: chroma planes sited as MPEG-2 at 2x): period A
@@ -1036,9 +909,6 @@ __device__ __forceinline__ void quad2_row7(f32x2& acc_a, f32x2& acc_b, f32x2 w0,
 // first / last row: host, PeriodicArgs::quad_inner): taps 1 .. 4 only.
 __device__ __forceinline__ void quad2_row6_inner(f32x2& acc_a, f32x2& acc_b, f32x2 w0, f32x2 w1, f32x2 w2, f32x2 c1, f32x2 c2, f32x2 c3, f32x2 c4) {
     f32x2 ta, tb;
-#define JINC_LO(T, W, C) "v_pk_mul_f32 " T ", " W ", " C " op_sel_hi:[0,1]\n\t"
-#define JINC_HI(T, W, C) "v_pk_mul_f32 " T ", " W ", " C " op_sel:[1,0] op_sel_hi:[1,1]\n\t"
-#define JINC_ADD2 "v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %3\n\t"
     asm(JINC_HI("%2", "%4", "%7") JINC_LO("%3", "%5", "%7") JINC_ADD2      // tap 1: A column 1, B column 2
         JINC_LO("%2", "%5", "%8") JINC_HI("%3", "%5", "%8") JINC_ADD2      // tap 2: A 2, B 3
         JINC_HI("%2", "%5", "%9") JINC_LO("%3", "%6", "%9") JINC_ADD2      // tap 3: A 3, B 4
@@ -1046,9 +916,6 @@ __device__ __forceinline__ void quad2_row6_inner(f32x2& acc_a, f32x2& acc_b, f32
         "v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %3"
         : "+v"(acc_a), "+v"(acc_b), "=&v"(ta), "=&v"(tb)
         : "v"(w0), "v"(w1), "v"(w2), "s"(c1), "s"(c2), "s"(c3), "s"(c4));
-#undef JINC_LO
-#undef JINC_HI
-#undef JINC_ADD2
 }
 
 // quad2_row7 on a span of its taps: the chord of a (kernel row, q) of the 6-row x 7-column support -- form 1 = taps 1 .. 6, 2 = taps
@@ -1714,9 +1581,6 @@ struct Quad2x8Cfg {
 __device__ __forceinline__ void quad2_row8(f32x2& acc_a, f32x2& acc_b, f32x2 w0, f32x2 w1, f32x2 w2, f32x2 w3, f32x2 w4, f32x2 c0, f32x2 c1,
                                            f32x2 c2, f32x2 c3, f32x2 c4, f32x2 c5, f32x2 c6, f32x2 c7) {
     f32x2 ta, tb;
-#define JINC_LO(T, W, C) "v_pk_mul_f32 " T ", " W ", " C " op_sel_hi:[0,1]\n\t"
-#define JINC_HI(T, W, C) "v_pk_mul_f32 " T ", " W ", " C " op_sel:[1,0] op_sel_hi:[1,1]\n\t"
-#define JINC_ADD2 "v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %3\n\t"
     asm(JINC_LO("%2", "%4", "%9") JINC_HI("%3", "%4", "%9") JINC_ADD2       // tap 0: A column 0, B column 1
         JINC_HI("%2", "%4", "%10") JINC_LO("%3", "%5", "%10") JINC_ADD2     // tap 1: A 1, B 2
         JINC_LO("%2", "%5", "%11") JINC_HI("%3", "%5", "%11") JINC_ADD2     // tap 2
@@ -1728,10 +1592,10 @@ __device__ __forceinline__ void quad2_row8(f32x2& acc_a, f32x2& acc_b, f32x2 w0,
         "v_pk_add_f32 %0, %0, %2\n\tv_pk_add_f32 %1, %1, %3"
         : "+v"(acc_a), "+v"(acc_b), "=&v"(ta), "=&v"(tb)
         : "v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(w4), "s"(c0), "s"(c1), "s"(c2), "s"(c3), "s"(c4), "s"(c5), "s"(c6), "s"(c7));
+}
 #undef JINC_LO
 #undef JINC_HI
 #undef JINC_ADD2
-}
 
 template <int SLOT>
 __device__ __forceinline__ void quad2x8_load_row(f32x2 (&w)[40], const float* p) {

@@ -849,6 +849,7 @@ QUAD_CASES = [
     ("Y8", 192, 108, 384, 216, dict(tap=4)),
     ("Y16", 700, 200, 1400, 400, dict(tap=4)),
     ("RGBPS", 320, 180, 640, 360, dict(tap=4, blur=0.98)),       # C4's arguments
+    ("Y32", 150, 130, 300, 260, dict(tap=4)),                    # a float plane at tap 4 on three tile columns and five tile rows, the last of each partial
     ("YUV420P10", 256, 144, 512, 288, dict(tap=4, cplace="topleft")),
 ]
 
