@@ -87,7 +87,8 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_batch_device_of_frame", "jinc_batch_process", "jinc_batch_free", "jinc_batch_last_error",
            "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share",
            "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided",
-           "jinc_filter_process_device_shifted", "jinc_filter_process_device_packed10", "jinc_packed10_layout"]
+           "jinc_filter_process_device_shifted", "jinc_filter_process_device_packed10", "jinc_packed10_layout",
+           "jinc_filter_process_device_v210", "jinc_v210_row_bytes"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -122,6 +123,10 @@ def lib():
         L.jinc_filter_process_device_shifted.argtypes = [C.c_void_p] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p]
         L.jinc_filter_process_device_packed10.argtypes = [C.c_void_p] + [C.c_void_p] * 7 + [C.c_uint, C.c_void_p, C.c_int, C.c_void_p]
         L.jinc_packed10_layout.argtypes = [C.c_char_p, C.c_int * 3, C.POINTER(C.c_uint)]
+        L.jinc_filter_process_device_v210.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_int, C.c_void_p]
+        L.jinc_v210_row_bytes.argtypes = [C.c_int]
+        L.jinc_v210_row_bytes.restype = C.c_size_t
         L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
         L.jinc_debug_last_strided.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         L.jinc_filter_sync.argtypes = [C.c_void_p]
@@ -321,6 +326,12 @@ def packed10_layout(name: str) -> Tuple[List[int], int]:
     if rc != 0:
         raise JincError(rc, lib().jinc_last_error().decode())
     return [int(o[i]) for i in range(3)], int(fill.value)
+
+
+def v210_row_bytes(width: int) -> int:
+    """Bytes of the blocks of one v210 row of `width` luma samples, 16 * ceil(width / 6); 0 for width < 1 (jinc_v210_row_bytes; no
+    device needed).  Writers conventionally pad the pitch to a multiple of 128 bytes."""
+    return int(lib().jinc_v210_row_bytes(int(width)))
 
 
 class KernelMode(enum.IntEnum):
@@ -844,6 +855,25 @@ class Filter:
             self._h, arr(_P4, src_ptrs, n), arr(_I4, src_pitches, n), arr(C.c_int * 3, src_offsets, 3), arr(_S4, src_strides, n),
             arr(_P4, dst_ptrs, n), arr(_I4, dst_pitches, n), arr(C.c_int * 3, dst_offsets, 3), C.c_uint(int(dst_fill) & 0xFFFFFFFF),
             arr(_S4, dst_strides, n), int(nframes), C.c_void_p(stream)))
+
+    def process_device_v210(self, src_ptrs, src_pitches, src_is_v210, src_strides, dst_ptrs, dst_pitches, dst_is_v210, dst_strides,
+                            nframes: int, stream: int = 0) -> None:
+        """process_device on v210 frames (jinc_filter_process_device_v210; YUV422P10 filters): a side whose flag is set is ONE buffer
+        of 16-byte blocks of six pixels (element 0 of its pointers, pitches and strides; a row is v210_row_bytes(width) bytes), a side
+        whose flag is clear is dense planes.  Stored blocks have zeros in bits 30 - 31 and in the unused fields of a partial last
+        block.  Frame strides may be None (one frame)."""
+        n = self.fmt.planes
+
+        def arr(kind, values):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(min(n, len(values))):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_v210(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), int(bool(src_is_v210)), arr(_S4, src_strides), arr(_P4, dst_ptrs),
+            arr(_I4, dst_pitches), int(bool(dst_is_v210)), arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
     strided_groups = staticmethod(strided_groups)

@@ -1088,7 +1088,41 @@ void check_packed10_side(const void* base, int pitch, const size_t* fs, int widt
     if (static_cast<size_t>(pitch) < 4 * static_cast<size_t>(width)) throw ArgError("JincResize: pitch of packed 10-bit words is smaller than 4 * width.");
 }
 
+// One side of a v210 call as a launch argument: plane 0 is the luma stand-in, planes 1 and 2 the chroma stand-ins (one size).
+jinc::V210Args v210_args(const Side& s, const void* base, int pitch, const size_t* fs, char* scratch, int first_frame, int slice_frames,
+                         int nframes) {
+    jinc::V210Args a;
+    const size_t frame_stride = (fs && nframes > 1) ? fs[0] : 0;
+    a.blocks = const_cast<char*>(static_cast<const char*>(base)) + static_cast<size_t>(first_frame) * frame_stride;
+    a.block_frame_stride = frame_stride;
+    a.block_pitch = static_cast<uint32_t>(pitch);
+    a.luma_pitch = static_cast<uint32_t>(s.dense_pitch[0]);
+    a.chroma_pitch = static_cast<uint32_t>(s.dense_pitch[1]);
+    a.luma_frame_stride = s.dense_fs[0];
+    a.chroma_frame_stride = s.dense_fs[1];
+    a.width = static_cast<uint32_t>(s.w[0]);
+    a.rows = static_cast<uint32_t>(s.h[0]);
+    a.whole_blocks = a.width / 6;
+    const uintptr_t al = reinterpret_cast<uintptr_t>(base) | static_cast<uintptr_t>(pitch) | static_cast<uintptr_t>(frame_stride);
+    a.unit = al % 16 == 0 ? 16u : 4u;
+    for (int c = 0; c < 3; ++c) a.plane[c] = scratch + s.offset[c] * static_cast<size_t>(slice_frames);
+    return a;
+}
+
+void check_v210_side(const void* base, int pitch, const size_t* fs, const Side& s, int nframes) {
+    if (!base) throw ArgError("JincResize: null plane pointer.");
+    if (s.w[0] != 2 * s.w[1] || s.w[1] != s.w[2] || s.h[0] != s.h[1] || s.h[1] != s.h[2])
+        throw ArgError("JincResize: v210 blocks need an even width and chroma planes of half that width.");
+    if (reinterpret_cast<uintptr_t>(base) % 4) throw ArgError("JincResize: v210 blocks are not aligned to 4 bytes.");
+    if (pitch <= 0 || pitch % 4) throw ArgError("JincResize: pitch of v210 blocks is not a multiple of 4.");
+    if (fs && nframes > 1 && fs[0] % 4) throw ArgError("JincResize: frame stride of v210 blocks is not a multiple of 4.");
+    if (static_cast<size_t>(pitch) < v210_row_bytes(s.w[0]))
+        throw ArgError("JincResize: pitch of v210 blocks is smaller than the row's blocks (16 * ceil(width / 6) bytes).");
+}
+
 }  // namespace
+
+size_t v210_row_bytes(int width) { return width < 1 ? 0 : 16 * ((static_cast<size_t>(width) + 5) / 6); }
 
 int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
                    const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
@@ -1184,6 +1218,49 @@ void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pi
             if (!dst_fields) return 0;
             const jinc::FieldArgs a = field_args(out, dst[0], dst_pitch[0], dst_fs, dst_fields, dst_fill, scratch, k0, slice, nframes);
             hip_check(static_cast<hipError_t>(jinc::launch_pack_fields(a, n, stream)), "pack launch");
+            return 1;
+        });
+}
+
+// ---- jinc_filter_process_device_v210: 10-bit 4:2:2 in 16-byte blocks of six pixels (capture and playout cards, ProRes / DNxHR tools) ----
+// A v210 side is ONE group of the filter's three planes (YUV422P10): unpack_v210_kernel fills their dense stand-ins from the blocks,
+// pack_v210_kernel builds the blocks from the result stand-ins (kernel_interleave.hip, v210_rows.h).  Everything else is
+// run_on_stand_ins, as for the strided, shifted and packed10 calls.  Dense planes per frame: the luma stand-in is `width` samples
+// wide, both chroma stand-ins width / 2 -- 2 planes' worth of 2-byte samples, 4 bytes x the side's pixels (rows padded to 256
+// bytes).  1080p -> 4K: 1920 x 2 = 3840 and 960 x 2 = 1920 bytes are multiples of 256 already (as are 7680 and 3840), so the
+// source side takes (3840 + 2 x 1920) x 1080 = 8 294 400 bytes, the destination side (7680 + 2 x 3840) x 2160 = 33 177 600; both
+// 41 472 000, and the 1 GiB default holds floor(1 073 741 824 / 41 472 000) = 25 frames -- below kSliceFrames, so no rounding: a
+// call of 128 runs as 5 x 25 + 3.  v210 source only: 129 frames, a call of 128 in one slice; v210 destination only: 32 frames.
+void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], bool src_is_v210, const size_t* src_fs,
+                  void* const dst[4], const int dst_pitch[4], bool dst_is_v210, const size_t* dst_fs, int nframes, hipStream_t stream) {
+    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    if (!src_is_v210 && !dst_is_v210) {  // the call IS jinc_filter_process_device
+        enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
+        return;
+    }
+    Side in, out;
+    for (int i = 0; i < f.planecount; ++i) {
+        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
+        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
+        in.group_of[i] = in.channel_of[i] = src_is_v210 ? 0 : -1;
+        out.group_of[i] = out.channel_of[i] = dst_is_v210 ? 0 : -1;
+    }
+    in.ngroups = src_is_v210 ? 1 : 0;
+    out.ngroups = dst_is_v210 ? 1 : 0;
+    if (src_is_v210) check_v210_side(src[0], src_pitch[0], src_fs, in, nframes);
+    if (dst_is_v210) check_v210_side(dst[0], dst_pitch[0], dst_fs, out, nframes);
+    run_on_stand_ins(
+        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
+        [&](char* scratch, int k0, int slice, int n) {
+            if (!src_is_v210) return 0;
+            const jinc::V210Args a = v210_args(in, src[0], src_pitch[0], src_fs, scratch, k0, slice, nframes);
+            hip_check(static_cast<hipError_t>(jinc::launch_unpack_v210(a, n, stream)), "v210 unpack launch");
+            return 1;
+        },
+        [&](char* scratch, int k0, int slice, int n) {
+            if (!dst_is_v210) return 0;
+            const jinc::V210Args a = v210_args(out, dst[0], dst_pitch[0], dst_fs, scratch, k0, slice, nframes);
+            hip_check(static_cast<hipError_t>(jinc::launch_pack_v210(a, n, stream)), "v210 pack launch");
             return 1;
         });
 }

@@ -297,6 +297,31 @@ int jinc_filter_process_device_packed10(jinc_filter* f, const void* const src[4]
     });
 }
 
+int jinc_filter_process_device_v210(jinc_filter* f, const void* const src[4], const int src_pitch[4], int src_is_v210,
+                                    const size_t src_frame_stride[4], void* const dst[4], const int dst_pitch[4], int dst_is_v210,
+                                    const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    // the filter first (it needs no device), then the checks of jinc_filter_process_device_shifted in its order
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (src_is_v210 || dst_is_v210) {
+        if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0 || f->half || f->vi_in.component_size != 2 ||
+            f->vi_in.bits_per_component != 10)
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: v210 blocks need a filter with three 10-bit components in 16-bit samples and 4:2:2 "
+                                              "sub-sampling (YUV422P10).");
+    }
+    if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_v210(*f, src, src_pitch, src_is_v210 != 0, src_frame_stride, dst, dst_pitch, dst_is_v210 != 0, dst_frame_stride, nframes,
+                     static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+size_t jinc_v210_row_bytes(int width) { return v210_row_bytes(width); }
+
 int jinc_packed10_layout(const char* name, int field_offset[3], unsigned* opaque_fill) {
     // offsets of the library's planes (Y, U, V or G, B, R) in the word
     static const struct {

@@ -1,7 +1,7 @@
 // filter_internal.h -- types and internal interfaces shared by the host translation units of libjincresize_hip.so:
 //   filter_args.cpp   Create_JincResize's argument handling and geometry derivation (configure)
 //   device_plan.cpp   device-resident plans: upload, launch planning for every kernel family (init_device)
-//   dispatch.cpp      per-call kernel selection and launches (enqueue; enqueue_strided: planes with a sample step; enqueue_packed10: 10:10:10:2 words)
+//   dispatch.cpp      per-call kernel selection and launches (enqueue; enqueue_strided: planes with a sample step; enqueue_packed10: 10:10:10:2 words; enqueue_v210: v210 blocks)
 //   pipeline.cpp      frames in flight: device staging slots, pinned host ranges, H2D -> kernels -> D2H
 //   filter.cpp        the C ABI of include/jincresize_hip.h
 // Nothing here crosses the C ABI.
@@ -256,7 +256,7 @@ struct jinc_filter {
     static constexpr int kForkEvents = 16;
     hipEvent_t ev_fork[kForkEvents] = {}, ev_join[kForkEvents] = {};
     unsigned fork_turn = 0;
-    // jinc_filter_process_device_strided / _shifted / _packed10 (dispatch.cpp run_on_stand_ins): the dense planes strided, shifted or packed ones are split into / merged from -- one allocation,
+    // jinc_filter_process_device_strided / _shifted / _packed10 / _v210 (dispatch.cpp run_on_stand_ins): the dense planes strided, shifted or packed ones are split into / merged from -- one allocation,
     // made on first use, grown when a call needs more -- and, because successive calls share them, an event behind each call's last
     // merge (a ring, as above) for the next call to wait on when it comes on another stream.
     void* strided_scratch = nullptr;
@@ -330,6 +330,12 @@ void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pit
 void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_fields, const size_t* src_fs,
                       void* const dst[4], const int dst_pitch[4], const int* dst_fields, unsigned dst_fill, const size_t* dst_fs,
                       int nframes, hipStream_t stream);
+// ... enqueue for sides that are ONE buffer of v210 blocks (10-bit 4:2:2, six pixels in 16 bytes; the filter has been checked by
+// filter.cpp: YUV422P10).  A side whose flag is false is dense planes; both false: enqueue itself.  Of a v210 side only base[0],
+// pitch[0] and frame stride [0] are read.
+void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], bool src_is_v210, const size_t* src_fs,
+                  void* const dst[4], const int dst_pitch[4], bool dst_is_v210, const size_t* dst_fs, int nframes, hipStream_t stream);
+size_t v210_row_bytes(int width);  // 16 * ceil(width / 6); 0 for width < 1
 // ... the channel groups of one side's planes (pure: test header jinc_debug_strided_groups); returns their number
 int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
                    const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]);
@@ -337,7 +343,7 @@ struct StridedReport {  // test header: jinc_debug_last_strided
     int split_launches = 0, merge_launches = 0, slices = 0;
     long long scratch_bytes = 0;
 };
-const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided / enqueue_packed10
+const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided / enqueue_packed10 / enqueue_v210
 int last_call_frames_in_process();
 const char* last_interior_instance_in_process();
 // pipeline.cpp: frames in flight on one instance

@@ -26,9 +26,23 @@
 // accesses on the word side (consecutive lanes at consecutive 32-byte pieces, 2 KiB per wave in one piece; eight dwords where base,
 // pitch or frame stride is a multiple of 4 only) and one 16-byte access per dense plane.  The offsets and the fill are kernel
 // arguments: wave-uniform, in scalar registers.  The rest of a row moves word by word.
+//
+// V210 forms (jinc_filter_process_device_v210): 10-bit 4:2:2 in 16-byte blocks of six pixels, twelve fields in four words in an
+// order that repeats only every 128 bits.  unpack_v210_kernel fills the three dense planes of YUV422P10 from the blocks,
+// pack_v210_kernel builds the blocks in registers (bits 30 - 31 and the unused fields of a partial block are zeros by construction)
+// and stores them whole; it never reads the destination.  Same shape: grid = row blocks x frames, a wave owns a row.  A lane owns
+// ONE block per trip, so a wave's trip is 64 consecutive blocks: 1 KiB in one piece on the block side (one 16-byte access per
+// lane; four dwords where base, pitch or frame stride is a multiple of 4 only) and 768 bytes in one piece on the luma plane (one
+// 12-byte access per lane, 4-byte aligned).  Chroma: a block holds 3 samples of each plane, 6 bytes -- no aligned access -- so
+// lanes l and l ^ 1 swap three samples through one cross-lane move of two dwords (DPP, no LDS) and then the even lane moves the
+// pair's 6 Cb samples and the odd lane its 6 Cr samples, 12 bytes each.  Every block byte is read once or written once; block and
+// sample indices come from the lane number by additions, shifts and multiplications by constants.  What the pairs leave over
+// (the odd whole block, the partial last block) moves sample by sample under a width guard.  The row functions are v210_rows.h:
+// plain inline functions that a host program runs lane by lane against exactly sized buffers.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "v210_rows.h"
 
 namespace jinc {
 namespace {
@@ -317,7 +331,58 @@ int launch_fields(const FieldArgs& a, int nframes, void* stream) {
     return hipGetLastError();
 }
 
+// ---- v210 blocks (kernels.h V210Args; the row functions: v210_rows.h) ----
+// The value lane l ^ 1 holds (quad_perm [1, 0, 3, 2]).  Both lanes of a pair are active wherever this is called: pairs of blocks
+// start at even blocks and the walk starts at block `lane`.
+__device__ __forceinline__ v210::Three from_partner(const v210::Three& t) {
+    v210::Three r;
+    r.lo = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(t.lo), 0xB1, 0xF, 0xF, false));
+    r.hi = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(t.hi), 0xB1, 0xF, 0xF, false));
+    return r;
+}
+
+// Row blockIdx.x * 4 + wave of frame blockIdx.y (the wave's number through a scalar register: the row's addresses are wave-uniform).
+__global__ __launch_bounds__(256) void unpack_v210_kernel(const V210Args a) {
+    const uint32_t row = blockIdx.x * 4 + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+    if (row >= a.rows) return;
+    const uint32_t lane = threadIdx.x & 63u, paired = v210::paired_blocks(a), blocks = v210::row_blocks(a);
+    const v210::RowOf r = v210::row_of(a, blockIdx.y, row);
+    for (uint32_t b = lane; b < paired; b += 64) {
+        v210::LaneState s;
+        v210::unpack_pair_begin(a, r, b, s);
+        v210::unpack_pair_end(a, r, b, s, from_partner(s.send));
+    }
+    for (uint32_t b = paired + lane; b < blocks; b += 64) v210::unpack_tail(a, r, b);
+}
+__global__ __launch_bounds__(256) void pack_v210_kernel(const V210Args a) {
+    const uint32_t row = blockIdx.x * 4 + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+    if (row >= a.rows) return;
+    const uint32_t lane = threadIdx.x & 63u, paired = v210::paired_blocks(a), blocks = v210::row_blocks(a);
+    const v210::RowOf r = v210::row_of(a, blockIdx.y, row);
+    for (uint32_t b = lane; b < paired; b += 64) {
+        v210::LaneState s;
+        uint32_t y[3];
+        v210::pack_pair_begin(a, r, b, y, s);
+        v210::pack_pair_end(a, r, b, y, s, from_partner(s.send));
+    }
+    for (uint32_t b = paired + lane; b < blocks; b += 64) v210::pack_tail(a, r, b);
+}
+
+template <bool Pack>
+int launch_v210(const V210Args& a, int nframes, void* stream) {
+    if (nframes <= 0 || a.rows == 0 || a.width == 0) return hipSuccess;
+    if ((a.unit != 16 && a.unit != 4) || a.whole_blocks != a.width / 6 || (a.width & 1u)) return hipErrorInvalidValue;
+    const dim3 grid((a.rows + 3) / 4, static_cast<uint32_t>(nframes));
+    if constexpr (Pack) hipLaunchKernelGGL(pack_v210_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL(unpack_v210_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+int launch_unpack_v210(const V210Args& a, int nframes, void* stream) { return launch_v210<false>(a, nframes, stream); }
+
+int launch_pack_v210(const V210Args& a, int nframes, void* stream) { return launch_v210<true>(a, nframes, stream); }
 
 int launch_unpack_fields(const FieldArgs& a, int nframes, void* stream) { return launch_fields<false>(a, nframes, stream); }
 

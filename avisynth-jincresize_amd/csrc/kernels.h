@@ -545,6 +545,25 @@ struct FieldArgs {
 int launch_unpack_fields(const FieldArgs& a, int nframes, void* stream);
 int launch_pack_fields(const FieldArgs& a, int nframes, void* stream);
 
+// v210 blocks <-> the three dense 16-bit planes of a 10-bit 4:2:2 frame (kernel_interleave.hip, v210_rows.h;
+// jinc_filter_process_device_v210).  Block b of row y of frame n lies at blocks + n * block_frame_stride + y * block_pitch + 16 * b
+// and holds luma samples 6b .. 6b+5 and chroma samples 3b .. 3b+2 of both chroma planes (the field table: v210_rows.h).  plane[0]
+// is the luma plane, `width` samples wide, sample x at plane[0] + n * luma_frame_stride + y * luma_pitch + 2 * x; plane[1] = Cb
+// and plane[2] = Cr are width / 2 wide and share chroma_pitch and chroma_frame_stride.  The planes are the filter's own (bases,
+// pitches and frame strides multiples of 256 bytes).  Base, pitch and frame stride of the blocks are multiples of 4 (dispatch.cpp
+// refuses others); unit: 16 where they are multiples of 16 as well (one 16-byte access per block), else 4 (four dwords).
+// whole_blocks: width / 6, the blocks of a row whose six pixels all lie inside it; a row has one more, partial, block when
+// width is no multiple of 6.
+struct V210Args {
+    char* blocks = nullptr;
+    char* plane[3] = {nullptr, nullptr, nullptr};
+    size_t block_frame_stride = 0, luma_frame_stride = 0, chroma_frame_stride = 0;
+    uint32_t block_pitch = 0, luma_pitch = 0, chroma_pitch = 0, width = 0, rows = 0, whole_blocks = 0, unit = 4;
+};
+// One launch over every row and frame of `a`.
+int launch_unpack_v210(const V210Args& a, int nframes, void* stream);
+int launch_pack_v210(const V210Args& a, int nframes, void* stream);
+
 // Measurement hook (kernel_probe.hip): `samplers` single-lane workgroups stamp the shader clock counter and the 100 MHz
 // real-time counter until *stop_flag (device memory) becomes non-zero or max_seconds pass; out[2 k] = shader ticks,
 // out[2 k + 1] = real-time ticks of sampler k.

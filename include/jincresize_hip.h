@@ -325,6 +325,44 @@ JINC_API int jinc_filter_process_device_packed10(jinc_filter *f, const void *con
                                                  unsigned dst_fill, const size_t dst_frame_stride[4], int nframes,
                                                  void *hip_stream);
 
+/* jinc_filter_process_device on v210 frames: 10-bit 4:2:2 in 128-bit groups of six pixels, as SDI capture and playout cards
+ * (AJA, Blackmagic, Bluefish) DMA it and as ProRes / DNxHR tool chains exchange it.  Neither a sample step, a shift nor one word
+ * per pixel describes it: six pixels share four words in a pattern that repeats only every 128 bits.
+ *   A row is a run of 16-byte blocks of four little-endian 32-bit words.  Block b holds luma samples 6b .. 6b+5 and samples
+ *   3b .. 3b+2 of each chroma plane, three 10-bit fields per word at bits 0, 10 and 20 (bits 30 - 31 are unused):
+ *       word 0: Cb[3b]   Y[6b]     Cr[3b]            word 2: Cr[3b+1] Y[6b+3]   Cb[3b+2]
+ *       word 1: Y[6b+1]  Cb[3b+1]  Y[6b+2]           word 3: Y[6b+4]  Cr[3b+2]  Y[6b+5]
+ *   A row of `width` luma samples occupies jinc_v210_row_bytes(width) = 16 * ceil(width / 6) bytes; the last block is partial
+ *   (2 luma + 1 Cb + 1 Cr, or 4 luma + 2 Cb + 2 Cr) when width is no multiple of 6.  Writers conventionally pad rows to 128
+ *   bytes (48 pixels): that padding is part of the pitch, not of the row's blocks.
+ *   A side whose flag is 0 is dense planes, exactly as in jinc_filter_process_device; with both flags 0 the call IS that call
+ *   (the same launches, on any filter).  A side whose flag is set is ONE buffer of blocks: only element [0] of its base, pitch
+ *   and frame stride arrays is read; block b of row y of frame n lies at base[0] + n * frame_stride[0] + y * pitch[0] + 16 * b.
+ *   Source and destination are independent: v210 in and planar YUV422P10 out, the reverse, or v210 on both sides.
+ *   The call computes exactly what jinc_filter_process_device computes for dense low-aligned 10-bit planes Y, U = Cb, V = Cr of
+ *   the field values.  Source bits 30 - 31, the fields of a partial last block beyond `width` and everything behind the row's
+ *   blocks are ignored whatever they hold.  Each destination row gets exactly its jinc_v210_row_bytes(width) bytes stored,
+ *   every block whole: bits 30 - 31 of every word and the unused fields of a partial last block are zeros.  No byte outside
+ *   those blocks is stored to -- row padding (the 128-byte convention included) and the gaps between frames stay as they are.
+ *   The destination is never read.
+ * Accepted only on a filter with three components, sub_w 1 and sub_h 0, component_size 2 and bits_per_component 10, not
+ * binary16 (YUV422P10).  Any other filter with a flag set is JINC_ERR_INVALID_ARG, before the null checks of the plane arrays
+ * and before the device check; then null arguments, nframes and frame strides as for jinc_filter_process_device_shifted.  A
+ * v210 base, pitch or frame stride that is no multiple of 4 and a pitch below jinc_v210_row_bytes(width) are
+ * JINC_ERR_INVALID_ARG, each with a message of its own and with nothing written.  Base, pitch and frame stride that are all
+ * multiples of 16 get 16-byte accesses on the block side, others dwords.
+ * A v210 side takes dense stand-ins of the filter's own for its three planes (the scratch of the strided call, same knob
+ * strided_scratch_bytes, same ordering between calls, so these calls may alternate with strided, shifted and packed10 ones on
+ * one filter): 4 bytes per pixel of that side, rows padded to 256 bytes.  1080p -> 4K with both sides v210 is
+ * 4 x (1920 x 1080 + 3840 x 2160) = 41 472 000 bytes per frame, so the 1 GiB default runs a long call in slices of 25 frames
+ * (128 frames: 5 x 25 + 3); with only the source v210 129 frames fit (128 in one slice), with only the destination 32. */
+JINC_API int jinc_filter_process_device_v210(jinc_filter *f, const void *const src[4], const int src_pitch[4], int src_is_v210,
+                                             const size_t src_frame_stride[4], void *const dst[4], const int dst_pitch[4],
+                                             int dst_is_v210, const size_t dst_frame_stride[4], int nframes, void *hip_stream);
+
+/* Bytes of the blocks of one v210 row of `width` luma samples: 16 * ceil(width / 6); 0 for width < 1.  Needs no device. */
+JINC_API size_t jinc_v210_row_bytes(int width);
+
 /* The field offsets of a named 10:10:10:2 word in the library's plane order, and the fill that sets every spare bit (an opaque
  * pixel); opaque_fill may be NULL.  Needs no device.  Names match without regard to case; an unknown one is
  * JINC_ERR_INVALID_ARG.
