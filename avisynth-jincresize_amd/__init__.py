@@ -27,7 +27,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JINC_LIB") or os.path.join(_HERE, "lib", "libjincresize_hip.so")  # JINC_LIB: A/B runs against another build
 SIMD_ORDER_ISA_PATH = os.path.join(_HERE, "lib", "kernel_simdorder-gfx950.s")  # the one unit with (explicit) fused multiply-adds
-ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_interleave", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
+ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_interleave", "kernel_widen", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
                        "kernel_quasi_exact_fs9", "kernel_quasi_lane_fs7", "kernel_quasi_lane_fs9")]
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip.h")
 TEST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip_test.h")  # introspection, knobs, hooks
@@ -88,7 +88,7 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share",
            "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided",
            "jinc_filter_process_device_shifted", "jinc_filter_process_device_packed10", "jinc_packed10_layout",
-           "jinc_filter_process_device_v210", "jinc_v210_row_bytes"]
+           "jinc_filter_process_device_v210", "jinc_v210_row_bytes", "jinc_filter_process_device_widened"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -125,6 +125,7 @@ def lib():
         L.jinc_packed10_layout.argtypes = [C.c_char_p, C.c_int * 3, C.POINTER(C.c_uint)]
         L.jinc_filter_process_device_v210.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_widened.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
         L.jinc_v210_row_bytes.argtypes = [C.c_int]
         L.jinc_v210_row_bytes.restype = C.c_size_t
         L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
@@ -874,6 +875,28 @@ class Filter:
         self._check(lib().jinc_filter_process_device_v210(
             self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), int(bool(src_is_v210)), arr(_S4, src_strides), arr(_P4, dst_ptrs),
             arr(_I4, dst_pitches), int(bool(dst_is_v210)), arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
+
+    def process_device_widened(self, src_ptrs, src_pitches, src_steps, src_shifts, src_bits: int, src_strides, dst_ptrs, dst_pitches,
+                               dst_steps, dst_strides, nframes: int, stream: int = 0) -> None:
+        """INTEGER device samples into this fp32 / binary16 filter (jinc_filter_process_device_widened): the source is addressed as in
+        process_device_shifted, its sample size comes from src_bits (8: bytes; 9 .. 16: 16-bit words) and a sample's value is
+        (raw >> shift[i]) & ((1 << src_bits) - 1); the destination side is process_device_strided's on this filter.  The result is
+        process_device's on dense planes of those values as float / half.  NV12 into YUV420PS: Y step 1, U = uv, V = uv + 1
+        sample, both step 2, src_bits 8; P010 into YUV420PH / PS: the same with src_bits 10, shifts 6.  Half filters take
+        src_bits <= 11.  Steps, shifts and frame strides may be None."""
+        n = self.fmt.planes
+
+        def arr(kind, values):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(n):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_widened(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_I4, src_shifts), int(src_bits),
+            arr(_S4, src_strides), arr(_P4, dst_ptrs), arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_S4, dst_strides), int(nframes),
+            C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
     strided_groups = staticmethod(strided_groups)

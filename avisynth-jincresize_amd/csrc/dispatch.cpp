@@ -1265,5 +1265,104 @@ void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[
         });
 }
 
+// ---- jinc_filter_process_device_widened: integer device frames into an fp32 / binary16 filter (NV12, P010, Y210, BGRA8, planar) ----
+// The split that joins a decoder's surface to the float filters: EVERY source plane, dense ones included, takes a dense stand-in of
+// the filter's sample type, filled by widen_samples_kernel (kernel_widen.hip) with float((raw >> shift) & mask) -- exact.  From
+// there the call is enqueue on float planes, so the result is jinc_filter_process_device's on planes of those values by
+// construction: same plan, same kernels, same finite scan (which finds nothing).  The destination side is enqueue_strided's:
+// planes with step 1 are written where they lie, the others merged from result stand-ins.  Everything else is run_on_stand_ins.
+// Dense planes per frame, 1080p -> 4K into planar planes: fp32 rows of 1920 x 4 = 7680 and 960 x 4 = 3840 bytes are multiples of
+// 256 already, so NV12 / P010 take 7680 x 1080 + 2 x 3840 x 540 = 12 441 600 bytes and the 1 GiB default holds
+// floor(1 073 741 824 / 12 441 600) = 86 frames -- below kSliceFrames, so no rounding: a call of 128 runs as 86 + 42.  binary16:
+// 3840 x 1080 + 2 x 1920 x 540 = 6 220 800 bytes, 172 frames, rounded down to 128: a call of 128 in one slice.
+namespace {
+// The groups of a widened source as launch arguments, one WidenArgs per step (fill_args for source samples of their own size).
+void fill_widen_args(const jinc_filter& f, const Side& s, const void* const base[4], const int pitch[4], const int* step, const int* shift,
+                     const size_t* fs, size_t src_bytes, uint32_t mask, char* scratch, int first_frame, int slice_frames, int nframes,
+                     WidenArgs by_step[5]) {
+    for (int g = 0; g < s.ngroups; ++g) {
+        WidenGroup e;
+        int members = 0, first = -1;
+        uintptr_t lo = 0;
+        for (int i = 0; i < f.planecount; ++i) {
+            if (s.group_of[i] != g) continue;
+            if (first < 0) first = i;
+            const uintptr_t b = reinterpret_cast<uintptr_t>(base[i]);
+            lo = members ? std::min(lo, b) : b;
+            ++members;
+            e.plane[s.channel_of[i]] = scratch + s.offset[i] * static_cast<size_t>(slice_frames);
+            e.shift[s.channel_of[i]] = static_cast<uint8_t>(shift_of(shift, i));
+        }
+        const int n = step_of(step, first);
+        const size_t frame_stride = (fs && nframes > 1) ? fs[first] : 0;
+        e.packed = reinterpret_cast<const char*>(lo) + static_cast<size_t>(first_frame) * frame_stride;
+        e.packed_frame_stride = frame_stride;
+        e.plane_frame_stride = s.dense_fs[first];
+        e.packed_pitch = static_cast<uint32_t>(pitch[first]);
+        e.plane_pitch = static_cast<uint32_t>(s.dense_pitch[first]);
+        e.width = static_cast<uint32_t>(s.w[first]);
+        e.rows = static_cast<uint32_t>(s.h[first]);
+        const uintptr_t a = lo | static_cast<uintptr_t>(pitch[first]) | static_cast<uintptr_t>(frame_stride);
+        e.unit = a % 16 == 0 ? 16u : a % 4 == 0 ? 4u : 0u;
+        const uint32_t lane_pixels = static_cast<uint32_t>(16 / src_bytes);
+        // (a group with a channel missing leaves the row's last pixel to the tail: its missing samples may lie behind the caller's buffer)
+        const uint32_t vec_from = members == n ? e.width : e.width - 1;
+        e.vec_pixels = e.unit ? vec_from / lane_pixels * lane_pixels : 0u;
+        WidenArgs& a_n = by_step[n];
+        a_n.mask = mask;
+        a_n.g[a_n.ngroups++] = e;
+    }
+}
+}  // namespace
+
+void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
+                     int src_bits, const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step,
+                     const size_t* dst_fs, int nframes, hipStream_t stream) {
+    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    const size_t sb = static_cast<size_t>(f.vi_in.component_size), src_bytes = src_bits > 8 ? 2 : 1;
+    Side in, out;
+    for (int i = 0; i < f.planecount; ++i) {
+        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
+        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
+    }
+    // Every source plane is a member of a group (groups_of_side gives a plane of step 1 a group of its own when it has a shift: here
+    // every plane counts as having one); planes of one pixel share a group by the strided call's rule, in source samples.
+    static const int kEveryPlane[4] = {1, 1, 1, 1};
+    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
+    in.ngroups = groups_of_side(src, src_pitch, src_step, kEveryPlane, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(src_bytes), f.planecount, in.group_of, in.channel_of);
+    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, nullptr, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(sb), f.planecount, out.group_of, out.channel_of);
+    for (int i = 0; i < f.planecount; ++i) {  // (base alignment and the row's size: filter.cpp, in front of the device check)
+        if (!src[i]) throw ArgError("JincResize: null plane pointer.");
+        if (src_pitch[i] <= 0 || src_pitch[i] % src_bytes) throw ArgError("JincResize: source pitch is not a multiple of the source sample size.");
+        if (src_fs && nframes > 1 && src_fs[i] % src_bytes) throw ArgError("JincResize: source frame stride is not a multiple of the source sample size.");
+    }
+    check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
+    const uint32_t mask = (1u << src_bits) - 1u;
+    run_on_stand_ins(
+        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
+        [&](char* scratch, int k0, int slice, int n) {
+            WidenArgs widen[5];
+            fill_widen_args(f, in, src, src_pitch, src_step, src_shift, src_fs, src_bytes, mask, scratch, k0, slice, nframes, widen);
+            int launches = 0;
+            for (int step = 1; step <= 4; ++step)
+                if (widen[step].ngroups) {
+                    hip_check(static_cast<hipError_t>(jinc::launch_widen_samples(widen[step], static_cast<int>(src_bytes), step, static_cast<int>(sb), n, stream)), "widen launch");
+                    ++launches;
+                }
+            return launches;
+        },
+        [&](char* scratch, int k0, int slice, int n) {
+            InterleaveArgs merge[5];
+            fill_args(f, out, dst_c, dst_pitch, dst_step, nullptr, dst_fs, scratch, k0, slice, nframes, true, merge);
+            int launches = 0;
+            for (int step = 1; step <= 4; ++step)
+                if (merge[step].ngroups) {
+                    hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], static_cast<int>(sb), step, n, stream)), "merge launch");
+                    ++launches;
+                }
+            return launches;
+        });
+}
+
 }  // namespace host
 }  // namespace jinc

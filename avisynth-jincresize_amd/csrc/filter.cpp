@@ -322,6 +322,56 @@ int jinc_filter_process_device_v210(jinc_filter* f, const void* const src[4], co
 
 size_t jinc_v210_row_bytes(int width) { return v210_row_bytes(width); }
 
+int jinc_filter_process_device_widened(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                                       const int src_sample_shift[4], int src_bits, const size_t src_frame_stride[4], void* const dst[4],
+                                       const int dst_pitch[4], const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
+                                       void* hip_stream) {
+    // the filter, src_bits, the steps, the shifts and the source's bases and pitches first (they need no device), then the checks
+    // of jinc_filter_process_device_shifted in its order
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (!f->float_samples())
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: widened integer sources need an fp32 or binary16 filter; this filter has " +
+                                              std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_shifted).");
+    if (src_bits < 8 || src_bits > 16)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: src_bits must be in 8..16 (got " + std::to_string(src_bits) + ").");
+    if (f->half && src_bits > 11)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: " + std::to_string(src_bits) + "-bit samples are not exact in binary16 (at most 11 bits): "
+                                              "widen them into an fp32 filter.");
+    for (const int* step : {src_sample_step, dst_sample_step})
+        for (int i = 0; step && i < f->planecount; ++i)
+            if (step[i] < 1 || step[i] > 4)
+                return fail(JINC_ERR_INVALID_ARG, std::string("JincResize: ") + (step == src_sample_step ? "source" : "destination") +
+                                                      " sample step must be in 1..4 (got " + std::to_string(step[i]) + ").");
+    const int src_bytes = src_bits > 8 ? 2 : 1, spare = 8 * src_bytes - src_bits;
+    for (int i = 0; src_sample_shift && i < f->planecount; ++i) {
+        if (src_sample_shift[i] < 0) return fail(JINC_ERR_INVALID_ARG, "JincResize: sample shift must not be negative.");
+        if (src_sample_shift[i] > spare)
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: sample shift " + std::to_string(src_sample_shift[i]) + " is larger than the padding of a " +
+                                                  std::to_string(src_bits) + "-bit sample in its container (" + std::to_string(spare) + " bits).");
+    }
+    for (int i = 0; src && src_pitch && i < f->planecount; ++i) {
+        int w = 0, h = 0;
+        f->plane_dims(f->vi_in, i, w, h);
+        if (reinterpret_cast<uintptr_t>(src[i]) % static_cast<uintptr_t>(src_bytes))
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: source plane pointer is not aligned to the source sample size.");
+        const size_t step = static_cast<size_t>(src_sample_step ? src_sample_step[i] : 1);
+        const size_t need = (static_cast<size_t>(w - 1) * step + 1) * static_cast<size_t>(src_bytes);
+        if (src_pitch[i] < 0 || static_cast<size_t>(src_pitch[i]) < need)
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: source pitch " + std::to_string(src_pitch[i]) + " is smaller than the row of " +
+                                                  std::to_string(need) + " bytes at this sample step and size.");
+    }
+    if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_widened(*f, src, src_pitch, src_sample_step, src_sample_shift, src_bits, src_frame_stride, dst, dst_pitch, dst_sample_step,
+                        dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
 int jinc_packed10_layout(const char* name, int field_offset[3], unsigned* opaque_fill) {
     // offsets of the library's planes (Y, U, V or G, B, R) in the word
     static const struct {

@@ -564,6 +564,31 @@ struct V210Args {
 int launch_unpack_v210(const V210Args& a, int nframes, void* stream);
 int launch_pack_v210(const V210Args& a, int nframes, void* stream);
 
+// Integer samples -> the dense planes of an fp32 / binary16 filter (kernel_widen.hip, widen_rows.h;
+// jinc_filter_process_device_widened).  A channel group as in InterleaveGroup, read only: `step` source samples of src_bytes (1: a
+// byte; 2: a little-endian 16-bit word) per pixel at packed, channel c of pixel x of row y of frame n at packed +
+// n * packed_frame_stride + y * packed_pitch + (x * step + c) * src_bytes.  The dense plane of channel c (plane[c]; nullptr: not
+// given, neither read nor written) holds float / binary16 ((raw >> shift[c]) & mask) at plane[c] + n * plane_frame_stride +
+// y * plane_pitch + x * out_bytes.  A group may have step 1: every source plane of such a call takes a stand-in.  The dense planes
+// are the filter's own: bases, pitch and frame stride multiples of 256 bytes.
+// unit / vec_pixels as in InterleaveGroup, with 16 / src_bytes pixels per lane: a group with a channel missing stops its vectors in
+// front of the row's last pixel.
+struct WidenGroup {
+    const char* packed = nullptr;
+    char* plane[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t packed_frame_stride = 0, plane_frame_stride = 0;
+    uint32_t packed_pitch = 0, plane_pitch = 0, width = 0, rows = 0, vec_pixels = 0, unit = 0;
+    uint8_t shift[4] = {0, 0, 0, 0};
+};
+struct WidenArgs {
+    WidenGroup g[4];
+    int ngroups = 0;
+    uint32_t mask = 0xffu;  // (1 << src_bits) - 1
+};
+// One launch over every group and frame of `a`: src_bytes 1 or 2 (a byte takes no shift: mask 0xff, shifts 0); step 1 .. 4 (the
+// same for all groups of a launch); out_bytes 4 (fp32) or 2 (binary16: every value must be <= 2047 to be exact).
+int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int nframes, void* stream);
+
 // Measurement hook (kernel_probe.hip): `samplers` single-lane workgroups stamp the shader clock counter and the 100 MHz
 // real-time counter until *stop_flag (device memory) becomes non-zero or max_seconds pass; out[2 k] = shader ticks,
 // out[2 k + 1] = real-time ticks of sampler k.

@@ -1,0 +1,132 @@
+// widen_rows.h -- one lane's share of one row of the widening pass (kernel_widen.hip widen_samples_kernel; kernels.h WidenGroup),
+// as plain inline functions for host and device: a stand-alone host program runs exactly this code lane by lane against exactly
+// sized buffers (tests/host_sanitizer/widen_rows_main.cpp).
+//
+// Integer samples of SB bytes (1: a byte; 2: a little-endian 16-bit word), N per pixel, become fp32 (OB = 4) or binary16 (OB = 2)
+// samples of up to N dense planes: plane c holds float((raw >> shift[c]) & mask) of channel c.  The conversion is exact: every
+// integer below 2^24 is an fp32 value, every integer up to 2047 a binary16 value (dispatch refuses wider samples into half planes).
+//
+// A lane owns 16 / SB whole pixels per step, as in split_samples_kernel: N 16-byte accesses on the source side (consecutive lanes,
+// consecutive addresses; 4 N dwords where base, pitch or frame stride is a multiple of 4 only) and, per given plane, OB / SB whole
+// 16-byte vectors of converted samples that lie side by side -- a wave's trip stores one piece of 64 x 16 x OB / SB bytes to each
+// plane.  The samples are picked out of the loaded dwords with shifts whose amounts are compile-time constants; shift[c] and the
+// mask are the same in every lane.  Bytes take neither: src_bits 8 fills the byte, so a byte is its value.
+// What is left moves sample by sample under a width guard: a row's tail, groups whose base, pitch or frame stride is no multiple of
+// 4 bytes (vec_pixels 0), and the last pixel of a group with a channel missing, whose missing samples may lie behind the end of the
+// caller's buffer.  Nothing beyond `width` samples is read from a given channel or stored to a plane; the source is never written.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+#include "kernels.h"
+
+#if defined(__HIPCC__)
+#define JINC_WIDEN_HD __host__ __device__ __forceinline__
+#else
+#define JINC_WIDEN_HD inline
+#endif
+
+namespace jinc {
+namespace widen {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // 16 bytes as ONE access
+
+// 16 N bytes of whole pixels: N 16-byte accesses where the group allows them, else 4 N dwords.
+template <int N>
+JINC_WIDEN_HD void load_pixels(const char* p, uint32_t unit, uint32_t* w) {
+    if (unit == 16) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const u32x4 v = *reinterpret_cast<const u32x4*>(p + 16 * k);
+            w[4 * k] = v.x, w[4 * k + 1] = v.y, w[4 * k + 2] = v.z, w[4 * k + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4 * N; ++k) w[k] = *reinterpret_cast<const uint32_t*>(p + 4 * k);
+    }
+}
+JINC_WIDEN_HD void store16(char* p, const uint32_t* w) {
+    u32x4 v;
+    v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
+    *reinterpret_cast<u32x4*>(p) = v;
+}
+
+// The value of a raw sample as fp32 (v_cvt_f32_ubyte0..3 on the bytes of a dword, v_cvt_f32_u32 behind shift and mask on words).
+template <int SB>
+JINC_WIDEN_HD float value_of(uint32_t raw, uint32_t shift, uint32_t mask) {
+    if constexpr (SB == 1) return static_cast<float>(raw);
+    else return static_cast<float>((raw >> shift) & mask);
+}
+// Sample i of a run of SB-byte samples held in dwords (i is a constant once the loops around the calls are unrolled).
+template <int SB>
+JINC_WIDEN_HD float value_at(const uint32_t* w, int i, uint32_t shift, uint32_t mask) {
+    if constexpr (SB == 1) return value_of<1>((w[i >> 2] >> (8 * (i & 3))) & 0xffu, shift, mask);
+    else return value_of<2>((w[i >> 1] >> (16 * (i & 1))) & 0xffffu, shift, mask);
+}
+JINC_WIDEN_HD uint32_t float_bits(float v) {
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    return b;
+}
+// binary16 of an fp32 value that is an integer in 0 .. 2047: exact, so every rounding mode gives the same bits.
+JINC_WIDEN_HD uint32_t half_bits(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const _Float16 h = static_cast<_Float16>(v);  // v_cvt_f16_f32
+    uint16_t b;
+    memcpy(&b, &h, 2);
+    return b;
+#else
+    // (host: no half type needed) fp32 is 1.m x 2^(e - 127) with at most 10 significant bits of m here: the exponent moves from
+    // bias 127 to bias 15, the mantissa loses 13 bits that are zeros.
+    const uint32_t f = float_bits(v);
+    return f ? (f >> 13) - ((127u - 15u) << 10) : 0u;
+#endif
+}
+
+// Lane `lane` of the wave that owns row `row` of frame `frame` of group g.
+template <int SB, int N, int OB>
+JINC_WIDEN_HD void widen_row(const WidenGroup& g, uint32_t mask, uint32_t frame, uint32_t row, uint32_t lane) {
+    static_assert((SB == 1 || SB == 2) && N >= 1 && N <= 4 && (OB == 4 || OB == 2), "no such form");
+    constexpr uint32_t P = 16 / SB;          // pixels a lane owns per step
+    constexpr int kVectors = OB / SB;        // 16-byte vectors of P converted samples
+    constexpr int kPerVector = 16 / OB;      // samples in one of them
+    const char* __restrict__ packed = g.packed + frame * g.packed_frame_stride + static_cast<size_t>(row) * g.packed_pitch;
+    const size_t dense = frame * g.plane_frame_stride + static_cast<size_t>(row) * g.plane_pitch;
+    for (uint32_t x = lane * P; x < g.vec_pixels; x += 64 * P) {
+        uint32_t in[4 * N];
+        load_pixels<N>(packed + static_cast<size_t>(x) * (N * SB), g.unit, in);
+#pragma unroll
+        for (int c = 0; c < N; ++c) {
+            if (!g.plane[c]) continue;
+            const uint32_t sh = g.shift[c];
+            char* out = g.plane[c] + dense + static_cast<size_t>(x) * OB;
+#pragma unroll
+            for (int v = 0; v < kVectors; ++v) {
+                uint32_t o[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int p = v * kPerVector + (OB == 4 ? k : 2 * k);  // the pixel of dword k's (first) sample
+                    if constexpr (OB == 4) o[k] = float_bits(value_at<SB>(in, p * N + c, sh, mask));
+                    else o[k] = half_bits(value_at<SB>(in, p * N + c, sh, mask)) | (half_bits(value_at<SB>(in, (p + 1) * N + c, sh, mask)) << 16);
+                }
+                store16(out + 16 * v, o);
+            }
+        }
+    }
+    for (uint32_t x = g.vec_pixels + lane; x < g.width; x += 64) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) {
+            if (!g.plane[c]) continue;
+            uint32_t raw;
+            if constexpr (SB == 1) raw = reinterpret_cast<const uint8_t*>(packed)[static_cast<size_t>(x) * N + c];
+            else raw = reinterpret_cast<const uint16_t*>(packed)[static_cast<size_t>(x) * N + c];
+            const float v = value_of<SB>(raw, g.shift[c], mask);
+            if constexpr (OB == 4) reinterpret_cast<float*>(g.plane[c] + dense)[x] = v;
+            else reinterpret_cast<uint16_t*>(g.plane[c] + dense)[x] = static_cast<uint16_t>(half_bits(v));
+        }
+    }
+}
+
+}  // namespace widen
+}  // namespace jinc

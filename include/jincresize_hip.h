@@ -363,6 +363,46 @@ JINC_API int jinc_filter_process_device_v210(jinc_filter *f, const void *const s
 /* Bytes of the blocks of one v210 row of `width` luma samples: 16 * ceil(width / 6); 0 for width < 1.  Needs no device. */
 JINC_API size_t jinc_v210_row_bytes(int width);
 
+/* INTEGER device frames into an fp32 or binary16 filter: a decoder's NV12 / P010 surface resampled straight into the float or half
+ * planes a network reads, with nothing rounded to a code value on the way.
+ *   `f` is an fp32 filter (bits_per_component 32) or a binary16 filter (JINC_SAMPLE_FLOAT16); its geometry, number of components
+ *   and sub-sampling describe the frame exactly as for jinc_filter_process_device_strided.
+ *   The SOURCE is integer samples, addressed exactly as in jinc_filter_process_device_shifted (base, pitch, step 1 .. 4 in samples,
+ *   shift, frame stride; NULL step and shift arrays mean all ones and all zeros), but the sample size comes from src_bits, not from
+ *   the filter: src_bits 8 is 1-byte samples, src_bits 9 .. 16 little-endian 2-byte words.  Sample x of row y of frame n of plane i
+ *   lies at base[i] + n * frame_stride[i] + y * pitch[i] + x * step[i] * bytes, a shift lies in 0 .. 8 * bytes - src_bits, and the
+ *   value of a source sample is (raw >> shift) & ((1 << src_bits) - 1): whatever lies below and above the sample is ignored.  The
+ *   source is never written.
+ *   The DESTINATION is float / half planes of the filter's own type: exactly the dst side of jinc_filter_process_device_strided on
+ *   that filter, steps included (interleaved RGB float output through the same merge), with the same no-overwrite guarantee.
+ *     NV12 into YUV420PS:           Y = y, step 1; U = uv, V = uv + 1 sample, step 2; src_bits 8.
+ *     P010 into YUV420PH or PS:     the same with src_bits 10 and all shifts 6.
+ *     BGRA8 into RGBPS:             G = p + 1, B = p, R = p + 2, all step 4; src_bits 8.
+ *     planar YUV420P10:             steps 1, shifts 0, src_bits 10.
+ *   The result is exactly what jinc_filter_process_device computes on that filter for dense planes holding those values converted
+ *   to the filter's sample type (the conversion is exact): the same plan, the same un-fused chain, the trimmed support (integer
+ *   values are always finite), nothing clamped, and for half filters the same round-to-nearest-even narrowing of the fp32 sum.
+ *   Since the integer filters convert every source sample to float before the multiply, the fp32 result is their sum in front of
+ *   clamp and lrintf.
+ *   A binary16 filter needs src_bits <= 11, so that every value is exact in binary16 (8-bit and 10-bit sources: NV12, P010, Y210);
+ *   wider samples go into an fp32 filter.
+ * JINC_ERR_INVALID_ARG, each with a message of its own, before the device check and before anything is queued: an integer filter;
+ * src_bits outside 8 .. 16; src_bits above 11 on a binary16 filter; a step outside 1 .. 4 (either side); a shift outside its range;
+ * a source base not aligned to the source sample size; a source pitch below ((width - 1) * step + 1) * bytes of that plane.  Then
+ * null arguments, nframes and frame strides as for jinc_filter_process_device_shifted.
+ * EVERY source plane takes a dense float / half stand-in of the filter's own (the scratch of the strided call: same knob
+ * strided_scratch_bytes, same slicing of long calls, same ordering between calls, so these calls may alternate with strided ones
+ * on one filter), rows padded to 256 bytes; a destination plane takes one only where its step is not 1.  1080p -> 4K NV12 into
+ * planar fp32: 1920 x 4 = 7680 and 960 x 4 = 3840 bytes per row are multiples of 256 already, so a frame needs 7680 x 1080 +
+ * 2 x 3840 x 540 = 12 441 600 bytes and the 1 GiB default holds floor(1 073 741 824 / 12 441 600) = 86 frames (a call of 128 runs
+ * as 86 + 42); P010 into planar binary16 needs half of that, 6 220 800 bytes, 172 frames: a call of 128 in one slice.
+ * Y410 / RGB10A2 words and v210 blocks are not taken as widened sources. */
+JINC_API int jinc_filter_process_device_widened(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                const int src_sample_step[4], const int src_sample_shift[4], int src_bits,
+                                                const size_t src_frame_stride[4], void *const dst[4], const int dst_pitch[4],
+                                                const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
+                                                void *hip_stream);
+
 /* The field offsets of a named 10:10:10:2 word in the library's plane order, and the fill that sets every spare bit (an opaque
  * pixel); opaque_fill may be NULL.  Needs no device.  Names match without regard to case; an unknown one is
  * JINC_ERR_INVALID_ARG.
