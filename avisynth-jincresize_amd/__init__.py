@@ -88,7 +88,8 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share",
            "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided",
            "jinc_filter_process_device_shifted", "jinc_filter_process_device_packed10", "jinc_packed10_layout",
-           "jinc_filter_process_device_v210", "jinc_v210_row_bytes", "jinc_filter_process_device_widened"]
+           "jinc_filter_process_device_v210", "jinc_v210_row_bytes", "jinc_filter_process_device_widened",
+           "jinc_filter_process_device_widened_packed10", "jinc_filter_process_device_widened_v210"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -126,6 +127,8 @@ def lib():
         L.jinc_filter_process_device_v210.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_int, C.c_void_p]
         L.jinc_filter_process_device_widened.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_widened_packed10.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_widened_v210.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
         L.jinc_v210_row_bytes.argtypes = [C.c_int]
         L.jinc_v210_row_bytes.restype = C.c_size_t
         L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
@@ -897,6 +900,44 @@ class Filter:
             self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_I4, src_shifts), int(src_bits),
             arr(_S4, src_strides), arr(_P4, dst_ptrs), arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_S4, dst_strides), int(nframes),
             C.c_void_p(stream)))
+
+    def process_device_widened_packed10(self, src_ptr: int, src_pitch: int, src_offsets, src_stride: int, dst_ptrs, dst_pitches, dst_steps,
+                                        dst_strides, nframes: int, stream: int = 0) -> None:
+        """10:10:10:2 words into this fp32 / binary16 filter (jinc_filter_process_device_widened_packed10; three components, no
+        sub-sampling): the source is ONE buffer of 32-bit words, one per pixel, plane i's value is (word >> src_offsets[i]) & 1023
+        (packed10_layout names the usual words); the destination side is process_device_strided's on this filter.  The result is
+        process_device's on dense planes of those values as float / half.  Steps and frame strides may be None."""
+        n = self.fmt.planes
+
+        def arr(kind, values, count=n):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(min(count, len(values))):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_widened_packed10(
+            self._h, C.c_void_p(src_ptr), int(src_pitch), arr(C.c_int * 3, src_offsets, 3), C.c_size_t(int(src_stride or 0)),
+            arr(_P4, dst_ptrs), arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
+
+    def process_device_widened_v210(self, src_ptr: int, src_pitch: int, src_stride: int, dst_ptrs, dst_pitches, dst_steps, dst_strides,
+                                    nframes: int, stream: int = 0) -> None:
+        """v210 blocks into this fp32 / binary16 4:2:2 filter (jinc_filter_process_device_widened_v210; YUV422PS, YUV422PH): the
+        source is ONE buffer of 16-byte blocks of six pixels, a row is v210_row_bytes(width) bytes; the destination side is
+        process_device_strided's on this filter.  The result is process_device's on dense planes of the field values as float /
+        half.  Steps and frame strides may be None."""
+        n = self.fmt.planes
+
+        def arr(kind, values):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(min(n, len(values))):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_widened_v210(
+            self._h, C.c_void_p(src_ptr), int(src_pitch), C.c_size_t(int(src_stride or 0)), arr(_P4, dst_ptrs), arr(_I4, dst_pitches),
+            arr(_I4, dst_steps), arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
     strided_groups = staticmethod(strided_groups)

@@ -1227,10 +1227,11 @@ void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pi
 // pack_v210_kernel builds the blocks from the result stand-ins (kernel_interleave.hip, v210_rows.h).  Everything else is
 // run_on_stand_ins, as for the strided, shifted and packed10 calls.  Dense planes per frame: the luma stand-in is `width` samples
 // wide, both chroma stand-ins width / 2 -- 2 planes' worth of 2-byte samples, 4 bytes x the side's pixels (rows padded to 256
-// bytes).  1080p -> 4K: 1920 x 2 = 3840 and 960 x 2 = 1920 bytes are multiples of 256 already (as are 7680 and 3840), so the
-// source side takes (3840 + 2 x 1920) x 1080 = 8 294 400 bytes, the destination side (7680 + 2 x 3840) x 2160 = 33 177 600; both
-// 41 472 000, and the 1 GiB default holds floor(1 073 741 824 / 41 472 000) = 25 frames -- below kSliceFrames, so no rounding: a
-// call of 128 runs as 5 x 25 + 3.  v210 source only: 129 frames, a call of 128 in one slice; v210 destination only: 32 frames.
+// bytes).  1080p -> 4K: 3840, 7680 and 3840 bytes a row are multiples of 256 already, the source's chroma rows of 960 x 2 = 1920
+// bytes are padded to 2048, so the source side takes (3840 + 2 x 2048) x 1080 = 8 570 880 bytes, the destination side
+// (7680 + 2 x 3840) x 2160 = 33 177 600; both 41 748 480, and the 1 GiB default holds floor(1 073 741 824 / 41 748 480) = 25
+// frames -- below kSliceFrames, so no rounding: a call of 128 runs as 5 x 25 + 3.  v210 source only: 125 frames, a call of 128 runs
+// as 125 + 3; v210 destination only: 32 frames.
 void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], bool src_is_v210, const size_t* src_fs,
                   void* const dst[4], const int dst_pitch[4], bool dst_is_v210, const size_t* dst_fs, int nframes, hipStream_t stream) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
@@ -1313,6 +1314,20 @@ void fill_widen_args(const jinc_filter& f, const Side& s, const void* const base
         a_n.g[a_n.ngroups++] = e;
     }
 }
+// The merge of a widened call's destination side (enqueue_strided's, without shifts): planes with a step other than 1 out of their
+// result stand-ins.  Returns the number of launches.
+int merge_widened(const jinc_filter& f, const Side& out, const void* const dst_c[4], const int dst_pitch[4], const int* dst_step,
+                  const size_t* dst_fs, char* scratch, int k0, int slice, int n, int nframes, hipStream_t stream) {
+    InterleaveArgs merge[5];
+    fill_args(f, out, dst_c, dst_pitch, dst_step, nullptr, dst_fs, scratch, k0, slice, nframes, true, merge);
+    int launches = 0;
+    for (int step = 1; step <= 4; ++step)
+        if (merge[step].ngroups) {
+            hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], f.vi_in.component_size, step, n, stream)), "merge launch");
+            ++launches;
+        }
+    return launches;
+}
 }  // namespace
 
 void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
@@ -1351,17 +1366,75 @@ void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pit
                 }
             return launches;
         },
+        [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });
+}
+
+// ---- jinc_filter_process_device_widened_packed10 / _v210: Y410 / RGB10A2 words and v210 blocks into an fp32 / binary16 filter ----
+// The source is ONE group of the filter's three planes, as the packed side of enqueue_packed10 or the v210 side of enqueue_v210, and
+// every source plane takes a stand-in of the FILTER's type: widen_fields_kernel / widen_v210_kernel (kernel_widen.hip) fill them
+// with float(field) -- ten bits, exact in fp32 and in binary16.  The destination side and its merge are enqueue_widened's, and
+// everything else is run_on_stand_ins, so these calls alternate with strided and widened ones on one filter.  The report counts the
+// widening launch as a split launch.
+// Dense planes per frame of a 1080p source (rows padded to 256 bytes), planar destination: Y410 into fp32 3 x 7680 x 1080 =
+// 24 883 200 bytes, floor(1 073 741 824 / 24 883 200) = 43 frames under the 1 GiB default; into binary16 3 x 3840 x 1080 =
+// 12 441 600 bytes, 86 frames.  v210 into fp32 (7680 + 2 x 3840) x 1080 = 16 588 800 bytes, 64 frames; into binary16 the chroma
+// rows of 960 x 2 = 1920 bytes are padded to 2048: (3840 + 2 x 2048) x 1080 = 8 570 880 bytes, 125 frames.  All below kSliceFrames,
+// so no rounding: a call of 128 runs as 43 + 43 + 42, 86 + 42, 64 + 64 and 125 + 3.
+namespace {
+// The sides of such a call: the source one group of three stand-ins, the destination enqueue_strided's.
+void widened_words_sides(const jinc_filter& f, void* const dst[4], const int dst_pitch[4], const int* dst_step, const size_t* dst_fs,
+                         int nframes, Side& in, Side& out) {
+    for (int i = 0; i < f.planecount; ++i) {
+        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
+        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
+        in.group_of[i] = in.channel_of[i] = 0;
+    }
+    in.ngroups = 1;
+    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
+    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, nullptr, nframes > 1 ? dst_fs : nullptr, out.w, out.h, f.vi_in.component_size, f.planecount, out.group_of, out.channel_of);
+    check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
+}
+}  // namespace
+
+void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, const int* src_fields, size_t src_fs, void* const dst[4],
+                              const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream) {
+    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    Side in, out;
+    widened_words_sides(f, dst, dst_pitch, dst_step, dst_fs, nframes, in, out);
+    check_packed10_side(src, src_pitch, &src_fs, in.w[0], nframes);  // (filter.cpp has refused these already, with messages of this call's own)
+    // (every source plane has a stand-in: run_on_stand_ins reads none of these)
+    const void* const src_planes[4] = {src, src, src, nullptr};
+    const int src_pitches[4] = {src_pitch, src_pitch, src_pitch, 0};
+    const size_t src_strides[4] = {src_fs, src_fs, src_fs, 0};
+    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
+    run_on_stand_ins(
+        f, in, out, src_planes, src_pitches, src_strides, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
-            InterleaveArgs merge[5];
-            fill_args(f, out, dst_c, dst_pitch, dst_step, nullptr, dst_fs, scratch, k0, slice, nframes, true, merge);
-            int launches = 0;
-            for (int step = 1; step <= 4; ++step)
-                if (merge[step].ngroups) {
-                    hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], static_cast<int>(sb), step, n, stream)), "merge launch");
-                    ++launches;
-                }
-            return launches;
-        });
+            const jinc::FieldArgs a = field_args(in, src, src_pitch, src_strides, src_fields, 0u, scratch, k0, slice, nframes);
+            hip_check(static_cast<hipError_t>(jinc::launch_widen_fields(a, f.vi_in.component_size, n, stream)), "widen fields launch");
+            return 1;
+        },
+        [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });
+}
+
+void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t src_fs, void* const dst[4], const int dst_pitch[4],
+                          const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream) {
+    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    Side in, out;
+    widened_words_sides(f, dst, dst_pitch, dst_step, dst_fs, nframes, in, out);
+    check_v210_side(src, src_pitch, &src_fs, in, nframes);  // (filter.cpp has refused these already, with messages of this call's own)
+    const void* const src_planes[4] = {src, src, src, nullptr};
+    const int src_pitches[4] = {src_pitch, src_pitch, src_pitch, 0};
+    const size_t src_strides[4] = {src_fs, src_fs, src_fs, 0};
+    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
+    run_on_stand_ins(
+        f, in, out, src_planes, src_pitches, src_strides, dst, dst_pitch, dst_fs, nframes, stream,
+        [&](char* scratch, int k0, int slice, int n) {
+            const jinc::V210Args a = v210_args(in, src, src_pitch, src_strides, scratch, k0, slice, nframes);
+            hip_check(static_cast<hipError_t>(jinc::launch_widen_v210(a, f.vi_in.component_size, n, stream)), "widen v210 launch");
+            return 1;
+        },
+        [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });
 }
 
 }  // namespace host

@@ -52,6 +52,25 @@ const jinc::PlanePlan* table_or_null(const jinc_filter* f, int table) {
     return &f->plans[table];
 }
 
+// What the two widened calls for words and blocks refuse alike, behind the checks of the filter: the destination steps, then base,
+// pitch and frame stride of the one source buffer (`what`: "packed 10-bit words" / "v210 blocks"; row_bytes: what a row occupies).
+// Returns a message, empty when there is nothing to refuse.
+std::string refuse_widened_words(const jinc_filter* f, const char* what, const void* src, int src_pitch, size_t src_frame_stride,
+                                 size_t row_bytes, const char* row_text, const int* dst_sample_step, int nframes) {
+    for (int i = 0; dst_sample_step && i < f->planecount; ++i)
+        if (dst_sample_step[i] < 1 || dst_sample_step[i] > 4)
+            return "JincResize: destination sample step of a widened call for " + std::string(what) + " must be in 1..4 (got " +
+                   std::to_string(dst_sample_step[i]) + ").";
+    if (reinterpret_cast<uintptr_t>(src) % 4) return "JincResize: widened " + std::string(what) + " are not aligned to 4 bytes.";
+    if (src_pitch % 4) return "JincResize: pitch " + std::to_string(src_pitch) + " of widened " + what + " is not a multiple of 4.";
+    if (nframes > 1 && src_frame_stride % 4)
+        return "JincResize: frame stride " + std::to_string(src_frame_stride) + " of widened " + what + " is not a multiple of 4.";
+    if (src_pitch <= 0 || static_cast<size_t>(src_pitch) < row_bytes)
+        return "JincResize: pitch " + std::to_string(src_pitch) + " of widened " + what + " is smaller than the row's " + std::to_string(row_bytes) +
+               " bytes (" + row_text + ").";
+    return std::string();
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,6 +388,74 @@ int jinc_filter_process_device_widened(jinc_filter* f, const void* const src[4],
         hip_check(hipSetDevice(f->device), "hipSetDevice");
         enqueue_widened(*f, src, src_pitch, src_sample_step, src_sample_shift, src_bits, src_frame_stride, dst, dst_pitch, dst_sample_step,
                         dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int jinc_filter_process_device_widened_packed10(jinc_filter* f, const void* src, int src_pitch, const int src_field_offset[3],
+                                                size_t src_frame_stride, void* const dst[4], const int dst_pitch[4],
+                                                const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
+                                                void* hip_stream) {
+    // the filter, the offsets, the destination steps and the source's base, pitch and frame stride first (they need no device),
+    // then the checks of jinc_filter_process_device_shifted in its order
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (!f->float_samples())
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words need an fp32 or binary16 filter; this filter has " +
+                                              std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_packed10).");
+    if (f->planecount != 3 || f->subsampled)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words need a float filter with three components and no sub-sampling "
+                                          "(YUV444PS, YUV444PH, RGBPS, RGBPH); this filter has " + std::to_string(f->planecount) + " component(s), sub_w " +
+                                              std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
+    for (int i = 0; src_field_offset && i < 3; ++i)
+        if (src_field_offset[i] < 0 || src_field_offset[i] > 22)
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: a field offset of a widened packed 10:10:10:2 word must be in 0..22 (got " +
+                                                  std::to_string(src_field_offset[i]) + ").");
+    for (int i = 0; src_field_offset && i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (src_field_offset[i] - src_field_offset[j] < 10 && src_field_offset[j] - src_field_offset[i] < 10)
+                return fail(JINC_ERR_INVALID_ARG, "JincResize: two fields of a widened packed 10:10:10:2 word overlap (offsets " +
+                                                      std::to_string(src_field_offset[i]) + " and " + std::to_string(src_field_offset[j]) + ").");
+    int w = 0, h = 0;
+    f->plane_dims(f->vi_in, 0, w, h);
+    const std::string refusal = refuse_widened_words(f, "packed 10-bit words", src, src_pitch, src_frame_stride, 4 * static_cast<size_t>(w),
+                                                     "4 * width", dst_sample_step, nframes);
+    if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
+    if (!src || !src_field_offset || !dst || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && !dst_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_widened_packed10(*f, src, src_pitch, src_field_offset, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_frame_stride,
+                                 nframes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int jinc_filter_process_device_widened_v210(jinc_filter* f, const void* src, int src_pitch, size_t src_frame_stride, void* const dst[4],
+                                            const int dst_pitch[4], const int dst_sample_step[4], const size_t dst_frame_stride[4],
+                                            int nframes, void* hip_stream) {
+    // the filter, the destination steps and the source's base, pitch and frame stride first (they need no device), then the checks
+    // of jinc_filter_process_device_shifted in its order
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (!f->float_samples())
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: widened v210 blocks need an fp32 or binary16 filter; this filter has " +
+                                              std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_v210).");
+    if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: widened v210 blocks need a float filter with three components and 4:2:2 sub-sampling "
+                                          "(YUV422PS, YUV422PH: sub_w 1, sub_h 0); this filter has " + std::to_string(f->planecount) + " component(s), sub_w " +
+                                              std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
+    int w = 0, h = 0;
+    f->plane_dims(f->vi_in, 0, w, h);
+    const std::string refusal = refuse_widened_words(f, "v210 blocks", src, src_pitch, src_frame_stride, v210_row_bytes(w),
+                                                     "16 * ceil(width / 6)", dst_sample_step, nframes);
+    if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
+    if (!src || !dst || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && !dst_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_widened_v210(*f, src, src_pitch, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_frame_stride, nframes,
+                             static_cast<hipStream_t>(hip_stream));
     });
 }
 

@@ -42,6 +42,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "v210_exchange.h"
 #include "v210_rows.h"
 
 namespace jinc {
@@ -331,15 +332,8 @@ int launch_fields(const FieldArgs& a, int nframes, void* stream) {
     return hipGetLastError();
 }
 
-// ---- v210 blocks (kernels.h V210Args; the row functions: v210_rows.h) ----
-// The value lane l ^ 1 holds (quad_perm [1, 0, 3, 2]).  Both lanes of a pair are active wherever this is called: pairs of blocks
-// start at even blocks and the walk starts at block `lane`.
-__device__ __forceinline__ v210::Three from_partner(const v210::Three& t) {
-    v210::Three r;
-    r.lo = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(t.lo), 0xB1, 0xF, 0xF, false));
-    r.hi = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(t.hi), 0xB1, 0xF, 0xF, false));
-    return r;
-}
+// ---- v210 blocks (kernels.h V210Args; the row functions: v210_rows.h; the exchange between lanes l and l ^ 1: v210_exchange.h) ----
+using v210::from_partner;
 
 // Row blockIdx.x * 4 + wave of frame blockIdx.y (the wave's number through a scalar register: the row's addresses are wave-uniform).
 __global__ __launch_bounds__(256) void unpack_v210_kernel(const V210Args a) {

@@ -11,10 +11,21 @@
 // division or a modulo.  The row function is widen_rows.h: a lane owns 16 / SB whole pixels per step, N 16-byte loads (dwords where
 // the group's alignment allows no more) and OB / SB 16-byte stores per plane; tails, unaligned groups and the last pixel of a group
 // with a channel missing move sample by sample.  The source is read only.
+//
+// Two more sources whose samples neither a step nor a shift addresses (jinc_filter_process_device_widened_packed10 / _v210;
+// dispatch.cpp enqueue_widened_packed10 / enqueue_widened_v210): 10:10:10:2 words -- Y410, R10G10B10A2 and kin, three 10-bit fields
+// in one 32-bit word per pixel -- and v210 blocks, six pixels of 10-bit 4:2:2 in 16 bytes.  widen_fields_kernel has the shape of
+// unpack_fields_kernel and widen_v210_kernel that of unpack_v210_kernel (kernel_interleave.hip): one launch over every row and
+// frame of a slice, grid = row blocks x frames, a wave owns a row; they store the field values converted instead of 16-bit
+// integers.  The row functions are widen_fields_rows.h and widen_v210_rows.h; the exchange between the two lanes of a block pair
+// is v210_exchange.h's, RAW samples in front of the conversion.  Plain C++ and that one DPP builtin: no assembly, no scratch.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "v210_exchange.h"
+#include "widen_fields_rows.h"
 #include "widen_rows.h"
+#include "widen_v210_rows.h"
 
 namespace jinc {
 namespace {
@@ -48,7 +59,55 @@ int launch_by_step(const WidenArgs& a, int step, int nframes, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
+// ---- 10:10:10:2 words (kernels.h FieldArgs; the row function: widen_fields_rows.h) ----
+// Row blockIdx.x * 4 + wave of frame blockIdx.y.
+template <int OB>
+__global__ __launch_bounds__(256) void widen_fields_kernel(const FieldArgs a) {
+    const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row < a.rows) widen::widen_fields_row<OB>(a, blockIdx.y, row, threadIdx.x & 63u);
+}
+
+// ---- v210 blocks (kernels.h V210Args; the row functions: widen_v210_rows.h) ----
+// Row blockIdx.x * 4 + wave of frame blockIdx.y (the wave's number through a scalar register: the row's addresses are wave-uniform).
+template <int OB>
+__global__ __launch_bounds__(256) void widen_v210_kernel(const V210Args a) {
+    const uint32_t row = blockIdx.x * 4 + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+    if (row >= a.rows) return;
+    const uint32_t lane = threadIdx.x & 63u, paired = v210::paired_blocks(a), blocks = v210::row_blocks(a);
+    const v210::RowOf r = v210::row_of(a, blockIdx.y, row);
+    for (uint32_t b = lane; b < paired; b += 64) {
+        v210::LaneState s;
+        v210::widen_pair_begin<OB>(a, r, b, s);
+        v210::widen_pair_end<OB>(a, r, b, s, v210::from_partner(s.send));
+    }
+    for (uint32_t b = paired + lane; b < blocks; b += 64) v210::widen_tail<OB>(a, r, b);
+}
+
 }  // namespace
+
+int launch_widen_fields(const FieldArgs& a, int out_bytes, int nframes, void* stream) {
+    if (nframes <= 0 || a.rows == 0 || a.width == 0) return hipSuccess;
+    if ((a.unit != 16 && a.unit != 4) || a.vec_pixels > a.width || a.vec_pixels % 8u) return hipErrorInvalidValue;  // (a word is the smallest access)
+    for (int c = 0; c < 3; ++c)
+        if (a.offset[c] > 22u) return hipErrorInvalidValue;
+    const dim3 grid((a.rows + 3) / 4, static_cast<uint32_t>(nframes));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (out_bytes == 4) hipLaunchKernelGGL(widen_fields_kernel<4>, grid, dim3(256), 0, s, a);
+    else if (out_bytes == 2) hipLaunchKernelGGL(widen_fields_kernel<2>, grid, dim3(256), 0, s, a);
+    else return hipErrorInvalidValue;  // (no kernel for this shape: an error, never a silent skip)
+    return hipGetLastError();
+}
+
+int launch_widen_v210(const V210Args& a, int out_bytes, int nframes, void* stream) {
+    if (nframes <= 0 || a.rows == 0 || a.width == 0) return hipSuccess;
+    if ((a.unit != 16 && a.unit != 4) || a.whole_blocks != a.width / 6 || (a.width & 1u)) return hipErrorInvalidValue;
+    const dim3 grid((a.rows + 3) / 4, static_cast<uint32_t>(nframes));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (out_bytes == 4) hipLaunchKernelGGL(widen_v210_kernel<4>, grid, dim3(256), 0, s, a);
+    else if (out_bytes == 2) hipLaunchKernelGGL(widen_v210_kernel<2>, grid, dim3(256), 0, s, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
 
 int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int nframes, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);

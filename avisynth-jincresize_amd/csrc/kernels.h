@@ -588,6 +588,13 @@ struct WidenArgs {
 // One launch over every group and frame of `a`: src_bytes 1 or 2 (a byte takes no shift: mask 0xff, shifts 0); step 1 .. 4 (the
 // same for all groups of a launch); out_bytes 4 (fp32) or 2 (binary16: every value must be <= 2047 to be exact).
 int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int nframes, void* stream);
+// 10:10:10:2 words / v210 blocks -> the three dense planes of an fp32 / binary16 filter (kernel_widen.hip, widen_fields_rows.h,
+// widen_v210_rows.h; jinc_filter_process_device_widened_packed10 / _v210).  The records are FieldArgs and V210Args as they are, read
+// with samples of out_bytes (4: fp32, 2: binary16) on the plane side: plane c holds float / binary16 of the 10-bit field value at
+// plane[c] + n * frame stride + y * pitch + x * out_bytes (pitches and frame strides stay in bytes).  The word / block side is read
+// only; `fill` is not read.  One launch over every row and frame of `a`.
+int launch_widen_fields(const FieldArgs& a, int out_bytes, int nframes, void* stream);
+int launch_widen_v210(const V210Args& a, int out_bytes, int nframes, void* stream);
 
 // Measurement hook (kernel_probe.hip): `samplers` single-lane workgroups stamp the shader clock counter and the 100 MHz
 // real-time counter until *stop_flag (device memory) becomes non-zero or max_seconds pass; out[2 k] = shader ticks,

@@ -353,9 +353,11 @@ JINC_API int jinc_filter_process_device_packed10(jinc_filter *f, const void *con
  * multiples of 16 get 16-byte accesses on the block side, others dwords.
  * A v210 side takes dense stand-ins of the filter's own for its three planes (the scratch of the strided call, same knob
  * strided_scratch_bytes, same ordering between calls, so these calls may alternate with strided, shifted and packed10 ones on
- * one filter): 4 bytes per pixel of that side, rows padded to 256 bytes.  1080p -> 4K with both sides v210 is
- * 4 x (1920 x 1080 + 3840 x 2160) = 41 472 000 bytes per frame, so the 1 GiB default runs a long call in slices of 25 frames
- * (128 frames: 5 x 25 + 3); with only the source v210 129 frames fit (128 in one slice), with only the destination 32. */
+ * one filter): 4 bytes per pixel of that side, rows padded to 256 bytes.  1080p -> 4K with both sides v210: the source's chroma
+ * rows of 960 x 2 = 1920 bytes are padded to 2048, the other rows (3840, 7680, 3840 bytes) are multiples of 256 already, so a
+ * frame needs (3840 + 2 x 2048) x 1080 + (7680 + 2 x 3840) x 2160 = 8 570 880 + 33 177 600 = 41 748 480 bytes and the 1 GiB
+ * default runs a long call in slices of 25 frames (128 frames: 5 x 25 + 3); with only the source v210 125 frames fit (128 frames:
+ * 125 + 3), with only the destination 32. */
 JINC_API int jinc_filter_process_device_v210(jinc_filter *f, const void *const src[4], const int src_pitch[4], int src_is_v210,
                                              const size_t src_frame_stride[4], void *const dst[4], const int dst_pitch[4],
                                              int dst_is_v210, const size_t dst_frame_stride[4], int nframes, void *hip_stream);
@@ -396,12 +398,69 @@ JINC_API size_t jinc_v210_row_bytes(int width);
  * planar fp32: 1920 x 4 = 7680 and 960 x 4 = 3840 bytes per row are multiples of 256 already, so a frame needs 7680 x 1080 +
  * 2 x 3840 x 540 = 12 441 600 bytes and the 1 GiB default holds floor(1 073 741 824 / 12 441 600) = 86 frames (a call of 128 runs
  * as 86 + 42); P010 into planar binary16 needs half of that, 6 220 800 bytes, 172 frames: a call of 128 in one slice.
- * Y410 / RGB10A2 words and v210 blocks are not taken as widened sources. */
+ * Y410 / RGB10A2 words and v210 blocks have calls of their own: jinc_filter_process_device_widened_packed10 / _v210 below. */
 JINC_API int jinc_filter_process_device_widened(jinc_filter *f, const void *const src[4], const int src_pitch[4],
                                                 const int src_sample_step[4], const int src_sample_shift[4], int src_bits,
                                                 const size_t src_frame_stride[4], void *const dst[4], const int dst_pitch[4],
                                                 const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
                                                 void *hip_stream);
+
+/* 10:10:10:2 WORDS into an fp32 or binary16 filter: the HDR 4:4:4 surface of decoders and swap chains (Y410, R10G10B10A2, the DRM
+ * 2101010 / 1010102 orders) resampled straight into the float or half planes a network reads, with nothing rounded to a code value
+ * and nothing clamped on the way.
+ *   `f` is an fp32 or binary16 filter with three components and no sub-sampling (YUV444PS, YUV444PH, RGBPS, RGBPH).
+ *   The SOURCE is ONE buffer of little-endian 32-bit words, one per pixel, addressed exactly as the packed side of
+ *   jinc_filter_process_device_packed10: pixel x of row y of frame n is the word at src + n * src_frame_stride + y * src_pitch +
+ *   4 * x and its value of plane i (library order Y,U,V or G,B,R; jinc_packed10_layout gives the offsets in that order) is
+ *   (word >> src_field_offset[i]) & 1023.  Source bits outside the three fields and everything behind a row's `width` words are
+ *   ignored whatever they hold (the 2-bit alpha is not resampled).  The source is never written.  src_frame_stride is read only
+ *   for nframes > 1.
+ *   The DESTINATION is exactly the dst side of jinc_filter_process_device_widened, which is the strided call's: the filter's own
+ *   float / half planes with steps 1 .. 4 (NULL: all ones; interleaved float RGB through the same merge), with the same
+ *   no-overwrite guarantee.
+ *   The result is exactly what jinc_filter_process_device computes on that filter for dense planes holding the field values
+ *   converted to the filter's sample type.  Ten bits are exact in fp32 and in binary16 alike, so half filters need no extra rule.
+ *   The same plan, the same un-fused chain, the same finite scan (which finds nothing), and for half filters the same
+ *   round-to-nearest-even narrowing of the fp32 sum.
+ * JINC_ERR_INVALID_ARG, each with a message of its own, before the null checks of the plane arrays, before the device check and
+ * before anything is queued: an integer filter; a float filter of another shape (four components, sub-sampled chroma, a single
+ * plane); an offset outside 0 .. 22; two fields that overlap; a destination step outside 1 .. 4; a source base, a source pitch or
+ * (with nframes > 1) a source frame stride that is no multiple of 4; a source pitch below 4 * width.  Then null arguments, nframes
+ * and frame strides as for jinc_filter_process_device_shifted.  Base, pitch and frame stride that are all multiples of 16 get
+ * 16-byte loads, others dwords.
+ * The three source planes take dense stand-ins of the filter's own type (the scratch of the strided call: same knob
+ * strided_scratch_bytes, same slicing of long calls, same ordering between calls, so these calls may alternate with strided and
+ * widened ones on one filter), rows padded to 256 bytes; a destination plane takes one only where its step is not 1.  1080p Y410
+ * into planar fp32: rows of 1920 x 4 = 7680 bytes are multiples of 256 already, so a frame needs 3 x 7680 x 1080 = 24 883 200
+ * bytes and the 1 GiB default holds floor(1 073 741 824 / 24 883 200) = 43 frames (a call of 128 runs as 43 + 43 + 42); into planar
+ * binary16 3 x 3840 x 1080 = 12 441 600 bytes, 86 frames (86 + 42). */
+JINC_API int jinc_filter_process_device_widened_packed10(jinc_filter *f, const void *src, int src_pitch,
+                                                         const int src_field_offset[3], size_t src_frame_stride,
+                                                         void *const dst[4], const int dst_pitch[4],
+                                                         const int dst_sample_step[4], const size_t dst_frame_stride[4],
+                                                         int nframes, void *hip_stream);
+
+/* v210 BLOCKS into an fp32 or binary16 filter: the SDI / ProRes 4:2:2 surface resampled straight into float or half planes.
+ *   `f` is an fp32 or binary16 filter with three components, sub_w 1 and sub_h 0 (YUV422PS, YUV422PH).
+ *   The SOURCE is ONE buffer of blocks, addressed exactly as the v210 side of jinc_filter_process_device_v210 (the field table is
+ *   there): block b of row y of frame n lies at src + n * src_frame_stride + y * src_pitch + 16 * b, and a row of `width` luma
+ *   samples is jinc_v210_row_bytes(width) bytes.  Bits 30 - 31 of every word, the fields of a partial last block beyond `width`
+ *   and everything behind the row's blocks (the conventional 128-byte padding included) are ignored whatever they hold.  The
+ *   source is never written.  src_frame_stride is read only for nframes > 1.
+ *   DESTINATION and result are as for jinc_filter_process_device_widened_packed10, with planes Y, U = Cb, V = Cr.
+ * JINC_ERR_INVALID_ARG, each with a message of its own, before the null checks of the plane arrays, before the device check and
+ * before anything is queued: an integer filter; a float filter of another shape (four components, no or another sub-sampling, a
+ * single plane); a destination step outside 1 .. 4; a source base, a source pitch or (with nframes > 1) a source frame stride
+ * that is no multiple of 4; a source pitch below jinc_v210_row_bytes(width).  Then null arguments, nframes and frame strides as
+ * for jinc_filter_process_device_shifted.  Base, pitch and frame stride that are all multiples of 16 get one 16-byte load per
+ * block, others four dwords.
+ * Stand-ins as above.  1080p v210 into planar fp32: rows of 7680 and 3840 bytes, (7680 + 2 x 3840) x 1080 = 16 588 800 bytes a
+ * frame, floor(1 073 741 824 / 16 588 800) = 64 frames under the 1 GiB default (a call of 128 runs as 64 + 64); into planar
+ * binary16 the chroma rows of 960 x 2 = 1920 bytes are padded to 2048: (3840 + 2 x 2048) x 1080 = 8 570 880 bytes, 125 frames
+ * (125 + 3). */
+JINC_API int jinc_filter_process_device_widened_v210(jinc_filter *f, const void *src, int src_pitch, size_t src_frame_stride,
+                                                     void *const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
+                                                     const size_t dst_frame_stride[4], int nframes, void *hip_stream);
 
 /* The field offsets of a named 10:10:10:2 word in the library's plane order, and the fill that sets every spare bit (an opaque
  * pixel); opaque_fill may be NULL.  Needs no device.  Names match without regard to case; an unknown one is
