@@ -27,7 +27,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JINC_LIB") or os.path.join(_HERE, "lib", "libjincresize_hip.so")  # JINC_LIB: A/B runs against another build
 SIMD_ORDER_ISA_PATH = os.path.join(_HERE, "lib", "kernel_simdorder-gfx950.s")  # the one unit with (explicit) fused multiply-adds
-ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_interleave", "kernel_widen", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
+ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_interleave", "kernel_widen", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "bf16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
                        "kernel_quasi_exact_fs9", "kernel_quasi_lane_fs7", "kernel_quasi_lane_fs9")]
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip.h")
 TEST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip_test.h")  # introspection, knobs, hooks
@@ -77,7 +77,7 @@ ARG_BITS = {"src_left": 1 << 0, "src_top": 1 << 1, "src_width": 1 << 2, "src_hei
             "quant_y": 1 << 5, "tap": 1 << 6, "blur": 1 << 7, "cplace": 1 << 8, "threads": 1 << 9, "opt": 1 << 10,
             "initial_capacity": 1 << 11, "initial_factor": 1 << 12}
 
-EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_filter_create", "jinc_filter_create_ex", "jinc_batch_create_ex", "jinc_debug_convert_half", "jinc_filter_free", "jinc_filter_output_info",
+EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_filter_create", "jinc_filter_create_ex", "jinc_batch_create_ex", "jinc_debug_convert_half", "jinc_debug_convert_bfloat16", "jinc_filter_free", "jinc_filter_output_info",
            "jinc_filter_chroma_location", "jinc_filter_set_chroma_location_mode", "jinc_filter_get_frame", "jinc_filter_process_device", "jinc_filter_sync",
            "jinc_alias_args", "jinc_filter_num_tables", "jinc_filter_plan_info", "jinc_filter_plan_pixel",
            "jinc_filter_plan_dump", "jinc_filter_plan_runs", "jinc_filter_plan_set", "jinc_filter_lut", "jinc_filter_set_kernel_mode", "jinc_filter_set_border_strips", "jinc_filter_interior_kernel", "jinc_filter_last_kernel",
@@ -172,6 +172,7 @@ def lib():
         L.jinc_filter_last_kernel.restype = C.c_char_p
         L.jinc_debug_convert.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int]
         L.jinc_debug_convert_half.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.jinc_debug_convert_bfloat16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.jinc_filter_set_profiling.argtypes = [C.c_void_p, C.c_int]
         L.jinc_filter_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                                C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -477,9 +478,21 @@ def debug_convert_half(sums: np.ndarray, device: int = 0) -> np.ndarray:
     return out.view(np.float16)
 
 
+def debug_convert_bfloat16(sums: np.ndarray, device: int = 0) -> np.ndarray:
+    """The bfloat16 planes' fp32 -> bfloat16 store path applied to `sums` on the device (test hook); returns the bit patterns as
+    uint16 (numpy has no bfloat16 dtype)."""
+    sums = np.ascontiguousarray(sums, dtype=np.float32)
+    out = np.zeros(sums.shape, dtype=np.uint16)
+    rc = lib().jinc_debug_convert_bfloat16(sums.ctypes.data, out.ctypes.data, sums.size, device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return out
+
+
 # Sample types of jinc_filter_create_ex / jinc_batch_create_ex
 SAMPLE_DEFAULT = 0
 SAMPLE_FLOAT16 = 1
+SAMPLE_BFLOAT16 = 3  # (2 is not a sample type: jinc_filter_create_ex keeps refusing it)
 
 
 # ---- clip / format model (what an AviSynth+ host would provide) -----------------------------------
@@ -492,6 +505,7 @@ class Format:
     sub_h: int = 0
     rgb: bool = False
     half: bool = False  # IEEE binary16 samples (bits 16, 2 bytes): created with SAMPLE_FLOAT16; bits == 32 stays fp32
+    bfloat16: bool = False  # bfloat16 samples (bits 16, 2 bytes): created with SAMPLE_BFLOAT16; planes are uint16 bit patterns
 
     @property
     def sample_bytes(self) -> int:
@@ -499,7 +513,7 @@ class Format:
 
     @property
     def sample_type(self) -> int:
-        return SAMPLE_FLOAT16 if self.half else SAMPLE_DEFAULT
+        return SAMPLE_FLOAT16 if self.half else (SAMPLE_BFLOAT16 if self.bfloat16 else SAMPLE_DEFAULT)
 
     @property
     def dtype(self):
@@ -536,6 +550,13 @@ def _fmts() -> Dict[str, Format]:
         out[f"YUVA{fam}PH"] = Format(f"YUVA{fam}PH", 16, 4, sw, sh, half=True)
     out["RGBPH"] = Format("RGBPH", 16, 3, rgb=True, half=True)
     out["RGBAPH"] = Format("RGBAPH", 16, 4, rgb=True, half=True)
+    # bfloat16 planes (the upper halves of fp32 values; numpy has no such dtype: planes are np.uint16 holding the bit patterns)
+    out["YBF"] = Format("YBF", 16, 1, bfloat16=True)
+    for fam, sw, sh in (("420", 1, 1), ("422", 1, 0), ("444", 0, 0), ("411", 2, 0)):
+        out[f"YUV{fam}PBF"] = Format(f"YUV{fam}PBF", 16, 3, sw, sh, bfloat16=True)
+        out[f"YUVA{fam}PBF"] = Format(f"YUVA{fam}PBF", 16, 4, sw, sh, bfloat16=True)
+    out["RGBPBF"] = Format("RGBPBF", 16, 3, rgb=True, bfloat16=True)
+    out["RGBAPBF"] = Format("RGBAPBF", 16, 4, rgb=True, bfloat16=True)
     return out
 
 
@@ -881,12 +902,13 @@ class Filter:
 
     def process_device_widened(self, src_ptrs, src_pitches, src_steps, src_shifts, src_bits: int, src_strides, dst_ptrs, dst_pitches,
                                dst_steps, dst_strides, nframes: int, stream: int = 0) -> None:
-        """INTEGER device samples into this fp32 / binary16 filter (jinc_filter_process_device_widened): the source is addressed as in
+        """INTEGER device samples into this fp32 / binary16 / bfloat16 filter (jinc_filter_process_device_widened): the source is addressed as in
         process_device_shifted, its sample size comes from src_bits (8: bytes; 9 .. 16: 16-bit words) and a sample's value is
         (raw >> shift[i]) & ((1 << src_bits) - 1); the destination side is process_device_strided's on this filter.  The result is
         process_device's on dense planes of those values as float / half.  NV12 into YUV420PS: Y step 1, U = uv, V = uv + 1
         sample, both step 2, src_bits 8; P010 into YUV420PH / PS: the same with src_bits 10, shifts 6.  Half filters take
-        src_bits <= 11.  Steps, shifts and frame strides may be None."""
+        src_bits <= 11 and bfloat16 filters src_bits 8 only (NV12 into YUV420PBF, BGRA8 into RGBPBF): wider samples are not exact
+        in those types and are refused.  Steps, shifts and frame strides may be None."""
         n = self.fmt.planes
 
         def arr(kind, values):

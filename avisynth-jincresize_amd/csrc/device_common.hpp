@@ -31,13 +31,23 @@ namespace {
 // round-toward-zero conversion: it saturates at 65504 and rounds differently.)
 using half_t = _Float16;
 
-// Float-like samples (fp32 and binary16): no clamp, non-finite samples possible -- no zero-tap elision on frames that hold one.
+// bfloat16 planes (PlaneIO::sample_kind == kSampleBFloat16): a sample is the upper 16 bits of an fp32 value, so it widens with a
+// shift (no conversion instruction; exact for every pattern, subnormals, infinities and NaNs included), the fp32 chain is the float
+// planes' one, and the result narrows with round to nearest even (gfx950: v_cvt_pk_bf16_f32, two results per instruction): results
+// at or beyond 0x7f7f8000 in magnitude become +-inf, subnormals and the sign of zero are kept, a NaN stays a NaN, no clamp.
+using bf16_t = __bf16;
+
+// Float-like samples (fp32, binary16 and bfloat16): no clamp, non-finite samples possible -- no zero-tap elision on frames that
+// hold one.
 template <typename T>
-inline constexpr bool is_float_sample_v = std::is_same_v<T, float> || std::is_same_v<T, half_t>;
+inline constexpr bool is_float_sample_v = std::is_same_v<T, float> || std::is_same_v<T, half_t> || std::is_same_v<T, bf16_t>;
 
 template <typename T>
 __device__ __forceinline__ float to_float(T v) {
-    return static_cast<float>(v);
+    if constexpr (std::is_same_v<T, bf16_t>)
+        return __builtin_bit_cast(float, static_cast<uint32_t>(__builtin_bit_cast(uint16_t, v)) << 16);
+    else
+        return static_cast<float>(v);
 }
 
 // Bit 31 set when v is an infinity or a NaN (exponent field all ones: the biased field plus one carries into the sign bit);
@@ -48,6 +58,8 @@ __device__ __forceinline__ uint32_t nonfinite_bit(T v) {
         return (__builtin_bit_cast(uint32_t, v) & 0x7f800000u) + 0x00800000u;
     else if constexpr (std::is_same_v<T, half_t>)
         return ((static_cast<uint32_t>(__builtin_bit_cast(uint16_t, v)) & 0x7c00u) + 0x0400u) << 16;
+    else if constexpr (std::is_same_v<T, bf16_t>)
+        return ((static_cast<uint32_t>(__builtin_bit_cast(uint16_t, v)) & 0x7f80u) + 0x0080u) << 16;
     else
         return 0u;
 }
@@ -56,6 +68,20 @@ __device__ __forceinline__ uint16_t half_bits(float r) { return __builtin_bit_ca
 // The two binary16 samples of a dword (low half first) widened to fp32.
 __device__ __forceinline__ float half_lo(uint32_t w) { return static_cast<float>(__builtin_bit_cast(half_t, static_cast<uint16_t>(w))); }
 __device__ __forceinline__ float half_hi(uint32_t w) { return static_cast<float>(__builtin_bit_cast(half_t, static_cast<uint16_t>(w >> 16))); }
+// ... and the two bfloat16 samples of a dword: one shift, one mask.
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
+// The two 2-byte float samples of a dword, by type.
+template <typename T>
+__device__ __forceinline__ float float16_lo(uint32_t w) {
+    if constexpr (std::is_same_v<T, bf16_t>) return bf16_lo(w);
+    else return half_lo(w);
+}
+template <typename T>
+__device__ __forceinline__ float float16_hi(uint32_t w) {
+    if constexpr (std::is_same_v<T, bf16_t>) return bf16_hi(w);
+    else return half_hi(w);
+}
 
 // ref :581-582 -- clamp(result, 0, peak) then lrintf (round-half-even).  For every non-NaN input
 // v_med3_f32(r, 0, peak) equals the reference's "upper bound first, then lower" clamp; a NaN (only
@@ -83,11 +109,21 @@ __device__ __forceinline__ uint32_t round_pair_u16(float a, float b, float peak)
 __device__ __forceinline__ uint32_t round_pair_f16(float a, float b) {
     return static_cast<uint32_t>(half_bits(a)) | (static_cast<uint32_t>(half_bits(b)) << 16);
 }
+// bfloat16: both halves from ONE v_cvt_pk_bf16_f32 (the vector conversion selects it; two scalar casts cost a shift more).
+typedef float f32x2_cvt __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_cvt __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t round_pair_bf16(float a, float b) {
+    const f32x2_cvt v = {a, b};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_cvt));
+}
+__device__ __forceinline__ uint16_t bf16_bits(float r) { return __builtin_bit_cast(uint16_t, static_cast<bf16_t>(r)); }
 // A pair of samples of type T packed into one dword (2-byte samples only).
 template <typename T>
 __device__ __forceinline__ uint32_t round_pair16(float a, float b, float peak) {
     if constexpr (std::is_same_v<T, half_t>)
         return round_pair_f16(a, b);
+    else if constexpr (std::is_same_v<T, bf16_t>)
+        return round_pair_bf16(a, b);
     else
         return round_pair_u16(a, b, peak);
 }
@@ -98,6 +134,8 @@ __device__ __forceinline__ T convert_sample(float r, float peak) {
         return r;
     else if constexpr (std::is_same_v<T, half_t>)
         return static_cast<half_t>(r);
+    else if constexpr (std::is_same_v<T, bf16_t>)
+        return static_cast<bf16_t>(r);
     else if constexpr (std::is_same_v<T, uint8_t>)
         return static_cast<uint8_t>(round_sample_u8(r));
     else
@@ -121,6 +159,8 @@ __device__ __forceinline__ void store_sample_buf(BufferRsrc rsrc, uint32_t voffs
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, r), rsrc, voffset, soffset, 0);
     else if constexpr (std::is_same_v<T, half_t>)
         __builtin_amdgcn_raw_buffer_store_b16(half_bits(r), rsrc, voffset, soffset, 0);
+    else if constexpr (std::is_same_v<T, bf16_t>)
+        __builtin_amdgcn_raw_buffer_store_b16(bf16_bits(r), rsrc, voffset, soffset, 0);
     else if constexpr (std::is_same_v<T, uint8_t>)
         __builtin_amdgcn_raw_buffer_store_b8(static_cast<uint8_t>(round_sample_u8(r)), rsrc, voffset, soffset, 0);
     else

@@ -193,12 +193,12 @@ struct Choice {
     const size_t* src_fs;
     const int nframes;
     const int sb;
-    const int rule_sb;  // sample size the rules see: half planes take the decisions of fp32 planes of the same geometry
+    const int rule_sb;  // sample size the rules see: half and bfloat16 planes take the decisions of fp32 planes of the same geometry
     double call_samples = 0.0;  // output samples of the whole call
 
     Choice(const jinc_filter& filter, const int src_pitch_[4], const size_t src_fs_[4], int nframes_)
         : f(filter), src_pitch(src_pitch_), src_fs(src_fs_), nframes(nframes_), sb(filter.vi_in.component_size),
-          rule_sb(filter.half ? 4 : filter.vi_in.component_size) {
+          rule_sb(filter.float_samples() ? 4 : filter.vi_in.component_size) {
         for (int i = 0; i < f.planecount; ++i) {
             const DeviceTable& t = f.tables[f.table_of_plane(i)];
             call_samples += static_cast<double>(t.plan.dst_w) * t.plan.dst_h;
@@ -441,7 +441,7 @@ void launch_plane(jinc_filter& f, const Choice& c, int i, const void* const src[
     io.nframes = nframes;
     if (pair) io.src_frame_stride = pair->src_stride, io.dst_frame_stride = pair->dst_stride, io.nframes = 2;
     io.sample_bytes = sb;
-    io.sample_kind = f.half ? jinc::kSampleHalf : 0;
+    io.sample_kind = f.sample_kind();
     io.peak = f.peak;
     auto timed = [&](std::vector<EventPair>& sink, hipStream_t s, const char* what, auto&& launch) {
         EventPair ev;
@@ -1266,7 +1266,7 @@ void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[
         });
 }
 
-// ---- jinc_filter_process_device_widened: integer device frames into an fp32 / binary16 filter (NV12, P010, Y210, BGRA8, planar) ----
+// ---- jinc_filter_process_device_widened: integer device frames into an fp32 / binary16 / bfloat16 filter (NV12, P010, Y210, BGRA8, planar) ----
 // The split that joins a decoder's surface to the float filters: EVERY source plane, dense ones included, takes a dense stand-in of
 // the filter's sample type, filled by widen_samples_kernel (kernel_widen.hip) with float((raw >> shift) & mask) -- exact.  From
 // there the call is enqueue on float planes, so the result is jinc_filter_process_device's on planes of those values by
@@ -1361,7 +1361,7 @@ void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pit
             int launches = 0;
             for (int step = 1; step <= 4; ++step)
                 if (widen[step].ngroups) {
-                    hip_check(static_cast<hipError_t>(jinc::launch_widen_samples(widen[step], static_cast<int>(src_bytes), step, static_cast<int>(sb), n, stream)), "widen launch");
+                    hip_check(static_cast<hipError_t>(jinc::launch_widen_samples(widen[step], static_cast<int>(src_bytes), step, static_cast<int>(sb), f.sample_kind(), n, stream)), "widen launch");
                     ++launches;
                 }
             return launches;

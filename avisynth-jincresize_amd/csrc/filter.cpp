@@ -103,11 +103,14 @@ int jinc_filter_create_ex(const jinc_video_info* vi, const jinc_args* args, int 
     std::unique_ptr<jinc_filter> f(new (std::nothrow) jinc_filter());
     if (!f) return fail(JINC_ERR_NOMEM, "JincResize: out of memory.");
     int rc = guarded([&] {
-        if (sample_type != JINC_SAMPLE_DEFAULT && sample_type != JINC_SAMPLE_FLOAT16)
-            throw ArgError("JincResize: sample type must be JINC_SAMPLE_DEFAULT or JINC_SAMPLE_FLOAT16.");
+        if (sample_type != JINC_SAMPLE_DEFAULT && sample_type != JINC_SAMPLE_FLOAT16 && sample_type != JINC_SAMPLE_BFLOAT16)
+            throw ArgError("JincResize: sample type must be JINC_SAMPLE_DEFAULT, JINC_SAMPLE_FLOAT16 or JINC_SAMPLE_BFLOAT16.");
         if (sample_type == JINC_SAMPLE_FLOAT16 && (vi->bits_per_component != 16 || vi->component_size != 2))
             throw ArgError("JincResize: half-precision float clips must have 16 bits per component and 2-byte samples.");
+        if (sample_type == JINC_SAMPLE_BFLOAT16 && (vi->bits_per_component != 16 || vi->component_size != 2))
+            throw ArgError("JincResize: bfloat16 clips must have 16 bits per component and 2-byte samples.");
         f->half = sample_type == JINC_SAMPLE_FLOAT16;
+        f->bf16 = sample_type == JINC_SAMPLE_BFLOAT16;
         configure(*f, *vi, *args);
         if (device >= 0) init_device(*f, device);
     });
@@ -263,7 +266,7 @@ int jinc_filter_process_device_shifted(jinc_filter* f, const void* const src[4],
         for (int i = 0; step && i < f->planecount; ++i)
             if (step[i] < 1 || step[i] > 4) return fail(JINC_ERR_INVALID_ARG, "JincResize: sample step must be in 1..4.");
     // A shift is the padding below a sample in its word: integer samples narrower than their container (10 / 12 / 14 bits in 16).
-    const bool integer = !f->half && f->vi_in.bits_per_component <= 16;
+    const bool integer = !f->float_samples();  // (binary16 and bfloat16 fill their 16 bits)
     const int spare = integer ? 8 * f->vi_in.component_size - f->vi_in.bits_per_component : 0;
     for (const int* shift : {src_sample_shift, dst_sample_shift})
         for (int i = 0; shift && i < f->planecount; ++i) {
@@ -292,7 +295,7 @@ int jinc_filter_process_device_packed10(jinc_filter* f, const void* const src[4]
     // the filter and the offsets first (they need no device), then the checks of jinc_filter_process_device_shifted in its order
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (src_field_offset || dst_field_offset) {
-        if (f->planecount != 3 || f->subsampled || f->half || f->vi_in.component_size != 2 || f->vi_in.bits_per_component != 10)
+        if (f->planecount != 3 || f->subsampled || f->float_samples() || f->vi_in.component_size != 2 || f->vi_in.bits_per_component != 10)
             return fail(JINC_ERR_INVALID_ARG, "JincResize: packed 10:10:10:2 words need a filter with three 10-bit components in 16-bit samples and no "
                                               "sub-sampling (YUV444P10, RGBP10).");
         for (const int* o : {src_field_offset, dst_field_offset}) {
@@ -322,7 +325,7 @@ int jinc_filter_process_device_v210(jinc_filter* f, const void* const src[4], co
     // the filter first (it needs no device), then the checks of jinc_filter_process_device_shifted in its order
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (src_is_v210 || dst_is_v210) {
-        if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0 || f->half || f->vi_in.component_size != 2 ||
+        if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0 || f->float_samples() || f->vi_in.component_size != 2 ||
             f->vi_in.bits_per_component != 10)
             return fail(JINC_ERR_INVALID_ARG, "JincResize: v210 blocks need a filter with three 10-bit components in 16-bit samples and 4:2:2 "
                                               "sub-sampling (YUV422P10).");
@@ -349,12 +352,15 @@ int jinc_filter_process_device_widened(jinc_filter* f, const void* const src[4],
     // of jinc_filter_process_device_shifted in its order
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (!f->float_samples())
-        return fail(JINC_ERR_INVALID_ARG, "JincResize: widened integer sources need an fp32 or binary16 filter; this filter has " +
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: widened integer sources need an fp32 or binary16 filter, or a bfloat16 filter for 8-bit sources; this filter has " +
                                               std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_shifted).");
     if (src_bits < 8 || src_bits > 16)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: src_bits must be in 8..16 (got " + std::to_string(src_bits) + ").");
     if (f->half && src_bits > 11)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: " + std::to_string(src_bits) + "-bit samples are not exact in binary16 (at most 11 bits): "
+                                              "widen them into an fp32 filter.");
+    if (f->bf16 && src_bits > 8)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: " + std::to_string(src_bits) + "-bit samples are not exact in bfloat16 (at most 8 bits): "
                                               "widen them into an fp32 filter.");
     for (const int* step : {src_sample_step, dst_sample_step})
         for (int i = 0; step && i < f->planecount; ++i)
@@ -401,6 +407,9 @@ int jinc_filter_process_device_widened_packed10(jinc_filter* f, const void* src,
     if (!f->float_samples())
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words need an fp32 or binary16 filter; this filter has " +
                                               std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_packed10).");
+    if (f->bf16)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words do not go into a bfloat16 filter: 10-bit fields are not exact in "
+                                          "bfloat16 (at most 8 bits); widen them into an fp32 or binary16 filter.");
     if (f->planecount != 3 || f->subsampled)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words need a float filter with three components and no sub-sampling "
                                           "(YUV444PS, YUV444PH, RGBPS, RGBPH); this filter has " + std::to_string(f->planecount) + " component(s), sub_w " +
@@ -439,6 +448,9 @@ int jinc_filter_process_device_widened_v210(jinc_filter* f, const void* src, int
     if (!f->float_samples())
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened v210 blocks need an fp32 or binary16 filter; this filter has " +
                                               std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_v210).");
+    if (f->bf16)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: widened v210 blocks do not go into a bfloat16 filter: 10-bit samples are not exact in bfloat16 "
+                                          "(at most 8 bits); widen them into an fp32 or binary16 filter.");
     if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened v210 blocks need a float filter with three components and 4:2:2 sub-sampling "
                                           "(YUV422PS, YUV422PH: sub_w 1, sub_h 0); this filter has " + std::to_string(f->planecount) + " component(s), sub_w " +
@@ -671,6 +683,23 @@ int jinc_debug_convert_half(const float* sums, uint16_t* out, int n, int device)
     });
 }
 
+int jinc_debug_convert_bfloat16(const float* sums, uint16_t* out, int n, int device) {
+    if (!sums || !out || n < 0) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        float* d_in = nullptr;
+        uint16_t* d_out = nullptr;
+        hip_check(hipMalloc(&d_in, sizeof(float) * (n + 1)), "hipMalloc");
+        hip_check(hipMalloc(&d_out, sizeof(uint16_t) * (n + 1)), "hipMalloc");
+        bounce_upload(d_in, sums, sizeof(float) * n, "upload of the sums");
+        hip_check(static_cast<hipError_t>(jinc::launch_debug_convert_bfloat16(d_in, d_out, n, nullptr)), "convert launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bounce_download(out, d_out, sizeof(uint16_t) * n, "download of the samples");
+        (void)hipFree(d_in);
+        (void)hipFree(d_out);
+    });
+}
+
 int jinc_debug_convert(const float* sums, void* out, int n, int sample_bytes, float peak, int device) {
     if (!sums || !out || n < 0 || (sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4))
         return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
@@ -764,6 +793,8 @@ int jinc_filter_set_simd_order(jinc_filter* f, int order) {
     if (!f || order < 0 || order > 3) return fail(JINC_ERR_INVALID_ARG, "JincResize: SIMD order must be 0..3.");
     if (f->half && order != 0)
         return fail(JINC_ERR_UNSUPPORTED, "JincResize: SIMD-order modes do not exist for half-precision float clips (the reference has no half path).");
+    if (f->bf16 && order != 0)
+        return fail(JINC_ERR_UNSUPPORTED, "JincResize: SIMD-order modes do not exist for bfloat16 clips (the reference has no bfloat16 path).");
     f->simd_order = order;
     return JINC_OK;
 }

@@ -92,7 +92,7 @@ void configure(jinc_filter& f, const jinc_video_info& vi, const jinc_args& a) {
     f.vi_out.width = target_width;
     f.vi_out.height = target_height;
     f.cplace = cplace;
-    f.peak = (vi.bits_per_component <= 16 && !f.half) ? static_cast<float>((1 << vi.bits_per_component) - 1) : 0.f;  // (half: no clamp)
+    f.peak = (vi.bits_per_component <= 16 && !f.half && !f.bf16) ? static_cast<float>((1 << vi.bits_per_component) - 1) : 0.f;  // (half, bfloat16: no clamp)
     f.planecount = vi.num_components;
     const double radius = jinc::jinc_radius(tap);
     jinc::build_lut(f.lut, radius, blur);

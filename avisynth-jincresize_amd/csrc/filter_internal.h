@@ -203,8 +203,10 @@ struct jinc_filter {
     int chroma_location_mode = 0;        // jinc_filter_set_chroma_location_mode
     float peak = 0.f;
     bool half = false;  // JINC_SAMPLE_FLOAT16: IEEE binary16 samples (component_size 2); float planes' semantics
-    // Float-like samples (fp32 or binary16): no clamp, and the trimmed support only on frames whose samples are all finite.
-    bool float_samples() const { return half || vi_in.component_size == 4; }
+    bool bf16 = false;  // JINC_SAMPLE_BFLOAT16: the upper 16 bits of fp32 samples (component_size 2); float planes' semantics
+    // Float-like samples (fp32, binary16 or bfloat16): no clamp, and the trimmed support only on frames whose samples are all finite.
+    bool float_samples() const { return half || bf16 || vi_in.component_size == 4; }
+    int sample_kind() const { return half ? jinc::kSampleHalf : (bf16 ? jinc::kSampleBFloat16 : 0); }  // PlaneIO::sample_kind
     int planecount = 0;
     bool subsampled = false;
     jinc::JincLut lut;

@@ -204,6 +204,7 @@ int launch_colpair(const ColPairArgs& args, const PlaneIO& io, void* stream) {
         case 1: return launch_colpair_t<uint8_t>(args, io, s);
         case 2:
             if (io.sample_kind == kSampleHalf) return launch_colpair_t<half_t>(args, io, s);
+            if (io.sample_kind == kSampleBFloat16) return launch_colpair_t<bf16_t>(args, io, s);
             return launch_colpair_t<uint16_t>(args, io, s);
         default: return launch_colpair_t<float>(args, io, s);
     }

@@ -152,6 +152,7 @@ int launch_colstrip(const ColStripArgs& args, const PlaneIO& io, void* stream) {
         case 1: return launch_colstrip_t<uint8_t>(args, io, s);
         case 2:
             if (io.sample_kind == kSampleHalf) return launch_colstrip_t<half_t>(args, io, s);
+            if (io.sample_kind == kSampleBFloat16) return launch_colstrip_t<bf16_t>(args, io, s);
             return launch_colstrip_t<uint16_t>(args, io, s);
         default: return launch_colstrip_t<float>(args, io, s);
     }

@@ -25,6 +25,7 @@ int launch_direct_mode(const DirectArgs& args, const PlaneIO& io, hipStream_t s)
         case 1: return launch_direct_sx<uint8_t, MODE>(args, io, s);
         case 2:
             if (io.sample_kind == kSampleHalf) return launch_direct_sx<half_t, MODE>(args, io, s);
+            if (io.sample_kind == kSampleBFloat16) return launch_direct_sx<bf16_t, MODE>(args, io, s);
             return launch_direct_sx<uint16_t, MODE>(args, io, s);
         default: return launch_direct_sx<float, MODE>(args, io, s);
     }
@@ -90,6 +91,7 @@ int launch_direct(const DirectArgs& args, const PlaneIO& io, void* stream) {
         case 1: JINC_WALK_BY_SX(u8)
         case 2:
             if (io.sample_kind == kSampleHalf) JINC_WALK_BY_SX(f16)
+            if (io.sample_kind == kSampleBFloat16) JINC_WALK_BY_SX(bf16)
             JINC_WALK_BY_SX(u16)
         default: JINC_WALK_BY_SX(f32)
     }
@@ -113,6 +115,7 @@ int launch_direct_runs(const DirectArgs& args, const PlaneIO& io, void* stream) 
         case 1: JINC_RUNS_SX(u8)
         case 2:
             if (io.sample_kind == kSampleHalf) JINC_RUNS_SX(f16)
+            if (io.sample_kind == kSampleBFloat16) JINC_RUNS_SX(bf16)
             JINC_RUNS_SX(u16)
         default: JINC_RUNS_SX(f32)
     }

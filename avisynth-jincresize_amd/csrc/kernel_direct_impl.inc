@@ -116,6 +116,8 @@ __device__ __forceinline__ void convert_segment(const uint32_t (&raw)[RW], float
             seg[i] = static_cast<float>((raw[b / 4] >> (8 * (b % 4))) & 0xffu);  // v_cvt_f32_ubyteN
         else if constexpr (std::is_same_v<T, half_t>)
             seg[i] = (b % 4) ? half_hi(raw[b / 4]) : half_lo(raw[b / 4]);
+        else if constexpr (std::is_same_v<T, bf16_t>)
+            seg[i] = (b % 4) ? bf16_hi(raw[b / 4]) : bf16_lo(raw[b / 4]);  // a mask or a shift, no conversion
         else if constexpr (sizeof(T) == 2)
             seg[i] = static_cast<float>((raw[b / 4] >> (8 * (b % 4))) & 0xffffu);  // SDWA word select
         else

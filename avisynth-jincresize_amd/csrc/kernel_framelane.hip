@@ -447,6 +447,7 @@ int launch_framelane(const FrameLaneArgs& args, void* stream) {
         case 1: return launch_fl_fs<uint8_t>(args, s);
         case 2:
             if (args.io.sample_kind == kSampleHalf) return launch_fl_fs<half_t>(args, s);
+            if (args.io.sample_kind == kSampleBFloat16) return launch_fl_fs<bf16_t>(args, s);
             return launch_fl_fs<uint16_t>(args, s);
         default: return launch_fl_fs<float>(args, s);
     }

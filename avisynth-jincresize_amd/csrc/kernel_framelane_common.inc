@@ -18,6 +18,10 @@ struct FlPack<half_t> {
     using type = uint2;
 };
 template <>
+struct FlPack<bf16_t> {
+    using type = uint2;
+};
+template <>
 struct FlPack<float> {
     using type = float4;
 };
@@ -36,6 +40,8 @@ __device__ __forceinline__ typename FlPack<T>::type fl_pack(const float (&r)[4],
         return w;
     } else if constexpr (std::is_same_v<T, half_t>) {
         return make_uint2(round_pair_f16(r[0], r[1]), round_pair_f16(r[2], r[3]));
+    } else if constexpr (std::is_same_v<T, bf16_t>) {
+        return make_uint2(round_pair_bf16(r[0], r[1]), round_pair_bf16(r[2], r[3]));
     } else {
         return make_float4(r[0], r[1], r[2], r[3]);
     }

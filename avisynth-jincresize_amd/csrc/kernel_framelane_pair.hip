@@ -44,6 +44,10 @@ __device__ __forceinline__ f32x2 flp_load(const char* p) {
         const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
         r.x = half_lo(v);
         r.y = half_hi(v);
+    } else if constexpr (std::is_same_v<T, bf16_t>) {
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
+        r.x = bf16_lo(v);
+        r.y = bf16_hi(v);
     } else {
         r = *reinterpret_cast<const f32x2*>(p);
     }
@@ -301,6 +305,7 @@ int launch_framelane_pair(const FrameLaneArgs& args, void* stream) {
         case 1: return launch_flp_fs<uint8_t>(args, s);
         case 2:
             if (args.io.sample_kind == kSampleHalf) return launch_flp_fs<half_t>(args, s);
+            if (args.io.sample_kind == kSampleBFloat16) return launch_flp_fs<bf16_t>(args, s);
             return launch_flp_fs<uint16_t>(args, s);
         default: return launch_flp_fs<float>(args, s);
     }

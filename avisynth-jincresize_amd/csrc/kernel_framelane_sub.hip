@@ -295,6 +295,7 @@ int launch_framelane_sub(const FrameLaneArgs& args, void* stream) {
         case 1: return launch_sub_fs<uint8_t>(args, s);
         case 2:
             if (args.io.sample_kind == kSampleHalf) return launch_sub_fs<half_t>(args, s);
+            if (args.io.sample_kind == kSampleBFloat16) return launch_sub_fs<bf16_t>(args, s);
             return launch_sub_fs<uint16_t>(args, s);
         default: return launch_sub_fs<float>(args, s);
     }

@@ -353,6 +353,13 @@ int launch_debug_convert_half(const float* in, uint16_t* out, int n, void* strea
     return static_cast<int>(hipGetLastError());
 }
 
+int launch_debug_convert_bfloat16(const float* in, uint16_t* out, int n, void* stream) {
+    if (n <= 0) return 0;
+    const dim3 grid((n + 255) / 256), block(256);
+    hipLaunchKernelGGL(convert_kernel<bf16_t>, grid, block, 0, static_cast<hipStream_t>(stream), in, reinterpret_cast<bf16_t*>(out), n, 0.f);
+    return static_cast<int>(hipGetLastError());
+}
+
 int launch_gather(const DevicePlan& plan, const PlaneIO& io, const RectList& rects, void* stream) {
     GatherArgs ga;
     ga.plan = plan;
@@ -401,6 +408,7 @@ int launch_gather(const DevicePlan& plan, const PlaneIO& io, const RectList& rec
         case 1: return launch_gather_fs<uint8_t>(ga, total, s);
         case 2:
             if (io.sample_kind == kSampleHalf) return launch_gather_fs<half_t>(ga, total, s);
+            if (io.sample_kind == kSampleBFloat16) return launch_gather_fs<bf16_t>(ga, total, s);
             return launch_gather_fs<uint16_t>(ga, total, s);
         default: return launch_gather_fs<float>(ga, total, s);
     }

@@ -2222,6 +2222,7 @@ int launch_periodic(const PeriodicArgs& args, int fs, const PlaneIO& io, void* s
         case 1: return launch_periodic_fs<uint8_t>(args, fs, io, s, variant);
         case 2:
             if (io.sample_kind == kSampleHalf) return launch_periodic_fs<half_t>(args, fs, io, s, variant);
+            if (io.sample_kind == kSampleBFloat16) return launch_periodic_fs<bf16_t>(args, fs, io, s, variant);
             return launch_periodic_fs<uint16_t>(args, fs, io, s, variant);
         default: return launch_periodic_fs<float>(args, fs, io, s, variant);
     }

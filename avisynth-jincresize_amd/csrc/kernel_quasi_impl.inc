@@ -275,6 +275,7 @@ int JINC_QUASI_ENTRY(const QuasiArgs& args, const PlaneIO& io, void* stream) {
         case 1: return launch_quasi_sx<uint8_t, JINC_QUASI_FS>(args, io, s);
         case 2:
             if (io.sample_kind == kSampleHalf) return launch_quasi_sx<half_t, JINC_QUASI_FS>(args, io, s);
+            if (io.sample_kind == kSampleBFloat16) return launch_quasi_sx<bf16_t, JINC_QUASI_FS>(args, io, s);
             return launch_quasi_sx<uint16_t, JINC_QUASI_FS>(args, io, s);
         default: return launch_quasi_sx<float, JINC_QUASI_FS>(args, io, s);
     }

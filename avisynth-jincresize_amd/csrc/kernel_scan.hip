@@ -1,4 +1,4 @@
-// kernel_scan.hip -- does a batch of float (fp32 or binary16) planes hold nothing but finite samples?
+// kernel_scan.hip -- does a batch of float (fp32, binary16 or bfloat16) planes hold nothing but finite samples?
 //
 // The periodic kernels may run float planes on the TRIMMED support (device_plan.cpp trim_periodic) only where every source
 // sample is finite: a tap whose coefficient is 0.0f contributes sample * 0 = +-0 and may be left out -- unless the sample
@@ -14,14 +14,16 @@ namespace {
 constexpr int kScanThreads = 256;
 constexpr int kScanRowsPerBlock = 8;
 
-// Sample of a float plane as its bits: fp32 (W = uint32_t) or binary16 (W = uint16_t, PlaneIO::sample_kind == kSampleHalf).
-template <typename W>
+// Sample of a float plane as its bits, W, and the exponent field of its type, EXP: fp32 (uint32_t, 0x7f800000), binary16 (uint16_t,
+// 0x7c00: PlaneIO::sample_kind == kSampleHalf) or bfloat16 (uint16_t, 0x7f80: kSampleBFloat16) -- the size alone does not tell the
+// two 16-bit types apart.
+constexpr uint32_t kExpFloat = 0x7f800000u, kExpHalf = 0x7c00u, kExpBFloat16 = 0x7f80u;
+template <typename W, uint32_t EXP>
 __device__ __forceinline__ uint32_t nonfinite_sample(W v) {
-    constexpr uint32_t kExp = sizeof(W) == 4 ? 0x7f800000u : 0x7c00u;  // exponent all ones: infinity or NaN
-    return (static_cast<uint32_t>(v) & kExp) == kExp ? 1u : 0u;
+    return (static_cast<uint32_t>(v) & EXP) == EXP ? 1u : 0u;  // exponent all ones: infinity or NaN
 }
 
-template <typename W>
+template <typename W, uint32_t EXP>
 __global__ __launch_bounds__(kScanThreads) void finite_scan_kernel(const char* __restrict__ base, uint32_t pitch, size_t frame_stride, int w,
                                                                    int h, uint32_t* __restrict__ flags) {
     const size_t frame = blockIdx.z;
@@ -32,14 +34,14 @@ __global__ __launch_bounds__(kScanThreads) void finite_scan_kernel(const char* _
         const int y = y0 + r;
         if (y >= h) break;
         const W* row = reinterpret_cast<const W*>(plane + static_cast<size_t>(y) * pitch);
-        for (int x = blockIdx.x * kScanThreads + threadIdx.x; x < w; x += gridDim.x * kScanThreads) bad |= nonfinite_sample(row[x]);
+        for (int x = blockIdx.x * kScanThreads + threadIdx.x; x < w; x += gridDim.x * kScanThreads) bad |= nonfinite_sample<W, EXP>(row[x]);
     }
     if (__builtin_amdgcn_ballot_w64(bad != 0) != 0 && (threadIdx.x & 63) == 0) flags[frame] = 1u;  // (every writer writes 1)
 }
 
 // The plane minus the rectangle [rx0, rx1) x [ry0, ry1): rows above and below it over the whole width, columns left and right of
 // it over its height.  A few thousand samples per frame: one workgroup per frame walks them.
-template <typename W>
+template <typename W, uint32_t EXP>
 __global__ __launch_bounds__(kScanThreads) void finite_scan_outside_kernel(const char* __restrict__ base, uint32_t pitch, size_t frame_stride, int w,
                                                                            int h, int rx0, int ry0, int rx1, int ry1,
                                                                            uint32_t* __restrict__ flags) {
@@ -47,7 +49,7 @@ __global__ __launch_bounds__(kScanThreads) void finite_scan_outside_kernel(const
     const char* plane = base + frame * frame_stride;
     uint32_t bad = 0;
     auto check = [&](int x, int y) {
-        bad |= nonfinite_sample(*reinterpret_cast<const W*>(plane + static_cast<size_t>(y) * pitch + static_cast<size_t>(x) * sizeof(W)));
+        bad |= nonfinite_sample<W, EXP>(*reinterpret_cast<const W*>(plane + static_cast<size_t>(y) * pitch + static_cast<size_t>(x) * sizeof(W)));
     };
     const int tid = blockIdx.x * kScanThreads + threadIdx.x, nthreads = gridDim.x * kScanThreads;
     const int rows_above = ry0, rows_below = h - ry1, cols_left = rx0, cols_right = w - rx1, mid = ry1 - ry0;
@@ -66,8 +68,10 @@ int launch_finite_scan(const PlaneIO& io, int w, int h, uint32_t* flags, void* s
     if (w <= 0 || h <= 0 || io.nframes <= 0) return 0;
     const int bx = std::max(1, std::min(8, (w + kScanThreads * 4 - 1) / (kScanThreads * 4)));
     dim3 grid(bx, (h + kScanRowsPerBlock - 1) / kScanRowsPerBlock, io.nframes);
-    hipLaunchKernelGGL(io.sample_kind == kSampleHalf ? finite_scan_kernel<uint16_t> : finite_scan_kernel<uint32_t>, grid, dim3(kScanThreads), 0,
-                       static_cast<hipStream_t>(stream),
+    const auto kernel = io.sample_kind == kSampleHalf       ? finite_scan_kernel<uint16_t, kExpHalf>
+                        : io.sample_kind == kSampleBFloat16 ? finite_scan_kernel<uint16_t, kExpBFloat16>
+                                                            : finite_scan_kernel<uint32_t, kExpFloat>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kScanThreads), 0, static_cast<hipStream_t>(stream),
                        static_cast<const char*>(io.src), static_cast<uint32_t>(io.src_pitch), io.src_frame_stride, w, h, flags);
     return static_cast<int>(hipGetLastError());
 }
@@ -79,7 +83,10 @@ int launch_finite_scan_outside(const PlaneIO& io, int w, int h, int rx0, int ry0
     const long long outside = static_cast<long long>(w) * h - static_cast<long long>(rx1 - rx0) * (ry1 - ry0);
     if (outside <= 0) return 0;
     const int bx = static_cast<int>(std::max<long long>(1, std::min<long long>(16, outside / (kScanThreads * 16))));
-    hipLaunchKernelGGL(io.sample_kind == kSampleHalf ? finite_scan_outside_kernel<uint16_t> : finite_scan_outside_kernel<uint32_t>,
+    const auto kernel = io.sample_kind == kSampleHalf       ? finite_scan_outside_kernel<uint16_t, kExpHalf>
+                        : io.sample_kind == kSampleBFloat16 ? finite_scan_outside_kernel<uint16_t, kExpBFloat16>
+                                                            : finite_scan_outside_kernel<uint32_t, kExpFloat>;
+    hipLaunchKernelGGL(kernel,
                        dim3(bx, 1, io.nframes), dim3(kScanThreads), 0, static_cast<hipStream_t>(stream),
                        static_cast<const char*>(io.src), static_cast<uint32_t>(io.src_pitch), io.src_frame_stride, w, h, rx0, ry0, rx1, ry1, flags);
     return static_cast<int>(hipGetLastError());

@@ -138,7 +138,7 @@ int launch_so_t(const DevicePlan& p, const PlaneIO& io, int order, float min_val
 
 int launch_simd_order(const DevicePlan& plan, const PlaneIO& io, int order, float min_val, void* stream) {
     if (io.nframes <= 0 || plan.dst_w <= 0 || plan.dst_h <= 0) return 0;
-    if (io.sample_kind == kSampleHalf) return static_cast<int>(hipErrorInvalidValue);  // (no half path in the reference's SIMD code)
+    if (io.sample_kind == kSampleHalf || io.sample_kind == kSampleBFloat16) return static_cast<int>(hipErrorInvalidValue);  // (no half or bfloat16 path in the reference's SIMD code)
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (io.sample_bytes) {
         case 1: return launch_so_t<uint8_t>(plan, io, order, min_val, s);

@@ -168,8 +168,8 @@ __global__ __launch_bounds__(kStripLanes) void ewa_strip_kernel(const StripArgs 
                         const u32x2 v = {round_sample(r[0], io.peak) | (round_sample(r[1], io.peak) << 16),
                                          round_sample(r[2], io.peak) | (round_sample(r[3], io.peak) << 16)};
                         __builtin_amdgcn_raw_buffer_store_b64(v, drsrc, xoff, soff, 0);
-                    } else if constexpr (std::is_same_v<T, half_t>) {
-                        const u32x2 v = {round_pair_f16(r[0], r[1]), round_pair_f16(r[2], r[3])};
+                    } else if constexpr (std::is_same_v<T, half_t> || std::is_same_v<T, bf16_t>) {
+                        const u32x2 v = {round_pair16<T>(r[0], r[1], io.peak), round_pair16<T>(r[2], r[3], io.peak)};
                         __builtin_amdgcn_raw_buffer_store_b64(v, drsrc, xoff, soff, 0);
                     } else {
                         __builtin_amdgcn_raw_buffer_store_b64(u32x2{__builtin_bit_cast(uint32_t, r[0]), __builtin_bit_cast(uint32_t, r[1])}, drsrc, xoff, soff, 0);
@@ -217,6 +217,7 @@ int launch_strip(const StripArgs& args, const PlaneIO& io, void* stream) {
         case 1: return launch_strip_t<uint8_t>(args, io, s);
         case 2:
             if (io.sample_kind == kSampleHalf) return launch_strip_t<half_t>(args, io, s);
+            if (io.sample_kind == kSampleBFloat16) return launch_strip_t<bf16_t>(args, io, s);
             return launch_strip_t<uint16_t>(args, io, s);
         default: return launch_strip_t<float>(args, io, s);
     }

@@ -1,9 +1,9 @@
-// kernel_widen.hip -- integer samples -> the dense fp32 / binary16 planes the float filters' kernels read, in front of
+// kernel_widen.hip -- integer samples -> the dense fp32 / binary16 / bfloat16 planes the float filters' kernels read, in front of
 // jinc_filter_process_device_widened (dispatch.cpp enqueue_widened): the planes of a decoder's NV12 / P010 / Y210 surface, packed
 // 8-bit RGB(A) or planar integer frames become the stand-ins of a float or half filter.  A split (kernel_interleave.hip) that WIDENS:
 // it picks channel c out of N interleaved samples, drops the bits below and above the sample, (raw >> shift[c]) & mask, and stores
 // the value converted exactly -- v_cvt_f32_ubyte0..3 on the bytes of a loaded dword, v_cvt_f32_u32 on words, v_cvt_f16_f32 on top
-// for binary16 planes (values up to 2047 only).  No arithmetic beyond that: what the resampling kernels compute from these planes is
+// for binary16 planes (values up to 2047 only), the upper half of the fp32 bits for bfloat16 planes (bytes only).  No arithmetic beyond that: what the resampling kernels compute from these planes is
 // what they compute from any float plane holding the same values.
 //
 // Shape, after split_samples_kernel: ONE launch covers every channel group and frame of a call (grid = row blocks x frames x groups;
@@ -31,30 +31,30 @@ namespace jinc {
 namespace {
 
 // Row blockIdx.x * 4 + wave of frame blockIdx.y of group blockIdx.z.
-template <int SB, int N, int OB>
+template <int SB, int N, int OB, int KIND>
 __global__ __launch_bounds__(256) void widen_samples_kernel(const WidenArgs a) {
     const WidenGroup& g = a.g[blockIdx.z];
     const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row < g.rows) widen::widen_row<SB, N, OB>(g, a.mask, blockIdx.y, row, threadIdx.x & 63u);
+    if (row < g.rows) widen::widen_row<SB, N, OB, KIND>(g, a.mask, blockIdx.y, row, threadIdx.x & 63u);
 }
 
-template <int SB, int N, int OB>
+template <int SB, int N, int OB, int KIND>
 int launch(const WidenArgs& a, int nframes, hipStream_t s) {
     uint32_t rows = 0;
     for (int k = 0; k < a.ngroups; ++k) rows = a.g[k].rows > rows ? a.g[k].rows : rows;
     if (a.ngroups <= 0 || nframes <= 0 || rows == 0) return hipSuccess;
     const dim3 grid((rows + 3) / 4, static_cast<uint32_t>(nframes), static_cast<uint32_t>(a.ngroups));
-    hipLaunchKernelGGL((widen_samples_kernel<SB, N, OB>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((widen_samples_kernel<SB, N, OB, KIND>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-template <int SB, int OB>
+template <int SB, int OB, int KIND = 0>
 int launch_by_step(const WidenArgs& a, int step, int nframes, hipStream_t s) {
     switch (step) {
-        case 1: return launch<SB, 1, OB>(a, nframes, s);
-        case 2: return launch<SB, 2, OB>(a, nframes, s);
-        case 3: return launch<SB, 3, OB>(a, nframes, s);
-        case 4: return launch<SB, 4, OB>(a, nframes, s);
+        case 1: return launch<SB, 1, OB, KIND>(a, nframes, s);
+        case 2: return launch<SB, 2, OB, KIND>(a, nframes, s);
+        case 3: return launch<SB, 3, OB, KIND>(a, nframes, s);
+        case 4: return launch<SB, 4, OB, KIND>(a, nframes, s);
     }
     return hipErrorInvalidValue;
 }
@@ -109,7 +109,7 @@ int launch_widen_v210(const V210Args& a, int out_bytes, int nframes, void* strea
     return hipGetLastError();
 }
 
-int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int nframes, void* stream) {
+int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int out_kind, int nframes, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (a.ngroups > 4) return hipErrorInvalidValue;
     for (int k = 0; k < a.ngroups; ++k) {
@@ -120,6 +120,10 @@ int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_by
             if (src_bytes == 1 && g.shift[c]) return hipErrorInvalidValue;  // (a byte takes no shift)
     }
     if (out_bytes == 2 && a.mask > 2047u) return hipErrorInvalidValue;  // (not exact in binary16)
+    if (out_kind == kSampleBFloat16) {  // bytes only: nine bits are not exact in bfloat16
+        if (out_bytes != 2 || src_bytes != 1) return hipErrorInvalidValue;
+        return launch_by_step<1, 2, kSampleBFloat16>(a, step, nframes, s);
+    }
     switch (src_bytes * 8 + out_bytes) {
         case 1 * 8 + 4: return launch_by_step<1, 4>(a, step, nframes, s);
         case 1 * 8 + 2: return launch_by_step<1, 2>(a, step, nframes, s);

@@ -25,6 +25,7 @@ struct DevicePlan {
 };
 
 constexpr int kSampleHalf = 1;
+constexpr int kSampleBFloat16 = 2;
 
 // One plane of a batch of frames, device pointers, pitches/strides in bytes.
 struct PlaneIO {
@@ -33,8 +34,8 @@ struct PlaneIO {
     int src_pitch = 0, dst_pitch = 0;
     size_t src_frame_stride = 0, dst_frame_stride = 0;
     int nframes = 1;
-    int sample_bytes = 1;  // 1: uint8, 2: uint16 or binary16 (sample_kind), 4: float
-    int sample_kind = 0;   // kSampleHalf: IEEE binary16 samples (sample_bytes 2); else integer (1, 2 bytes) or fp32 (4 bytes)
+    int sample_bytes = 1;  // 1: uint8, 2: uint16, binary16 or bfloat16 (sample_kind), 4: float
+    int sample_kind = 0;   // kSampleHalf: IEEE binary16, kSampleBFloat16: bfloat16 samples (sample_bytes 2); else integer (1, 2 bytes) or fp32 (4 bytes)
     float peak = 255.f;    // clamp ceiling of integer planes (ref JincResize.cpp:582, :793)
 };
 
@@ -353,6 +354,7 @@ int last_direct_shape();
 JINC_DECLARE_DIRECT_WALK(u8)
 JINC_DECLARE_DIRECT_WALK(u16)
 JINC_DECLARE_DIRECT_WALK(f16)
+JINC_DECLARE_DIRECT_WALK(bf16)
 JINC_DECLARE_DIRECT_WALK(f32)
 #undef JINC_DECLARE_DIRECT_WALK
 int launch_direct_row_strips(const DirectArgs& args, const PlaneIO& io, void* stream);
@@ -367,6 +369,7 @@ int launch_direct_runs(const DirectArgs& args, const PlaneIO& io, void* stream);
 JINC_DECLARE_DIRECT_RUNS(u8)
 JINC_DECLARE_DIRECT_RUNS(u16)
 JINC_DECLARE_DIRECT_RUNS(f16)
+JINC_DECLARE_DIRECT_RUNS(bf16)
 JINC_DECLARE_DIRECT_RUNS(f32)
 #undef JINC_DECLARE_DIRECT_RUNS
 
@@ -586,8 +589,9 @@ struct WidenArgs {
     uint32_t mask = 0xffu;  // (1 << src_bits) - 1
 };
 // One launch over every group and frame of `a`: src_bytes 1 or 2 (a byte takes no shift: mask 0xff, shifts 0); step 1 .. 4 (the
-// same for all groups of a launch); out_bytes 4 (fp32) or 2 (binary16: every value must be <= 2047 to be exact).
-int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int nframes, void* stream);
+// same for all groups of a launch); out_bytes 4 (fp32) or 2 (out_kind 0 / kSampleHalf: binary16, every value must be <= 2047 to be
+// exact; out_kind kSampleBFloat16: bfloat16, src_bytes 1 only -- nine bits are not exact).
+int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int out_kind, int nframes, void* stream);
 // 10:10:10:2 words / v210 blocks -> the three dense planes of an fp32 / binary16 filter (kernel_widen.hip, widen_fields_rows.h,
 // widen_v210_rows.h; jinc_filter_process_device_widened_packed10 / _v210).  The records are FieldArgs and V210Args as they are, read
 // with samples of out_bytes (4: fp32, 2: binary16) on the plane side: plane c holds float / binary16 of the 10-bit field value at
@@ -609,5 +613,7 @@ int launch_valu_pair_probe(float* out, int blocks, int iters, void* stream);
 int launch_debug_convert(const float* in, void* out, int n, int sample_bytes, float peak, void* stream);
 // ... the binary16 stores of half planes (both the plain and the buffer-store paths, and the packed pair)
 int launch_debug_convert_half(const float* in, uint16_t* out, int n, void* stream);
+// ... and the bfloat16 stores (the single conversion and the packed pair's)
+int launch_debug_convert_bfloat16(const float* in, uint16_t* out, int n, void* stream);
 
 }  // namespace jinc

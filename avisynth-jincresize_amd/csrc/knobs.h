@@ -40,6 +40,7 @@ template <> constexpr const char* type_name<unsigned char>() { return "unsigned 
 template <> constexpr const char* type_name<unsigned short>() { return "unsigned short"; }
 template <> constexpr const char* type_name<float>() { return "float"; }
 template <> constexpr const char* type_name<_Float16>() { return "_Float16"; }
+template <> constexpr const char* type_name<__bf16>() { return "__bf16"; }
 
 }  // namespace knobs
 }  // namespace jinc

@@ -2,9 +2,11 @@
 // as plain inline functions for host and device: a stand-alone host program runs exactly this code lane by lane against exactly
 // sized buffers (tests/host_sanitizer/widen_rows_main.cpp).
 //
-// Integer samples of SB bytes (1: a byte; 2: a little-endian 16-bit word), N per pixel, become fp32 (OB = 4) or binary16 (OB = 2)
-// samples of up to N dense planes: plane c holds float((raw >> shift[c]) & mask) of channel c.  The conversion is exact: every
-// integer below 2^24 is an fp32 value, every integer up to 2047 a binary16 value (dispatch refuses wider samples into half planes).
+// Integer samples of SB bytes (1: a byte; 2: a little-endian 16-bit word), N per pixel, become fp32 (OB = 4), binary16 (OB = 2) or
+// bfloat16 (OB = 2, KIND = kSampleBFloat16: the size no longer says which 16-bit type is meant) samples of up to N dense planes:
+// plane c holds float((raw >> shift[c]) & mask) of channel c.  The conversion is exact: every integer below 2^24 is an fp32 value,
+// every integer up to 2047 a binary16 value and every integer up to 256 a bfloat16 value (dispatch refuses wider samples into half
+// and bfloat16 planes; the bfloat16 form exists for bytes only).
 //
 // A lane owns 16 / SB whole pixels per step, as in split_samples_kernel: N 16-byte accesses on the source side (consecutive lanes,
 // consecutive addresses; 4 N dwords where base, pitch or frame stride is a multiple of 4 only) and, per given plane, OB / SB whole
@@ -84,10 +86,19 @@ JINC_WIDEN_HD uint32_t half_bits(float v) {
 #endif
 }
 
+// The 16-bit sample of an fp32 value that the type holds exactly: binary16, or bfloat16 -- the upper half of the fp32 bits, whose
+// lower half is zeros for an integer of at most 8 bits, so nothing is rounded.
+template <int KIND>
+JINC_WIDEN_HD uint32_t narrow_bits(float v) {
+    if constexpr (KIND == kSampleBFloat16) return float_bits(v) >> 16;
+    else return half_bits(v);
+}
+
 // Lane `lane` of the wave that owns row `row` of frame `frame` of group g.
-template <int SB, int N, int OB>
+template <int SB, int N, int OB, int KIND = 0>
 JINC_WIDEN_HD void widen_row(const WidenGroup& g, uint32_t mask, uint32_t frame, uint32_t row, uint32_t lane) {
     static_assert((SB == 1 || SB == 2) && N >= 1 && N <= 4 && (OB == 4 || OB == 2), "no such form");
+    static_assert(KIND == 0 || KIND == kSampleHalf || (KIND == kSampleBFloat16 && OB == 2 && SB == 1), "no such form");
     constexpr uint32_t P = 16 / SB;          // pixels a lane owns per step
     constexpr int kVectors = OB / SB;        // 16-byte vectors of P converted samples
     constexpr int kPerVector = 16 / OB;      // samples in one of them
@@ -108,7 +119,7 @@ JINC_WIDEN_HD void widen_row(const WidenGroup& g, uint32_t mask, uint32_t frame,
                 for (int k = 0; k < 4; ++k) {
                     const int p = v * kPerVector + (OB == 4 ? k : 2 * k);  // the pixel of dword k's (first) sample
                     if constexpr (OB == 4) o[k] = float_bits(value_at<SB>(in, p * N + c, sh, mask));
-                    else o[k] = half_bits(value_at<SB>(in, p * N + c, sh, mask)) | (half_bits(value_at<SB>(in, (p + 1) * N + c, sh, mask)) << 16);
+                    else o[k] = narrow_bits<KIND>(value_at<SB>(in, p * N + c, sh, mask)) | (narrow_bits<KIND>(value_at<SB>(in, (p + 1) * N + c, sh, mask)) << 16);
                 }
                 store16(out + 16 * v, o);
             }
@@ -123,7 +134,7 @@ JINC_WIDEN_HD void widen_row(const WidenGroup& g, uint32_t mask, uint32_t frame,
             else raw = reinterpret_cast<const uint16_t*>(packed)[static_cast<size_t>(x) * N + c];
             const float v = value_of<SB>(raw, g.shift[c], mask);
             if constexpr (OB == 4) reinterpret_cast<float*>(g.plane[c] + dense)[x] = v;
-            else reinterpret_cast<uint16_t*>(g.plane[c] + dense)[x] = static_cast<uint16_t>(half_bits(v));
+            else reinterpret_cast<uint16_t*>(g.plane[c] + dense)[x] = static_cast<uint16_t>(narrow_bits<KIND>(v));
         }
     }
 }

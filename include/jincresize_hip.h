@@ -142,13 +142,23 @@ JINC_API int jinc_filter_create(const jinc_video_info *vi, const jinc_args *args
  * that fp32 plane (same plan, same un-fused (ly, lx) chain, the trimmed support only on frames whose samples are all
  * finite), and it narrows to binary16 with round-to-nearest-even: |r| >= 65520 becomes an infinity, subnormal results
  * and the sign of zero are kept, nothing is clamped.  The reference has no half formats; its SIMD-order modes
- * (jinc_filter_set_simd_order 1 .. 3) do not exist for half filters. */
+ * (jinc_filter_set_simd_order 1 .. 3) do not exist for half filters.
+ * JINC_SAMPLE_BFLOAT16: bfloat16 planes, the 16-bit type networks on this hardware read; they too need bits_per_component
+ * == 16 and component_size == 2.  A bfloat16 sample is the upper 16 bits of an IEEE fp32 value, and a bfloat16 filter
+ *   1. widens: fp32 bits = sample bits << 16, exact for every pattern, subnormals, infinities and NaNs included;
+ *   2. computes exactly what the library computes for that fp32 plane (same plan, same un-fused (ly, lx) chain, the trimmed
+ *      support only on frames whose samples are all finite, nothing clamped);
+ *   3. narrows the fp32 result with round-to-nearest-even: results at or beyond 0x7f7f8000 in magnitude become +-inf,
+ *      subnormal results and the sign of zero are kept, and a NaN result is stored as a NaN (never as an infinity).
+ * The kernel choice is fp32's, as for half.  No SIMD-order modes either: a non-zero order is JINC_ERR_UNSUPPORTED. */
 #define JINC_SAMPLE_DEFAULT 0
 #define JINC_SAMPLE_FLOAT16 1
+#define JINC_SAMPLE_BFLOAT16 3 /* (2 is not a sample type: it stays refused, as before bfloat16 existed) */
 
 /* jinc_filter_create with a sample type: jinc_filter_create(...) is jinc_filter_create_ex(..., JINC_SAMPLE_DEFAULT, ...).
- * A sample type other than the two above, or JINC_SAMPLE_FLOAT16 with bits_per_component != 16 or component_size != 2,
- * is JINC_ERR_INVALID_ARG with a "JincResize: ..." message.  device = -1 builds a host-only plan, as for create. */
+ * A sample type other than the three above (2 included), or JINC_SAMPLE_FLOAT16 / JINC_SAMPLE_BFLOAT16 with bits_per_component != 16 or
+ * component_size != 2, is JINC_ERR_INVALID_ARG with a "JincResize: ..." message.  device = -1 builds a host-only plan, as for
+ * create. */
 JINC_API int jinc_filter_create_ex(const jinc_video_info *vi, const jinc_args *args, int sample_type, int device,
                                    jinc_filter **out, char *err, size_t err_len);
 
@@ -387,9 +397,11 @@ JINC_API size_t jinc_v210_row_bytes(int width);
  *   Since the integer filters convert every source sample to float before the multiply, the fp32 result is their sum in front of
  *   clamp and lrintf.
  *   A binary16 filter needs src_bits <= 11, so that every value is exact in binary16 (8-bit and 10-bit sources: NV12, P010, Y210);
- *   wider samples go into an fp32 filter.
+ *   wider samples go into an fp32 filter.  A bfloat16 filter (JINC_SAMPLE_BFLOAT16) needs src_bits == 8 for the same reason: its
+ *   eight significant bits hold every integer up to 256 and no 9-bit sample (NV12, BGRA8 and planar 8-bit frames; NV12 into
+ *   YUV420PBF is the first line above with a bfloat16 filter).
  * JINC_ERR_INVALID_ARG, each with a message of its own, before the device check and before anything is queued: an integer filter;
- * src_bits outside 8 .. 16; src_bits above 11 on a binary16 filter; a step outside 1 .. 4 (either side); a shift outside its range;
+ * src_bits outside 8 .. 16; src_bits above 11 on a binary16 filter; src_bits above 8 on a bfloat16 filter; a step outside 1 .. 4 (either side); a shift outside its range;
  * a source base not aligned to the source sample size; a source pitch below ((width - 1) * step + 1) * bytes of that plane.  Then
  * null arguments, nframes and frame strides as for jinc_filter_process_device_shifted.
  * EVERY source plane takes a dense float / half stand-in of the filter's own (the scratch of the strided call: same knob
@@ -421,10 +433,10 @@ JINC_API int jinc_filter_process_device_widened(jinc_filter *f, const void *cons
  *   The result is exactly what jinc_filter_process_device computes on that filter for dense planes holding the field values
  *   converted to the filter's sample type.  Ten bits are exact in fp32 and in binary16 alike, so half filters need no extra rule.
  *   The same plan, the same un-fused chain, the same finite scan (which finds nothing), and for half filters the same
- *   round-to-nearest-even narrowing of the fp32 sum.
+ *   round-to-nearest-even narrowing of the fp32 sum.  Ten bits are NOT exact in bfloat16: a bfloat16 filter is refused.
  * JINC_ERR_INVALID_ARG, each with a message of its own, before the null checks of the plane arrays, before the device check and
- * before anything is queued: an integer filter; a float filter of another shape (four components, sub-sampled chroma, a single
- * plane); an offset outside 0 .. 22; two fields that overlap; a destination step outside 1 .. 4; a source base, a source pitch or
+ * before anything is queued: an integer filter; a bfloat16 filter; a float filter of another shape (four components, sub-sampled
+ * chroma, a single plane); an offset outside 0 .. 22; two fields that overlap; a destination step outside 1 .. 4; a source base, a source pitch or
  * (with nframes > 1) a source frame stride that is no multiple of 4; a source pitch below 4 * width.  Then null arguments, nframes
  * and frame strides as for jinc_filter_process_device_shifted.  Base, pitch and frame stride that are all multiples of 16 get
  * 16-byte loads, others dwords.
@@ -449,8 +461,8 @@ JINC_API int jinc_filter_process_device_widened_packed10(jinc_filter *f, const v
  *   source is never written.  src_frame_stride is read only for nframes > 1.
  *   DESTINATION and result are as for jinc_filter_process_device_widened_packed10, with planes Y, U = Cb, V = Cr.
  * JINC_ERR_INVALID_ARG, each with a message of its own, before the null checks of the plane arrays, before the device check and
- * before anything is queued: an integer filter; a float filter of another shape (four components, no or another sub-sampling, a
- * single plane); a destination step outside 1 .. 4; a source base, a source pitch or (with nframes > 1) a source frame stride
+ * before anything is queued: an integer filter; a bfloat16 filter (ten bits are not exact in bfloat16); a float filter of another
+ * shape (four components, no or another sub-sampling, a single plane); a destination step outside 1 .. 4; a source base, a source pitch or (with nframes > 1) a source frame stride
  * that is no multiple of 4; a source pitch below jinc_v210_row_bytes(width).  Then null arguments, nframes and frame strides as
  * for jinc_filter_process_device_shifted.  Base, pitch and frame stride that are all multiples of 16 get one 16-byte load per
  * block, others four dwords.
@@ -496,7 +508,7 @@ typedef struct jinc_batch jinc_batch;
 JINC_API int jinc_shard_device(int frame, int ndevices);
 JINC_API int jinc_batch_create(const jinc_video_info *vi, const jinc_args *args, int ndevices, int streams_per_device,
                                int register_host_buffers, jinc_batch **out, char *err, size_t err_len);
-/* jinc_batch_create with a sample type (JINC_SAMPLE_DEFAULT / JINC_SAMPLE_FLOAT16, as jinc_filter_create_ex). */
+/* jinc_batch_create with a sample type (JINC_SAMPLE_DEFAULT / JINC_SAMPLE_FLOAT16 / JINC_SAMPLE_BFLOAT16, as jinc_filter_create_ex). */
 JINC_API int jinc_batch_create_ex(const jinc_video_info *vi, const jinc_args *args, int sample_type, int ndevices,
                                   int streams_per_device, int register_host_buffers, jinc_batch **out, char *err, size_t err_len);
 JINC_API int jinc_batch_devices(const jinc_batch *b);

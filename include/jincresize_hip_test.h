@@ -101,7 +101,7 @@ typedef enum jinc_kernel_mode {
  * kernel name for the others.  bench.py reports it as roofline.kernel and the parity tests assert it, so that the
  * instantiation a benchmark times is one the parity tests have checked. */
 JINC_API const char *jinc_filter_last_instance(const jinc_filter *f, int table);
-/* Float planes (fp32, binary16) on the trimmed support: the per-frame flags the most recent frame call raised for `plane` -- 1 where
+/* Float planes (fp32, binary16, bfloat16) on the trimmed support: the per-frame flags the most recent frame call raised for `plane` -- 1 where
  * the trimmed launch (or the scan of the rim no tile stages, or the scan pass of knob FLOAT_SCAN) met an infinity or a NaN in that
  * frame's plane, so that the full-window launch behind it computed the frame again; 0 where the trimmed result stands.  Waits for the
  * device, copies up to `capacity` words (one per frame of that call, in order) to `flags` and returns the call's frame count.
@@ -265,6 +265,9 @@ JINC_API int jinc_debug_convert(const float *sums, void *out, int n, int sample_
 /* ... the binary16 store path of half filters (JINC_SAMPLE_FLOAT16: round to nearest even, overflow to +-inf, no clamp),
  * the plain, buffer and packed-pair stores alike, on `n` fp32 values; out receives the binary16 bit patterns. */
 JINC_API int jinc_debug_convert_half(const float *sums, uint16_t *out, int n, int device);
+/* ... and the bfloat16 store path of JINC_SAMPLE_BFLOAT16 filters (round to nearest even, overflow to +-inf, a NaN stays a NaN, no
+ * clamp): the single conversion and the pair store's packed one; out receives the bfloat16 bit patterns. */
+JINC_API int jinc_debug_convert_bfloat16(const float *sums, uint16_t *out, int n, int device);
 
 /* Test hook: 1 when the device's buffer range check covers the scalar offset of buffer loads (the premise of the
  * direct kernel's bounded segment fetches; probed once per device, the direct kernel is not used where it fails), 0 when
