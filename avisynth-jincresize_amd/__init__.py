@@ -27,7 +27,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JINC_LIB") or os.path.join(_HERE, "lib", "libjincresize_hip.so")  # JINC_LIB: A/B runs against another build
 SIMD_ORDER_ISA_PATH = os.path.join(_HERE, "lib", "kernel_simdorder-gfx950.s")  # the one unit with (explicit) fused multiply-adds
-ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_interleave", "kernel_widen", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "bf16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
+ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_interleave", "kernel_widen", "kernel_narrow", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "bf16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
                        "kernel_quasi_exact_fs9", "kernel_quasi_lane_fs7", "kernel_quasi_lane_fs9")]
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip.h")
 TEST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip_test.h")  # introspection, knobs, hooks
@@ -89,7 +89,8 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided",
            "jinc_filter_process_device_shifted", "jinc_filter_process_device_packed10", "jinc_packed10_layout",
            "jinc_filter_process_device_v210", "jinc_v210_row_bytes", "jinc_filter_process_device_widened",
-           "jinc_filter_process_device_widened_packed10", "jinc_filter_process_device_widened_v210"]
+           "jinc_filter_process_device_widened_packed10", "jinc_filter_process_device_widened_v210",
+           "jinc_filter_process_device_narrowed", "jinc_debug_narrow"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -129,6 +130,7 @@ def lib():
         L.jinc_filter_process_device_widened.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
         L.jinc_filter_process_device_widened_packed10.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
         L.jinc_filter_process_device_widened_v210.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_narrowed.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.jinc_v210_row_bytes.argtypes = [C.c_int]
         L.jinc_v210_row_bytes.restype = C.c_size_t
         L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
@@ -173,6 +175,7 @@ def lib():
         L.jinc_debug_convert.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int]
         L.jinc_debug_convert_half.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.jinc_debug_convert_bfloat16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.jinc_debug_narrow.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.jinc_filter_set_profiling.argtypes = [C.c_void_p, C.c_int]
         L.jinc_filter_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                                C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -484,6 +487,26 @@ def debug_convert_bfloat16(sums: np.ndarray, device: int = 0) -> np.ndarray:
     sums = np.ascontiguousarray(sums, dtype=np.float32)
     out = np.zeros(sums.shape, dtype=np.uint16)
     rc = lib().jinc_debug_convert_bfloat16(sums.ctypes.data, out.ctypes.data, sums.size, device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return out
+
+
+def debug_narrow(values: np.ndarray, dst_bits: int, shift: int = 0, bfloat16: bool = False, device: int = 0) -> np.ndarray:
+    """The narrowing pass of process_device_narrowed applied to one dense row of `values` on the device (test hook): float32 or
+    float16 values, or with bfloat16=True uint16 bit patterns of bfloat16 values; returns rint(clip(value, 0, 2^dst_bits - 1)) << shift
+    as uint8 (dst_bits 8) or uint16 (9 .. 16)."""
+    values = np.ascontiguousarray(values)
+    if bfloat16:
+        if values.dtype != np.uint16:
+            raise TypeError("bfloat16 values are given as uint16 bit patterns")
+        kind = SAMPLE_BFLOAT16
+    elif values.dtype == np.float16:
+        kind = SAMPLE_FLOAT16
+    else:
+        values, kind = np.ascontiguousarray(values, dtype=np.float32), SAMPLE_DEFAULT
+    out = np.zeros(values.shape, dtype=np.uint8 if dst_bits == 8 else np.uint16)
+    rc = lib().jinc_debug_narrow(values.ctypes.data, kind, out.ctypes.data, values.size, int(dst_bits), int(shift), device)
     if rc != 0:
         raise JincError(rc, lib().jinc_last_error().decode())
     return out
@@ -960,6 +983,28 @@ class Filter:
         self._check(lib().jinc_filter_process_device_widened_v210(
             self._h, C.c_void_p(src_ptr), int(src_pitch), C.c_size_t(int(src_stride or 0)), arr(_P4, dst_ptrs), arr(_I4, dst_pitches),
             arr(_I4, dst_steps), arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
+
+    def process_device_narrowed(self, src_ptrs, src_pitches, src_steps, src_strides, dst_ptrs, dst_pitches, dst_steps, dst_shifts,
+                                dst_bits: int, dst_strides, nframes: int, stream: int = 0) -> None:
+        """This fp32 / binary16 / bfloat16 filter's results into INTEGER device samples (jinc_filter_process_device_narrowed): the
+        source side is process_device_strided's on this filter; the destination is addressed as in process_device_shifted, its
+        sample size comes from dst_bits (8: bytes; 9 .. 16: 16-bit words) and a stored sample is
+        rint(clip(r, 0, 2^dst_bits - 1)) << shift[i] with r what process_device stores for the same source planes (NaN -> 0).  NV12
+        from YUV420PS: Y step 1, U = uv, V = uv + 1 sample, both step 2, dst_bits 8; P010: the same with dst_bits 10, shifts 6;
+        BGRA8 from RGBPS: G = p + 1, B = p, R = p + 2, step 4.  Steps, shifts and frame strides may be None."""
+        n = self.fmt.planes
+
+        def arr(kind, values):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(n):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_narrowed(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_S4, src_strides), arr(_P4, dst_ptrs),
+            arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_I4, dst_shifts), int(dst_bits), arr(_S4, dst_strides), int(nframes),
+            C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
     strided_groups = staticmethod(strided_groups)

@@ -1437,5 +1437,104 @@ void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t
         [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });
 }
 
+// ---- jinc_filter_process_device_narrowed: the results of an fp32 / binary16 / bfloat16 filter into INTEGER device frames ----
+// The mirror image of enqueue_widened: the unchanged enqueue on stand-ins of the filter's own type and ONE new pass behind it.
+// EVERY destination plane takes a dense stand-in of the filter's type (for groups_of_side every plane counts as having a shift, in
+// destination sample bytes); narrow_samples_kernel (kernel_narrow.hip) stores lrintf(clamp(r, 0, peak)) << shift from them, one launch
+// per step value present -- NV12: 2 (Y at step 1, UV at step 2), planar: 1, BGRA8: 1 -- which the report counts as merge launches.
+// A source plane takes a stand-in only where its step is not 1, through enqueue_strided's split.  Everything else is
+// run_on_stand_ins, so these calls alternate with strided, shifted, packed10, v210 and widened ones on one filter.
+// Dense planes per frame, 1080p -> 4K into NV12 from planar planes: fp32 rows of 3840 x 4 = 15 360 and 1920 x 4 = 7680 bytes are
+// multiples of 256 already, so a frame takes 15 360 x 2160 + 2 x 7680 x 1080 = 49 766 400 bytes and the 1 GiB default holds
+// floor(1 073 741 824 / 49 766 400) = 21 frames -- below kSliceFrames, so no rounding: a call of 128 runs as 6 x 21 + 2.  binary16 /
+// bfloat16: 7680 x 2160 + 2 x 3840 x 1080 = 24 883 200 bytes, 43 frames: 43 + 43 + 42.
+namespace {
+// The groups of a narrowed destination as launch arguments, one NarrowArgs per step (fill_args for destination samples of their own size).
+void fill_narrow_args(const jinc_filter& f, const Side& s, void* const base[4], const int pitch[4], const int* step, const int* shift,
+                      const size_t* fs, size_t dst_bytes, float peak, const char* scratch, int first_frame, int slice_frames, int nframes,
+                      NarrowArgs by_step[5]) {
+    for (int g = 0; g < s.ngroups; ++g) {
+        NarrowGroup e;
+        int members = 0, first = -1;
+        uintptr_t lo = 0;
+        for (int i = 0; i < f.planecount; ++i) {
+            if (s.group_of[i] != g) continue;
+            if (first < 0) first = i;
+            const uintptr_t b = reinterpret_cast<uintptr_t>(base[i]);
+            lo = members ? std::min(lo, b) : b;
+            ++members;
+            e.plane[s.channel_of[i]] = scratch + s.offset[i] * static_cast<size_t>(slice_frames);
+            e.shift[s.channel_of[i]] = static_cast<uint8_t>(shift_of(shift, i));
+        }
+        const int n = step_of(step, first);
+        const size_t frame_stride = (fs && nframes > 1) ? fs[first] : 0;
+        e.packed = reinterpret_cast<char*>(lo) + static_cast<size_t>(first_frame) * frame_stride;
+        e.packed_frame_stride = frame_stride;
+        e.plane_frame_stride = s.dense_fs[first];
+        e.packed_pitch = static_cast<uint32_t>(pitch[first]);
+        e.plane_pitch = static_cast<uint32_t>(s.dense_pitch[first]);
+        e.width = static_cast<uint32_t>(s.w[first]);
+        e.rows = static_cast<uint32_t>(s.h[first]);
+        const uintptr_t a = lo | static_cast<uintptr_t>(pitch[first]) | static_cast<uintptr_t>(frame_stride);
+        e.unit = a % 16 == 0 ? 16u : a % 4 == 0 ? 4u : 0u;
+        const uint32_t lane_pixels = static_cast<uint32_t>(16 / dst_bytes);
+        // (a group with a channel missing stores sample by sample: only the given channels' samples may be stored to)
+        e.vec_pixels = (e.unit && members == n) ? e.width / lane_pixels * lane_pixels : 0u;
+        NarrowArgs& a_n = by_step[n];
+        a_n.peak = peak;
+        a_n.g[a_n.ngroups++] = e;
+    }
+}
+}  // namespace
+
+void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
+                      void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift, int dst_bits,
+                      const size_t* dst_fs, int nframes, hipStream_t stream) {
+    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    const size_t sb = static_cast<size_t>(f.vi_in.component_size), dst_bytes = dst_bits > 8 ? 2 : 1;
+    Side in, out;
+    for (int i = 0; i < f.planecount; ++i) {
+        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
+        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
+    }
+    // Every destination plane is a member of a group (groups_of_side gives a plane of step 1 a group of its own when it has a shift:
+    // here every plane counts as having one); planes of one pixel share a group by the strided call's rule, in destination samples.
+    static const int kEveryPlane[4] = {1, 1, 1, 1};
+    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
+    in.ngroups = groups_of_side(src, src_pitch, src_step, nullptr, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
+    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, kEveryPlane, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(dst_bytes), f.planecount, out.group_of, out.channel_of);
+    check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
+    for (int i = 0; i < f.planecount; ++i) {  // (base alignment and the row's size: filter.cpp, in front of the device check)
+        if (!dst[i]) throw ArgError("JincResize: null plane pointer.");
+        if (dst_pitch[i] <= 0 || dst_pitch[i] % dst_bytes) throw ArgError("JincResize: destination pitch is not a multiple of the destination sample size.");
+        if (dst_fs && nframes > 1 && dst_fs[i] % dst_bytes) throw ArgError("JincResize: destination frame stride is not a multiple of the destination sample size.");
+    }
+    const float peak = static_cast<float>((1u << dst_bits) - 1u);
+    run_on_stand_ins(
+        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
+        [&](char* scratch, int k0, int slice, int n) {
+            InterleaveArgs split[5];
+            fill_args(f, in, src, src_pitch, src_step, nullptr, src_fs, scratch, k0, slice, nframes, false, split);
+            int launches = 0;
+            for (int step = 2; step <= 4; ++step)
+                if (split[step].ngroups) {
+                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream)), "split launch");
+                    ++launches;
+                }
+            return launches;
+        },
+        [&](char* scratch, int k0, int slice, int n) {
+            NarrowArgs narrow[5];
+            fill_narrow_args(f, out, dst, dst_pitch, dst_step, dst_shift, dst_fs, dst_bytes, peak, scratch, k0, slice, nframes, narrow);
+            int launches = 0;
+            for (int step = 1; step <= 4; ++step)
+                if (narrow[step].ngroups) {
+                    hip_check(static_cast<hipError_t>(jinc::launch_narrow_samples(narrow[step], f.sample_kind(), step, static_cast<int>(dst_bytes), n, stream)), "narrow launch");
+                    ++launches;
+                }
+            return launches;
+        });
+}
+
 }  // namespace host
 }  // namespace jinc

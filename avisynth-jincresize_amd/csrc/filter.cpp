@@ -397,6 +397,53 @@ int jinc_filter_process_device_widened(jinc_filter* f, const void* const src[4],
     });
 }
 
+int jinc_filter_process_device_narrowed(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                                        const size_t src_frame_stride[4], void* const dst[4], const int dst_pitch[4],
+                                        const int dst_sample_step[4], const int dst_sample_shift[4], int dst_bits,
+                                        const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    // the filter, dst_bits, the steps, the shifts and the destination's bases and pitches first (they need no device), then the
+    // checks of jinc_filter_process_device_shifted in its order
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (!f->float_samples())
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed integer destinations need an fp32, binary16 or bfloat16 filter; this filter has " +
+                                              std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_shifted).");
+    if (dst_bits < 8 || dst_bits > 16)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: dst_bits must be in 8..16 (got " + std::to_string(dst_bits) + ").");
+    for (const int* step : {src_sample_step, dst_sample_step})
+        for (int i = 0; step && i < f->planecount; ++i)
+            if (step[i] < 1 || step[i] > 4)
+                return fail(JINC_ERR_INVALID_ARG, std::string("JincResize: ") + (step == src_sample_step ? "source" : "destination") +
+                                                      " sample step of a narrowed call must be in 1..4 (got " + std::to_string(step[i]) + ").");
+    const int dst_bytes = dst_bits > 8 ? 2 : 1, spare = 8 * dst_bytes - dst_bits;
+    for (int i = 0; dst_sample_shift && i < f->planecount; ++i) {
+        if (dst_sample_shift[i] < 0) return fail(JINC_ERR_INVALID_ARG, "JincResize: destination sample shift must not be negative.");
+        if (dst_sample_shift[i] > spare)
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: destination sample shift " + std::to_string(dst_sample_shift[i]) + " is larger than the padding of a " +
+                                                  std::to_string(dst_bits) + "-bit sample in its container (" + std::to_string(spare) + " bits).");
+    }
+    for (int i = 0; dst && dst_pitch && i < f->planecount; ++i) {
+        int w = 0, h = 0;
+        f->plane_dims(f->vi_out, i, w, h);
+        if (reinterpret_cast<uintptr_t>(dst[i]) % static_cast<uintptr_t>(dst_bytes))
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: destination plane pointer is not aligned to the destination sample size.");
+        const size_t step = static_cast<size_t>(dst_sample_step ? dst_sample_step[i] : 1);
+        const size_t need = (static_cast<size_t>(w - 1) * step + 1) * static_cast<size_t>(dst_bytes);
+        if (dst_pitch[i] < 0 || static_cast<size_t>(dst_pitch[i]) < need)
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: destination pitch " + std::to_string(dst_pitch[i]) + " is smaller than the row of " +
+                                                  std::to_string(need) + " bytes at this sample step and size.");
+    }
+    if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_narrowed(*f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_sample_shift, dst_bits,
+                         dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
 int jinc_filter_process_device_widened_packed10(jinc_filter* f, const void* src, int src_pitch, const int src_field_offset[3],
                                                 size_t src_frame_stride, void* const dst[4], const int dst_pitch[4],
                                                 const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
@@ -713,6 +760,36 @@ int jinc_debug_convert(const float* sums, void* out, int n, int sample_bytes, fl
         hip_check(static_cast<hipError_t>(jinc::launch_debug_convert(d_in, d_out, n, sample_bytes, peak, nullptr)), "convert launch");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         bounce_download(out, d_out, static_cast<size_t>(sample_bytes) * n, "download of the samples");
+        (void)hipFree(d_in);
+        (void)hipFree(d_out);
+    });
+}
+
+int jinc_debug_narrow(const void* in, int in_kind, void* out, int n, int dst_bits, int shift, int device) {
+    const bool kind_ok = in_kind == JINC_SAMPLE_DEFAULT || in_kind == JINC_SAMPLE_FLOAT16 || in_kind == JINC_SAMPLE_BFLOAT16;
+    if (!in || !out || n < 0 || !kind_ok || dst_bits < 8 || dst_bits > 16) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    const size_t in_bytes = in_kind == JINC_SAMPLE_DEFAULT ? 4 : 2, dst_bytes = dst_bits > 8 ? 2 : 1;
+    if (shift < 0 || shift > static_cast<int>(8 * dst_bytes) - dst_bits) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    if (n == 0) return JINC_OK;
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        char *d_in = nullptr, *d_out = nullptr;
+        hip_check(hipMalloc(&d_in, in_bytes * (n + 1)), "hipMalloc");
+        hip_check(hipMalloc(&d_out, dst_bytes * (n + 1)), "hipMalloc");
+        bounce_upload(d_in, in, in_bytes * n, "upload of the values");
+        jinc::NarrowArgs a;  // one group of one dense row: whole lanes by 16-byte accesses, the rest sample by sample
+        a.ngroups = 1;
+        a.peak = static_cast<float>((1u << dst_bits) - 1u);
+        jinc::NarrowGroup& g = a.g[0];
+        g.packed = d_out, g.plane[0] = d_in;
+        g.packed_pitch = static_cast<uint32_t>(dst_bytes * n), g.plane_pitch = static_cast<uint32_t>(in_bytes * n);
+        g.width = static_cast<uint32_t>(n), g.rows = 1, g.unit = 16;
+        g.vec_pixels = g.width / static_cast<uint32_t>(16 / dst_bytes) * static_cast<uint32_t>(16 / dst_bytes);
+        g.shift[0] = static_cast<uint8_t>(shift);
+        const int kind = in_kind == JINC_SAMPLE_FLOAT16 ? jinc::kSampleHalf : in_kind == JINC_SAMPLE_BFLOAT16 ? jinc::kSampleBFloat16 : 0;
+        hip_check(static_cast<hipError_t>(jinc::launch_narrow_samples(a, kind, 1, static_cast<int>(dst_bytes), 1, nullptr)), "narrow launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bounce_download(out, d_out, dst_bytes * n, "download of the samples");
         (void)hipFree(d_in);
         (void)hipFree(d_out);
     });

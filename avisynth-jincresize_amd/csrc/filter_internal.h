@@ -1,7 +1,7 @@
 // filter_internal.h -- types and internal interfaces shared by the host translation units of libjincresize_hip.so:
 //   filter_args.cpp   Create_JincResize's argument handling and geometry derivation (configure)
 //   device_plan.cpp   device-resident plans: upload, launch planning for every kernel family (init_device)
-//   dispatch.cpp      per-call kernel selection and launches (enqueue; enqueue_strided: planes with a sample step; enqueue_packed10: 10:10:10:2 words; enqueue_v210: v210 blocks; enqueue_widened: integer samples into float / half filters; enqueue_widened_packed10 / _v210: 10:10:10:2 words and v210 blocks into them)
+//   dispatch.cpp      per-call kernel selection and launches (enqueue; enqueue_strided: planes with a sample step; enqueue_packed10: 10:10:10:2 words; enqueue_v210: v210 blocks; enqueue_widened: integer samples into float / half filters; enqueue_widened_packed10 / _v210: 10:10:10:2 words and v210 blocks into them; enqueue_narrowed: their results into integer samples)
 //   pipeline.cpp      frames in flight: device staging slots, pinned host ranges, H2D -> kernels -> D2H
 //   filter.cpp        the C ABI of include/jincresize_hip.h
 // Nothing here crosses the C ABI.
@@ -352,6 +352,13 @@ void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, co
                               const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream);
 void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t src_fs, void* const dst[4], const int dst_pitch[4],
                           const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream);
+// ... enqueue on an fp32 / binary16 / bfloat16 filter whose results go into INTEGER samples of dst_bits bits (8: bytes; 9 .. 16:
+// 16-bit words) at `shift` in their container: every destination plane takes a dense stand-in of the filter's sample type and
+// narrow_samples_kernel stores lrintf(clamp(r, 0, peak)) << shift from it; the source side is enqueue_strided's (no shifts).
+// Filter, dst_bits, steps, shifts, destination bases and destination pitches have been checked by filter.cpp.
+void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
+                      void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift, int dst_bits,
+                      const size_t* dst_fs, int nframes, hipStream_t stream);
 // ... the channel groups of one side's planes (pure: test header jinc_debug_strided_groups); returns their number
 int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
                    const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]);
@@ -359,7 +366,7 @@ struct StridedReport {  // test header: jinc_debug_last_strided
     int split_launches = 0, merge_launches = 0, slices = 0;
     long long scratch_bytes = 0;
 };
-const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided / enqueue_packed10 / enqueue_v210 / enqueue_widened*
+const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided / enqueue_packed10 / enqueue_v210 / enqueue_widened* / enqueue_narrowed
 int last_call_frames_in_process();
 const char* last_interior_instance_in_process();
 // pipeline.cpp: frames in flight on one instance

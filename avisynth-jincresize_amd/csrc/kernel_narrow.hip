@@ -1,0 +1,83 @@
+// kernel_narrow.hip -- the dense fp32 / binary16 / bfloat16 planes a float filter's kernels have written -> integer samples, behind
+// jinc_filter_process_device_narrowed (dispatch.cpp enqueue_narrowed): the results of a float, half or bfloat16 filter become the
+// planes of an encoder's or a display's NV12 / P010 / Y210 surface, packed 8-bit RGB(A) or planar integer frames.  A merge
+// (kernel_interleave.hip) that NARROWS: it stores lrintf(clamp(r, 0, peak)) << shift[c] as channel c of N interleaved samples -- the
+// step the integer filters end in (ref JincResize.cpp:582), through device_common.hpp's round_sample_u8 / round_pair_u16 /
+// round_sample, so a float filter followed by this pass is the integer filter of the same geometry whenever the float planes hold
+// integers.  The mirror image of kernel_widen.hip's widen_samples_kernel.
+//
+// Shape, after merge_samples_kernel and widen_samples_kernel: ONE launch covers every channel group and frame of a slice (grid = row
+// blocks x frames x groups; the groups travel as kernel arguments, kernels.h NarrowArgs), a wave owns a row, its lanes walk along it,
+// and no access costs a division or a modulo.  The row function is narrow_rows.h: a lane owns 16 / DB whole pixels per step, IB / DB
+// 16-byte loads per plane and N 16-byte stores (dwords where the group's alignment allows no more); tails, unaligned groups and
+// groups with a channel missing store sample by sample and only their own samples.  The destination is never read.  Plain C++: no
+// assembly, no LDS, no scratch.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+#include "narrow_rows.h"
+
+namespace jinc {
+namespace {
+
+// Row blockIdx.x * 4 + wave of frame blockIdx.y of group blockIdx.z.
+template <int KIND, int N, int DB>
+__global__ __launch_bounds__(256) void narrow_samples_kernel(const NarrowArgs a) {
+    const NarrowGroup& g = a.g[blockIdx.z];
+    const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row < g.rows) narrow::narrow_row<KIND, N, DB>(g, a.peak, blockIdx.y, row, threadIdx.x & 63u);
+}
+
+template <int KIND, int N, int DB>
+int launch(const NarrowArgs& a, int nframes, hipStream_t s) {
+    uint32_t rows = 0;
+    for (int k = 0; k < a.ngroups; ++k) rows = a.g[k].rows > rows ? a.g[k].rows : rows;
+    if (a.ngroups <= 0 || nframes <= 0 || rows == 0) return hipSuccess;
+    const dim3 grid((rows + 3) / 4, static_cast<uint32_t>(nframes), static_cast<uint32_t>(a.ngroups));
+    hipLaunchKernelGGL((narrow_samples_kernel<KIND, N, DB>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+template <int KIND, int DB>
+int launch_by_step(const NarrowArgs& a, int step, int nframes, hipStream_t s) {
+    switch (step) {
+        case 1: return launch<KIND, 1, DB>(a, nframes, s);
+        case 2: return launch<KIND, 2, DB>(a, nframes, s);
+        case 3: return launch<KIND, 3, DB>(a, nframes, s);
+        case 4: return launch<KIND, 4, DB>(a, nframes, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <int KIND>
+int launch_by_size(const NarrowArgs& a, int step, int dst_bytes, int nframes, hipStream_t s) {
+    if (dst_bytes == 1) return launch_by_step<KIND, 1>(a, step, nframes, s);
+    if (dst_bytes == 2) return launch_by_step<KIND, 2>(a, step, nframes, s);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+int launch_narrow_samples(const NarrowArgs& a, int in_kind, int step, int dst_bytes, int nframes, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (a.ngroups > 4 || (dst_bytes != 1 && dst_bytes != 2)) return hipErrorInvalidValue;
+    // the peak of a byte is 255 (round_sample_u8 saturates there); a word's lies in 511 .. 65535 and is 2^bits - 1
+    if (dst_bytes == 1 ? a.peak != 255.f : !(a.peak >= 511.f && a.peak <= 65535.f)) return hipErrorInvalidValue;
+    for (int k = 0; k < a.ngroups; ++k) {
+        const NarrowGroup& g = a.g[k];
+        const uint32_t lane_pixels = 16u / static_cast<uint32_t>(dst_bytes);
+        if (g.vec_pixels > g.width || g.vec_pixels % lane_pixels || (g.vec_pixels && g.unit != 16 && g.unit != 4)) return hipErrorInvalidValue;
+        for (int c = 0; c < 4; ++c) {
+            if (g.vec_pixels && c < step && !g.plane[c]) return hipErrorInvalidValue;  // (vectors store every channel of a pixel)
+            if (dst_bytes == 1 ? g.shift[c] != 0 : (static_cast<uint32_t>(a.peak) << g.shift[c]) > 65535u) return hipErrorInvalidValue;
+        }
+    }
+    switch (in_kind) {
+        case 0: return launch_by_size<0>(a, step, dst_bytes, nframes, s);
+        case kSampleHalf: return launch_by_size<kSampleHalf>(a, step, dst_bytes, nframes, s);
+        case kSampleBFloat16: return launch_by_size<kSampleBFloat16>(a, step, dst_bytes, nframes, s);
+    }
+    return hipErrorInvalidValue;  // (no kernel for this shape: an error, never a silent skip)
+}
+
+}  // namespace jinc

@@ -600,6 +600,32 @@ int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_by
 int launch_widen_fields(const FieldArgs& a, int out_bytes, int nframes, void* stream);
 int launch_widen_v210(const V210Args& a, int out_bytes, int nframes, void* stream);
 
+// The dense planes of an fp32 / binary16 / bfloat16 filter -> INTEGER samples (kernel_narrow.hip, narrow_rows.h;
+// jinc_filter_process_device_narrowed): the mirror of WidenGroup.  A channel group as in InterleaveGroup, written only: `step`
+// destination samples of dst_bytes (1: a byte; 2: a little-endian 16-bit word) per pixel at packed, channel c of pixel x of row y of
+// frame n at packed + n * packed_frame_stride + y * packed_pitch + (x * step + c) * dst_bytes.  The dense plane of channel c
+// (plane[c]; nullptr: not given, its samples are not stored to) holds the filter's results, in_bytes (4: fp32; 2: binary16 or
+// bfloat16) a sample, at plane[c] + n * plane_frame_stride + y * plane_pitch + x * in_bytes; the stored sample is
+// lrintf(clamp(result, 0, peak)) << shift[c].  A group may have step 1: every destination plane of such a call takes a stand-in.  The
+// dense planes are the filter's own: bases, pitch and frame stride multiples of 256 bytes.
+// unit as in InterleaveGroup, of the packed side; vec_pixels: the leading pixels of every row stored by such accesses, a multiple of
+// the 16 / dst_bytes pixels a lane owns -- none in a group with a channel missing (only the given channels' samples may be stored to).
+struct NarrowGroup {
+    char* packed = nullptr;
+    const char* plane[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t packed_frame_stride = 0, plane_frame_stride = 0;
+    uint32_t packed_pitch = 0, plane_pitch = 0, width = 0, rows = 0, vec_pixels = 0, unit = 0;
+    uint8_t shift[4] = {0, 0, 0, 0};
+};
+struct NarrowArgs {
+    NarrowGroup g[4];
+    int ngroups = 0;
+    float peak = 255.f;  // (1 << dst_bits) - 1
+};
+// One launch over every group and frame of `a`: in_kind 0 (fp32), kSampleHalf or kSampleBFloat16; step 1 .. 4 (the same for all
+// groups of a launch); dst_bytes 1 (peak 255, shifts 0) or 2 (peak 511 .. 65535, peak << shift below 65536).
+int launch_narrow_samples(const NarrowArgs& a, int in_kind, int step, int dst_bytes, int nframes, void* stream);
+
 // Measurement hook (kernel_probe.hip): `samplers` single-lane workgroups stamp the shader clock counter and the 100 MHz
 // real-time counter until *stop_flag (device memory) becomes non-zero or max_seconds pass; out[2 k] = shader ticks,
 // out[2 k + 1] = real-time ticks of sampler k.

@@ -417,6 +417,53 @@ JINC_API int jinc_filter_process_device_widened(jinc_filter *f, const void *cons
                                                 const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
                                                 void *hip_stream);
 
+/* The results of an fp32, binary16 or bfloat16 filter into INTEGER device frames: what a network leaves in float / half / bfloat16
+ * planes, in code-value units, resampled in float and written straight into an encoder's or a display's NV12 / P010 / Y210 / BGRA
+ * surface.  The way back out of jinc_filter_process_device_widened.
+ *   `f` is an fp32 filter (bits_per_component 32), a binary16 filter (JINC_SAMPLE_FLOAT16) or a bfloat16 filter
+ *   (JINC_SAMPLE_BFLOAT16); its geometry, number of components and sub-sampling describe the frame exactly as for
+ *   jinc_filter_process_device_strided.
+ *   The SOURCE is exactly the src side of jinc_filter_process_device_strided on that filter: planes of the filter's own type, steps
+ *   1 .. 4 (NULL: all ones).  The source is never written.
+ *   The DESTINATION is integer samples, addressed exactly as the dst side of jinc_filter_process_device_shifted (base, pitch, step
+ *   1 .. 4 in samples, shift, frame stride; NULL step and shift arrays mean all ones and all zeros), but the sample size comes from
+ *   dst_bits, not from the filter: dst_bits 8 is 1-byte samples, dst_bits 9 .. 16 little-endian 2-byte words.  Sample x of row y of
+ *   frame n of plane i lies at base[i] + n * frame_stride[i] + y * pitch[i] + x * step[i] * bytes, a shift lies in
+ *   0 .. 8 * bytes - dst_bits, and the stored sample is value << shift as the whole byte / word: padding bits are zeros.
+ *     NV12 from YUV420PS / PH:      Y = y, step 1; U = uv, V = uv + 1 sample, step 2; dst_bits 8.
+ *     P010 / P012:                  the same with dst_bits 10 / 12 and all shifts 6 / 4.
+ *     Y210 from YUV422PS:           Y = p, step 2; U = p + 1, V = p + 3 samples, step 4, one buffer; dst_bits 10, shifts 6.
+ *     BGRA8 from RGBPS:             G = p + 1, B = p, R = p + 2, all step 4; dst_bits 8 (the X bytes are not stored to).
+ *     planar YUV420P10:             steps 1, shifts 0, dst_bits 10.
+ *   DEFINITION.  Let r be what jinc_filter_process_device stores on that filter for the same source planes, widened exactly to
+ *   fp32, and peak = (1 << dst_bits) - 1.  Then value = lrintf(clamp(r, 0, peak)), round half to even; a NaN becomes 0, -inf and -0
+ *   become 0, +inf becomes peak: the step the integer filters end in.  For binary16 and bfloat16 filters r is the ALREADY NARROWED
+ *   16-bit result, so such a call rounds twice -- once to the filter's type, once to the code value; an fp32 filter rounds once.
+ *   CONSEQUENCE.  The integer filters convert every source sample to float before the multiply, so on an fp32 filter whose source
+ *   planes hold integers in 0 .. peak, with dst_bits equal to an integer format's depth, the result equals that integer filter's
+ *   jinc_filter_process_device output, bit for bit.
+ *   No scale or offset lies between the float range and the code values, nothing is dithered, no colour is converted.
+ * As in the shifted call: no destination byte is stored to unless it belongs to a sample of a given plane (the X of BGRX under a
+ * three-component filter, row padding and gaps between frames keep their values), the destination is never read, and destination
+ * planes may share a buffer.
+ * JINC_ERR_INVALID_ARG, each with a message of its own, before the device check and before anything is queued: an integer filter;
+ * dst_bits outside 8 .. 16; a step outside 1 .. 4 (either side); a negative shift; a shift above its range; a destination base not
+ * aligned to the destination sample size; a destination pitch below ((width - 1) * step + 1) * bytes of that plane.  Then null
+ * arguments, nframes and frame strides as for jinc_filter_process_device_shifted; a destination pitch or frame stride that is no
+ * multiple of the destination sample size is refused behind the device check.  Destination base, pitch and frame stride that are
+ * all multiples of 16 get 16-byte stores, all multiples of 4 dwords, others sample-sized stores.
+ * EVERY destination plane takes a dense stand-in of the filter's own type (the scratch of the strided call: same knob
+ * strided_scratch_bytes, same slicing of long calls, same ordering between calls, so these calls may alternate with strided,
+ * shifted, packed and widened ones on one filter), rows padded to 256 bytes; a source plane takes one only where its step is not 1.
+ * 1080p -> 4K from planar fp32 into NV12: 3840 x 4 = 15 360 and 1920 x 4 = 7680 bytes per row are multiples of 256 already, so a
+ * frame needs 15 360 x 2160 + 2 x 7680 x 1080 = 49 766 400 bytes and the 1 GiB default holds floor(1 073 741 824 / 49 766 400) = 21
+ * frames (a call of 128 runs as 6 x 21 + 2); from binary16 or bfloat16 half of that, 24 883 200 bytes, 43 frames (43 + 43 + 42).
+ * 10:10:10:2 words and v210 blocks are no destinations of this call. */
+JINC_API int jinc_filter_process_device_narrowed(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                 const int src_sample_step[4], const size_t src_frame_stride[4], void *const dst[4],
+                                                 const int dst_pitch[4], const int dst_sample_step[4], const int dst_sample_shift[4],
+                                                 int dst_bits, const size_t dst_frame_stride[4], int nframes, void *hip_stream);
+
 /* 10:10:10:2 WORDS into an fp32 or binary16 filter: the HDR 4:4:4 surface of decoders and swap chains (Y410, R10G10B10A2, the DRM
  * 2101010 / 1010102 orders) resampled straight into the float or half planes a network reads, with nothing rounded to a code value
  * and nothing clamped on the way.

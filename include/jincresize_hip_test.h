@@ -268,6 +268,11 @@ JINC_API int jinc_debug_convert_half(const float *sums, uint16_t *out, int n, in
 /* ... and the bfloat16 store path of JINC_SAMPLE_BFLOAT16 filters (round to nearest even, overflow to +-inf, a NaN stays a NaN, no
  * clamp): the single conversion and the pair store's packed one; out receives the bfloat16 bit patterns. */
 JINC_API int jinc_debug_convert_bfloat16(const float *sums, uint16_t *out, int n, int device);
+/* ... and the narrowing pass of jinc_filter_process_device_narrowed itself: narrow_samples_kernel with one sample per pixel on ONE
+ * dense row of `n` caller-given values of in_kind (JINC_SAMPLE_DEFAULT: fp32; JINC_SAMPLE_FLOAT16 / JINC_SAMPLE_BFLOAT16: 16-bit
+ * patterns).  out receives n samples lrintf(clamp(value, 0, (1 << dst_bits) - 1)) << shift, bytes for dst_bits 8 and 16-bit words
+ * for 9 .. 16 (shift in 0 .. 8 * bytes - dst_bits): whole lanes through the 16-byte accesses, the rest sample by sample. */
+JINC_API int jinc_debug_narrow(const void *in, int in_kind, void *out, int n, int dst_bits, int shift, int device);
 
 /* Test hook: 1 when the device's buffer range check covers the scalar offset of buffer loads (the premise of the
  * direct kernel's bounded segment fetches; probed once per device, the direct kernel is not used where it fails), 0 when
