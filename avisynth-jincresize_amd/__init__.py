@@ -90,12 +90,15 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_process_device_shifted", "jinc_filter_process_device_packed10", "jinc_packed10_layout",
            "jinc_filter_process_device_v210", "jinc_v210_row_bytes", "jinc_filter_process_device_widened",
            "jinc_filter_process_device_widened_packed10", "jinc_filter_process_device_widened_v210",
-           "jinc_filter_process_device_narrowed", "jinc_debug_narrow"]
+           "jinc_filter_process_device_narrowed", "jinc_debug_narrow",
+           "jinc_filter_process_device_widened_scaled", "jinc_filter_process_device_narrowed_scaled", "jinc_code_range",
+           "jinc_debug_widen_scaled", "jinc_debug_narrow_scaled"]
 
 _lib = None
 _P4 = C.c_void_p * 4
 _I4 = C.c_int * 4
 _S4 = C.c_size_t * 4
+_F4 = C.c_float * 4
 
 
 def lib():
@@ -131,6 +134,9 @@ def lib():
         L.jinc_filter_process_device_widened_packed10.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
         L.jinc_filter_process_device_widened_v210.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
         L.jinc_filter_process_device_narrowed.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_widened_scaled.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_narrowed_scaled.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+        L.jinc_code_range.argtypes = [C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 4
         L.jinc_v210_row_bytes.argtypes = [C.c_int]
         L.jinc_v210_row_bytes.restype = C.c_size_t
         L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
@@ -176,6 +182,8 @@ def lib():
         L.jinc_debug_convert_half.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.jinc_debug_convert_bfloat16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.jinc_debug_narrow.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.jinc_debug_narrow_scaled.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int]
+        L.jinc_debug_widen_scaled.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.jinc_filter_set_profiling.argtypes = [C.c_void_p, C.c_int]
         L.jinc_filter_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                                C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -510,6 +518,57 @@ def debug_narrow(values: np.ndarray, dst_bits: int, shift: int = 0, bfloat16: bo
     if rc != 0:
         raise JincError(rc, lib().jinc_last_error().decode())
     return out
+
+
+def debug_narrow_scaled(values: np.ndarray, dst_bits: int, shift: int, scale: float, offset: float, bfloat16: bool = False,
+                        device: int = 0) -> np.ndarray:
+    """The scaled narrowing pass of process_device_narrowed_scaled applied to one dense row of `values` on the device (test hook;
+    values as for debug_narrow); returns rint(clip(fl32(fl32(value * scale) + offset), 0, 2^dst_bits - 1)) << shift as uint8
+    (dst_bits 8) or uint16 (9 .. 16)."""
+    values = np.ascontiguousarray(values)
+    if bfloat16:
+        if values.dtype != np.uint16:
+            raise TypeError("bfloat16 values are given as uint16 bit patterns")
+        kind = SAMPLE_BFLOAT16
+    elif values.dtype == np.float16:
+        kind = SAMPLE_FLOAT16
+    else:
+        values, kind = np.ascontiguousarray(values, dtype=np.float32), SAMPLE_DEFAULT
+    out = np.zeros(values.shape, dtype=np.uint8 if dst_bits == 8 else np.uint16)
+    rc = lib().jinc_debug_narrow_scaled(values.ctypes.data, kind, out.ctypes.data, values.size, int(dst_bits), int(shift), float(scale),
+                                        float(offset), device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return out
+
+
+def debug_widen_scaled(raw: np.ndarray, src_bits: int, shift: int, scale: float, offset: float, out_kind: int = 0,
+                       device: int = 0) -> np.ndarray:
+    """The scaled widening pass of process_device_widened_scaled applied to one dense row of integer samples on the device (test
+    hook): uint8 samples for src_bits 8, uint16 words for 9 .. 16.  Returns fl32(fl32(float((raw >> shift) & mask) * scale) + offset)
+    as float32 (out_kind SAMPLE_DEFAULT), float16 (SAMPLE_FLOAT16) or uint16 bfloat16 bit patterns (SAMPLE_BFLOAT16), the 16-bit
+    types rounded to nearest even."""
+    raw = np.ascontiguousarray(raw, dtype=np.uint8 if src_bits == 8 else np.uint16)
+    out = np.zeros(raw.shape, dtype=np.float32 if out_kind == SAMPLE_DEFAULT else np.uint16)
+    rc = lib().jinc_debug_widen_scaled(raw.ctypes.data, int(src_bits), int(shift), float(scale), float(offset), int(out_kind),
+                                       out.ctypes.data, raw.size, device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return out.view(np.float16) if out_kind == SAMPLE_FLOAT16 else out
+
+
+RANGE_FULL, RANGE_LIMITED = 0, 1          # jinc_code_range: range
+PLANE_LUMA_OR_RGB, PLANE_CHROMA = 0, 1    # jinc_code_range: plane_kind
+
+
+def code_range(bits: int, range: int, plane_kind: int) -> Tuple[float, float, float, float]:
+    """jinc_code_range: (to_float_scale, to_float_offset, to_code_scale, to_code_offset) between the code values of a `bits`-bit
+    plane and the float range 0 .. 1 (luma, RGB) or -0.5 .. 0.5 (chroma), as float32 values; needs no device."""
+    v = [C.c_float() for _ in (0, 1, 2, 3)]
+    rc = lib().jinc_code_range(int(bits), int(range), int(plane_kind), *[C.byref(x) for x in v])
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return tuple(np.float32(x.value) for x in v)
 
 
 # Sample types of jinc_filter_create_ex / jinc_batch_create_ex
@@ -1005,6 +1064,45 @@ class Filter:
             self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_S4, src_strides), arr(_P4, dst_ptrs),
             arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_I4, dst_shifts), int(dst_bits), arr(_S4, dst_strides), int(nframes),
             C.c_void_p(stream)))
+
+    def process_device_widened_scaled(self, src_ptrs, src_pitches, src_steps, src_shifts, src_bits: int, src_scales, src_offsets,
+                                      src_strides, dst_ptrs, dst_pitches, dst_steps, dst_strides, nframes: int, stream: int = 0) -> None:
+        """process_device_widened with a scale and an offset per plane (jinc_filter_process_device_widened_scaled): plane i holds
+        fl32(fl32(float(value) * src_scales[i]) + src_offsets[i]), narrowed round-to-nearest-even for half and bfloat16 filters, which
+        take every src_bits 8 .. 16 here.  src_scales None means all 1.0, src_offsets None all 0.0; both None IS
+        process_device_widened.  code_range gives the usual pairs."""
+        n = self.fmt.planes
+
+        def arr(kind, values):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(n):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_widened_scaled(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_I4, src_shifts), int(src_bits),
+            arr(_F4, src_scales), arr(_F4, src_offsets), arr(_S4, src_strides), arr(_P4, dst_ptrs), arr(_I4, dst_pitches),
+            arr(_I4, dst_steps), arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
+
+    def process_device_narrowed_scaled(self, src_ptrs, src_pitches, src_steps, src_strides, dst_ptrs, dst_pitches, dst_steps, dst_shifts,
+                                       dst_bits: int, dst_scales, dst_offsets, dst_strides, nframes: int, stream: int = 0) -> None:
+        """process_device_narrowed with a scale and an offset per plane (jinc_filter_process_device_narrowed_scaled): a stored sample
+        is rint(clip(fl32(fl32(r * dst_scales[i]) + dst_offsets[i]), 0, 2^dst_bits - 1)) << shift[i].  dst_scales None means all 1.0,
+        dst_offsets None all 0.0; both None IS process_device_narrowed.  code_range gives the usual pairs."""
+        n = self.fmt.planes
+
+        def arr(kind, values):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(n):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_narrowed_scaled(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_S4, src_strides), arr(_P4, dst_ptrs),
+            arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_I4, dst_shifts), int(dst_bits), arr(_F4, dst_scales), arr(_F4, dst_offsets),
+            arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
     strided_groups = staticmethod(strided_groups)

@@ -1279,8 +1279,8 @@ void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[
 namespace {
 // The groups of a widened source as launch arguments, one WidenArgs per step (fill_args for source samples of their own size).
 void fill_widen_args(const jinc_filter& f, const Side& s, const void* const base[4], const int pitch[4], const int* step, const int* shift,
-                     const size_t* fs, size_t src_bytes, uint32_t mask, char* scratch, int first_frame, int slice_frames, int nframes,
-                     WidenArgs by_step[5]) {
+                     const float* scale, const float* offset, const size_t* fs, size_t src_bytes, uint32_t mask, char* scratch,
+                     int first_frame, int slice_frames, int nframes, WidenArgs by_step[5]) {
     for (int g = 0; g < s.ngroups; ++g) {
         WidenGroup e;
         int members = 0, first = -1;
@@ -1293,6 +1293,8 @@ void fill_widen_args(const jinc_filter& f, const Side& s, const void* const base
             ++members;
             e.plane[s.channel_of[i]] = scratch + s.offset[i] * static_cast<size_t>(slice_frames);
             e.shift[s.channel_of[i]] = static_cast<uint8_t>(shift_of(shift, i));
+            e.scale[s.channel_of[i]] = scale ? scale[i] : 1.f;  // (plane i's pair travels with its channel of the group)
+            e.offset[s.channel_of[i]] = offset ? offset[i] : 0.f;
         }
         const int n = step_of(step, first);
         const size_t frame_stride = (fs && nframes > 1) ? fs[first] : 0;
@@ -1330,9 +1332,11 @@ int merge_widened(const jinc_filter& f, const Side& out, const void* const dst_c
 }
 }  // namespace
 
+// src_scale / src_offset (jinc_filter_process_device_widened_scaled; both nullptr: the unscaled call): the same stand-ins, the same
+// launches, the same report -- the widening kernel's scaled form stores fl32(fl32(float(value) * scale) + offset) in their place.
 void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
                      int src_bits, const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step,
-                     const size_t* dst_fs, int nframes, hipStream_t stream) {
+                     const size_t* dst_fs, int nframes, hipStream_t stream, const float* src_scale, const float* src_offset) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
     const size_t sb = static_cast<size_t>(f.vi_in.component_size), src_bytes = src_bits > 8 ? 2 : 1;
     Side in, out;
@@ -1353,15 +1357,16 @@ void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pit
     }
     check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
     const uint32_t mask = (1u << src_bits) - 1u;
+    const bool scaled = src_scale || src_offset;
     run_on_stand_ins(
         f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
             WidenArgs widen[5];
-            fill_widen_args(f, in, src, src_pitch, src_step, src_shift, src_fs, src_bytes, mask, scratch, k0, slice, nframes, widen);
+            fill_widen_args(f, in, src, src_pitch, src_step, src_shift, src_scale, src_offset, src_fs, src_bytes, mask, scratch, k0, slice, nframes, widen);
             int launches = 0;
             for (int step = 1; step <= 4; ++step)
                 if (widen[step].ngroups) {
-                    hip_check(static_cast<hipError_t>(jinc::launch_widen_samples(widen[step], static_cast<int>(src_bytes), step, static_cast<int>(sb), f.sample_kind(), n, stream)), "widen launch");
+                    hip_check(static_cast<hipError_t>(jinc::launch_widen_samples(widen[step], static_cast<int>(src_bytes), step, static_cast<int>(sb), f.sample_kind(), n, stream, scaled)), "widen launch");
                     ++launches;
                 }
             return launches;
@@ -1451,8 +1456,8 @@ void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t
 namespace {
 // The groups of a narrowed destination as launch arguments, one NarrowArgs per step (fill_args for destination samples of their own size).
 void fill_narrow_args(const jinc_filter& f, const Side& s, void* const base[4], const int pitch[4], const int* step, const int* shift,
-                      const size_t* fs, size_t dst_bytes, float peak, const char* scratch, int first_frame, int slice_frames, int nframes,
-                      NarrowArgs by_step[5]) {
+                      const float* scale, const float* offset, const size_t* fs, size_t dst_bytes, float peak, const char* scratch,
+                      int first_frame, int slice_frames, int nframes, NarrowArgs by_step[5]) {
     for (int g = 0; g < s.ngroups; ++g) {
         NarrowGroup e;
         int members = 0, first = -1;
@@ -1465,6 +1470,8 @@ void fill_narrow_args(const jinc_filter& f, const Side& s, void* const base[4], 
             ++members;
             e.plane[s.channel_of[i]] = scratch + s.offset[i] * static_cast<size_t>(slice_frames);
             e.shift[s.channel_of[i]] = static_cast<uint8_t>(shift_of(shift, i));
+            e.scale[s.channel_of[i]] = scale ? scale[i] : 1.f;  // (plane i's pair travels with its channel of the group)
+            e.offset[s.channel_of[i]] = offset ? offset[i] : 0.f;
         }
         const int n = step_of(step, first);
         const size_t frame_stride = (fs && nframes > 1) ? fs[first] : 0;
@@ -1487,9 +1494,11 @@ void fill_narrow_args(const jinc_filter& f, const Side& s, void* const base[4], 
 }
 }  // namespace
 
+// dst_scale / dst_offset (jinc_filter_process_device_narrowed_scaled; both nullptr: the unscaled call): the same stand-ins, the same
+// launches, the same report -- the narrowing kernel's scaled form takes fl32(fl32(r * scale) + offset) into the same conversion.
 void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
                       void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift, int dst_bits,
-                      const size_t* dst_fs, int nframes, hipStream_t stream) {
+                      const size_t* dst_fs, int nframes, hipStream_t stream, const float* dst_scale, const float* dst_offset) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
     const size_t sb = static_cast<size_t>(f.vi_in.component_size), dst_bytes = dst_bits > 8 ? 2 : 1;
     Side in, out;
@@ -1510,6 +1519,7 @@ void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pi
         if (dst_fs && nframes > 1 && dst_fs[i] % dst_bytes) throw ArgError("JincResize: destination frame stride is not a multiple of the destination sample size.");
     }
     const float peak = static_cast<float>((1u << dst_bits) - 1u);
+    const bool scaled = dst_scale || dst_offset;
     run_on_stand_ins(
         f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
@@ -1525,11 +1535,11 @@ void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pi
         },
         [&](char* scratch, int k0, int slice, int n) {
             NarrowArgs narrow[5];
-            fill_narrow_args(f, out, dst, dst_pitch, dst_step, dst_shift, dst_fs, dst_bytes, peak, scratch, k0, slice, nframes, narrow);
+            fill_narrow_args(f, out, dst, dst_pitch, dst_step, dst_shift, dst_scale, dst_offset, dst_fs, dst_bytes, peak, scratch, k0, slice, nframes, narrow);
             int launches = 0;
             for (int step = 1; step <= 4; ++step)
                 if (narrow[step].ngroups) {
-                    hip_check(static_cast<hipError_t>(jinc::launch_narrow_samples(narrow[step], f.sample_kind(), step, static_cast<int>(dst_bytes), n, stream)), "narrow launch");
+                    hip_check(static_cast<hipError_t>(jinc::launch_narrow_samples(narrow[step], f.sample_kind(), step, static_cast<int>(dst_bytes), n, stream, scaled)), "narrow launch");
                     ++launches;
                 }
             return launches;

@@ -71,6 +71,19 @@ std::string refuse_widened_words(const jinc_filter* f, const char* what, const v
     return std::string();
 }
 
+// What the two scaled calls refuse of their own: a scale or offset of a used plane that is NaN or infinite, a scale that is zero.
+// `side` is "source" (widened) or "destination" (narrowed).  Empty: nothing to refuse.
+std::string refuse_scale_offset(const char* side, const float* scale, const float* offset, int planes) {
+    for (int i = 0; i < planes; ++i) {
+        const std::string of_plane = std::string(side) + " plane " + std::to_string(i);
+        if (scale && std::isnan(scale[i])) return "JincResize: the scale of " + of_plane + " is NaN.";
+        if (scale && std::isinf(scale[i])) return "JincResize: the scale of " + of_plane + " is infinite.";
+        if (scale && scale[i] == 0.f) return "JincResize: the scale of " + of_plane + " is zero.";
+        if (offset && std::isnan(offset[i])) return "JincResize: the offset of " + of_plane + " is NaN.";
+        if (offset && std::isinf(offset[i])) return "JincResize: the offset of " + of_plane + " is infinite.";
+    }
+    return std::string();
+}
 }  // namespace
 
 extern "C" {
@@ -344,22 +357,25 @@ int jinc_filter_process_device_v210(jinc_filter* f, const void* const src[4], co
 
 size_t jinc_v210_row_bytes(int width) { return v210_row_bytes(width); }
 
-int jinc_filter_process_device_widened(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
-                                       const int src_sample_shift[4], int src_bits, const size_t src_frame_stride[4], void* const dst[4],
-                                       const int dst_pitch[4], const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
-                                       void* hip_stream) {
+namespace {
+// jinc_filter_process_device_widened and, with a scale or an offset array given, jinc_filter_process_device_widened_scaled.
+int process_device_widened(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                           const int src_sample_shift[4], int src_bits, const float* src_scale, const float* src_offset,
+                           const size_t src_frame_stride[4], void* const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
+                           const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
     // the filter, src_bits, the steps, the shifts and the source's bases and pitches first (they need no device), then the checks
     // of jinc_filter_process_device_shifted in its order
+    const bool scaled = src_scale || src_offset;  // (a defined rounding, no claim of exactness: every depth into every float type)
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (!f->float_samples())
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened integer sources need an fp32 or binary16 filter, or a bfloat16 filter for 8-bit sources; this filter has " +
                                               std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_shifted).");
     if (src_bits < 8 || src_bits > 16)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: src_bits must be in 8..16 (got " + std::to_string(src_bits) + ").");
-    if (f->half && src_bits > 11)
+    if (!scaled && f->half && src_bits > 11)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: " + std::to_string(src_bits) + "-bit samples are not exact in binary16 (at most 11 bits): "
                                               "widen them into an fp32 filter.");
-    if (f->bf16 && src_bits > 8)
+    if (!scaled && f->bf16 && src_bits > 8)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: " + std::to_string(src_bits) + "-bit samples are not exact in bfloat16 (at most 8 bits): "
                                               "widen them into an fp32 filter.");
     for (const int* step : {src_sample_step, dst_sample_step})
@@ -385,6 +401,8 @@ int jinc_filter_process_device_widened(jinc_filter* f, const void* const src[4],
             return fail(JINC_ERR_INVALID_ARG, "JincResize: source pitch " + std::to_string(src_pitch[i]) + " is smaller than the row of " +
                                                   std::to_string(need) + " bytes at this sample step and size.");
     }
+    const std::string refusal = refuse_scale_offset("source", src_scale, src_offset, f->planecount);
+    if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
     if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
     if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
@@ -393,14 +411,34 @@ int jinc_filter_process_device_widened(jinc_filter* f, const void* const src[4],
     return guarded([&] {
         hip_check(hipSetDevice(f->device), "hipSetDevice");
         enqueue_widened(*f, src, src_pitch, src_sample_step, src_sample_shift, src_bits, src_frame_stride, dst, dst_pitch, dst_sample_step,
-                        dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
+                        dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream), src_scale, src_offset);
     });
 }
+}  // namespace
 
-int jinc_filter_process_device_narrowed(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
-                                        const size_t src_frame_stride[4], void* const dst[4], const int dst_pitch[4],
-                                        const int dst_sample_step[4], const int dst_sample_shift[4], int dst_bits,
-                                        const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+int jinc_filter_process_device_widened(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                                       const int src_sample_shift[4], int src_bits, const size_t src_frame_stride[4], void* const dst[4],
+                                       const int dst_pitch[4], const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
+                                       void* hip_stream) {
+    return process_device_widened(f, src, src_pitch, src_sample_step, src_sample_shift, src_bits, nullptr, nullptr, src_frame_stride, dst,
+                                  dst_pitch, dst_sample_step, dst_frame_stride, nframes, hip_stream);
+}
+
+int jinc_filter_process_device_widened_scaled(jinc_filter* f, const void* const src[4], const int src_pitch[4],
+                                              const int src_sample_step[4], const int src_sample_shift[4], int src_bits,
+                                              const float src_scale[4], const float src_offset[4], const size_t src_frame_stride[4],
+                                              void* const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
+                                              const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    return process_device_widened(f, src, src_pitch, src_sample_step, src_sample_shift, src_bits, src_scale, src_offset, src_frame_stride,
+                                  dst, dst_pitch, dst_sample_step, dst_frame_stride, nframes, hip_stream);
+}
+
+namespace {
+// jinc_filter_process_device_narrowed and, with a scale or an offset array given, jinc_filter_process_device_narrowed_scaled.
+int process_device_narrowed(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                            const size_t src_frame_stride[4], void* const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
+                            const int dst_sample_shift[4], int dst_bits, const float* dst_scale, const float* dst_offset,
+                            const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
     // the filter, dst_bits, the steps, the shifts and the destination's bases and pitches first (they need no device), then the
     // checks of jinc_filter_process_device_shifted in its order
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
@@ -432,6 +470,8 @@ int jinc_filter_process_device_narrowed(jinc_filter* f, const void* const src[4]
             return fail(JINC_ERR_INVALID_ARG, "JincResize: destination pitch " + std::to_string(dst_pitch[i]) + " is smaller than the row of " +
                                                   std::to_string(need) + " bytes at this sample step and size.");
     }
+    const std::string refusal = refuse_scale_offset("destination", dst_scale, dst_offset, f->planecount);
+    if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
     if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
     if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
@@ -440,8 +480,44 @@ int jinc_filter_process_device_narrowed(jinc_filter* f, const void* const src[4]
     return guarded([&] {
         hip_check(hipSetDevice(f->device), "hipSetDevice");
         enqueue_narrowed(*f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_sample_shift, dst_bits,
-                         dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
+                         dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream), dst_scale, dst_offset);
     });
+}
+}  // namespace
+
+int jinc_filter_process_device_narrowed(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                                        const size_t src_frame_stride[4], void* const dst[4], const int dst_pitch[4],
+                                        const int dst_sample_step[4], const int dst_sample_shift[4], int dst_bits,
+                                        const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    return process_device_narrowed(f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_sample_shift,
+                                   dst_bits, nullptr, nullptr, dst_frame_stride, nframes, hip_stream);
+}
+
+int jinc_filter_process_device_narrowed_scaled(jinc_filter* f, const void* const src[4], const int src_pitch[4],
+                                               const int src_sample_step[4], const size_t src_frame_stride[4], void* const dst[4],
+                                               const int dst_pitch[4], const int dst_sample_step[4], const int dst_sample_shift[4],
+                                               int dst_bits, const float dst_scale[4], const float dst_offset[4],
+                                               const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    return process_device_narrowed(f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_sample_shift,
+                                   dst_bits, dst_scale, dst_offset, dst_frame_stride, nframes, hip_stream);
+}
+
+int jinc_code_range(int bits, int range, int plane_kind, float* to_float_scale, float* to_float_offset, float* to_code_scale,
+                    float* to_code_offset) {
+    if (bits < 8 || bits > 16) return fail(JINC_ERR_INVALID_ARG, "JincResize: bits of a code range must be in 8..16 (got " + std::to_string(bits) + ").");
+    if (range != JINC_RANGE_FULL && range != JINC_RANGE_LIMITED)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: the range of a code range must be JINC_RANGE_FULL or JINC_RANGE_LIMITED.");
+    if (plane_kind != JINC_PLANE_LUMA_OR_RGB && plane_kind != JINC_PLANE_CHROMA)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: the plane kind of a code range must be JINC_PLANE_LUMA_OR_RGB or JINC_PLANE_CHROMA.");
+    const bool chroma = plane_kind == JINC_PLANE_CHROMA;
+    const int k = 1 << (bits - 8);
+    const int den = range == JINC_RANGE_LIMITED ? (chroma ? 224 : 219) * k : (1 << bits) - 1;
+    const int zero = range == JINC_RANGE_LIMITED ? (chroma ? 128 : 16) * k : (chroma ? 1 << (bits - 1) : 0);
+    if (to_float_scale) *to_float_scale = static_cast<float>(1.0 / den);  // (computed in double, rounded once)
+    if (to_float_offset) *to_float_offset = static_cast<float>(-static_cast<double>(zero) / den);
+    if (to_code_scale) *to_code_scale = static_cast<float>(den);  // (exact: below 2^24)
+    if (to_code_offset) *to_code_offset = static_cast<float>(zero);
+    return JINC_OK;
 }
 
 int jinc_filter_process_device_widened_packed10(jinc_filter* f, const void* src, int src_pitch, const int src_field_offset[3],
@@ -790,6 +866,70 @@ int jinc_debug_narrow(const void* in, int in_kind, void* out, int n, int dst_bit
         hip_check(static_cast<hipError_t>(jinc::launch_narrow_samples(a, kind, 1, static_cast<int>(dst_bytes), 1, nullptr)), "narrow launch");
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         bounce_download(out, d_out, dst_bytes * n, "download of the samples");
+        (void)hipFree(d_in);
+        (void)hipFree(d_out);
+    });
+}
+
+int jinc_debug_narrow_scaled(const void* in, int in_kind, void* out, int n, int dst_bits, int shift, float scale, float offset, int device) {
+    const bool kind_ok = in_kind == JINC_SAMPLE_DEFAULT || in_kind == JINC_SAMPLE_FLOAT16 || in_kind == JINC_SAMPLE_BFLOAT16;
+    if (!in || !out || n < 0 || !kind_ok || dst_bits < 8 || dst_bits > 16) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    const size_t in_bytes = in_kind == JINC_SAMPLE_DEFAULT ? 4 : 2, dst_bytes = dst_bits > 8 ? 2 : 1;
+    if (shift < 0 || shift > static_cast<int>(8 * dst_bytes) - dst_bits) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    if (!std::isfinite(scale) || !std::isfinite(offset) || scale == 0.f) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    if (n == 0) return JINC_OK;
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        char *d_in = nullptr, *d_out = nullptr;
+        hip_check(hipMalloc(&d_in, in_bytes * (n + 1)), "hipMalloc");
+        hip_check(hipMalloc(&d_out, dst_bytes * (n + 1)), "hipMalloc");
+        bounce_upload(d_in, in, in_bytes * n, "upload of the values");
+        jinc::NarrowArgs a;  // one group of one dense row: whole lanes by 16-byte accesses, the rest sample by sample
+        a.ngroups = 1;
+        a.peak = static_cast<float>((1u << dst_bits) - 1u);
+        jinc::NarrowGroup& g = a.g[0];
+        g.packed = d_out, g.plane[0] = d_in;
+        g.packed_pitch = static_cast<uint32_t>(dst_bytes * n), g.plane_pitch = static_cast<uint32_t>(in_bytes * n);
+        g.width = static_cast<uint32_t>(n), g.rows = 1, g.unit = 16;
+        g.vec_pixels = g.width / static_cast<uint32_t>(16 / dst_bytes) * static_cast<uint32_t>(16 / dst_bytes);
+        g.shift[0] = static_cast<uint8_t>(shift);
+        g.scale[0] = scale, g.offset[0] = offset;
+        const int kind = in_kind == JINC_SAMPLE_FLOAT16 ? jinc::kSampleHalf : in_kind == JINC_SAMPLE_BFLOAT16 ? jinc::kSampleBFloat16 : 0;
+        hip_check(static_cast<hipError_t>(jinc::launch_narrow_samples(a, kind, 1, static_cast<int>(dst_bytes), 1, nullptr, true)), "narrow launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bounce_download(out, d_out, dst_bytes * n, "download of the samples");
+        (void)hipFree(d_in);
+        (void)hipFree(d_out);
+    });
+}
+
+int jinc_debug_widen_scaled(const void* in, int src_bits, int shift, float scale, float offset, int out_kind, void* out, int n, int device) {
+    const bool kind_ok = out_kind == JINC_SAMPLE_DEFAULT || out_kind == JINC_SAMPLE_FLOAT16 || out_kind == JINC_SAMPLE_BFLOAT16;
+    if (!in || !out || n < 0 || !kind_ok || src_bits < 8 || src_bits > 16) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    const size_t src_bytes = src_bits > 8 ? 2 : 1, out_bytes = out_kind == JINC_SAMPLE_DEFAULT ? 4 : 2;
+    if (shift < 0 || shift > static_cast<int>(8 * src_bytes) - src_bits) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    if (!std::isfinite(scale) || !std::isfinite(offset) || scale == 0.f) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    if (n == 0) return JINC_OK;
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        char *d_in = nullptr, *d_out = nullptr;
+        hip_check(hipMalloc(&d_in, src_bytes * (n + 1)), "hipMalloc");
+        hip_check(hipMalloc(&d_out, out_bytes * (n + 1)), "hipMalloc");
+        bounce_upload(d_in, in, src_bytes * n, "upload of the samples");
+        jinc::WidenArgs a;  // one group of one dense row: whole lanes by 16-byte accesses, the rest sample by sample
+        a.ngroups = 1;
+        a.mask = (1u << src_bits) - 1u;
+        jinc::WidenGroup& g = a.g[0];
+        g.packed = d_in, g.plane[0] = d_out;
+        g.packed_pitch = static_cast<uint32_t>(src_bytes * n), g.plane_pitch = static_cast<uint32_t>(out_bytes * n);
+        g.width = static_cast<uint32_t>(n), g.rows = 1, g.unit = 16;
+        g.vec_pixels = g.width / static_cast<uint32_t>(16 / src_bytes) * static_cast<uint32_t>(16 / src_bytes);
+        g.shift[0] = static_cast<uint8_t>(shift);
+        g.scale[0] = scale, g.offset[0] = offset;
+        const int kind = out_kind == JINC_SAMPLE_FLOAT16 ? jinc::kSampleHalf : out_kind == JINC_SAMPLE_BFLOAT16 ? jinc::kSampleBFloat16 : 0;
+        hip_check(static_cast<hipError_t>(jinc::launch_widen_samples(a, static_cast<int>(src_bytes), 1, static_cast<int>(out_bytes), kind, 1, nullptr, true)), "widen launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bounce_download(out, d_out, out_bytes * n, "download of the samples");
         (void)hipFree(d_in);
         (void)hipFree(d_out);
     });

@@ -341,9 +341,12 @@ size_t v210_row_bytes(int width);  // 16 * ceil(width / 6); 0 for width < 1
 // ... enqueue on an fp32 / binary16 filter for INTEGER source samples of src_bytes (1 or 2) holding src_bits bits above `shift`:
 // every source plane is widened into a dense stand-in of the filter's sample type; the destination side is enqueue_strided's.
 // Filter, src_bits, steps, shifts, source bases and source pitches have been checked by filter.cpp.
+// src_scale / src_offset (four floats in plane order, either may be nullptr; both nullptr: the unscaled call): the stand-ins hold
+// fl32(fl32(float(value) * scale) + offset) rounded to the filter's type -- same stand-ins, same launches, same report.
 void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
                      int src_bits, const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step,
-                     const size_t* dst_fs, int nframes, hipStream_t stream);
+                     const size_t* dst_fs, int nframes, hipStream_t stream, const float* src_scale = nullptr,
+                     const float* src_offset = nullptr);
 // ... enqueue on an fp32 / binary16 filter whose SOURCE is one buffer of 10:10:10:2 words (fields: the three bit offsets in plane
 // order) or of v210 blocks: the three source planes are widened into dense stand-ins of the filter's sample type
 // (widen_fields_kernel / widen_v210_kernel); the destination side is enqueue_strided's.  Filter, offsets, destination steps and the
@@ -356,9 +359,11 @@ void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t
 // 16-bit words) at `shift` in their container: every destination plane takes a dense stand-in of the filter's sample type and
 // narrow_samples_kernel stores lrintf(clamp(r, 0, peak)) << shift from it; the source side is enqueue_strided's (no shifts).
 // Filter, dst_bits, steps, shifts, destination bases and destination pitches have been checked by filter.cpp.
+// dst_scale / dst_offset (as above): the stored sample is lrintf(clamp(fl32(fl32(r * scale) + offset), 0, peak)) << shift.
 void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
                       void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift, int dst_bits,
-                      const size_t* dst_fs, int nframes, hipStream_t stream);
+                      const size_t* dst_fs, int nframes, hipStream_t stream, const float* dst_scale = nullptr,
+                      const float* dst_offset = nullptr);
 // ... the channel groups of one side's planes (pure: test header jinc_debug_strided_groups); returns their number
 int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
                    const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]);

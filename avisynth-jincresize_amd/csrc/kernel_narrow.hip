@@ -12,6 +12,8 @@
 // 16-byte loads per plane and N 16-byte stores (dwords where the group's alignment allows no more); tails, unaligned groups and
 // groups with a channel missing store sample by sample and only their own samples.  The destination is never read.  Plain C++: no
 // assembly, no LDS, no scratch.
+// The scaled forms (jinc_filter_process_device_narrowed_scaled) are the same kernel with one v_mul_f32 and one v_add_f32 per sample
+// in front of the conversion (scale[c], offset[c] of the group's channel in scalar registers; -ffp-contract=off keeps them apart).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -21,44 +23,54 @@ namespace jinc {
 namespace {
 
 // Row blockIdx.x * 4 + wave of frame blockIdx.y of group blockIdx.z.
-template <int KIND, int N, int DB>
+template <int KIND, int N, int DB, bool Scaled>
 __global__ __launch_bounds__(256) void narrow_samples_kernel(const NarrowArgs a) {
     const NarrowGroup& g = a.g[blockIdx.z];
     const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row < g.rows) narrow::narrow_row<KIND, N, DB>(g, a.peak, blockIdx.y, row, threadIdx.x & 63u);
+    if (row < g.rows) narrow::narrow_row<KIND, N, DB, Scaled>(g, a.peak, blockIdx.y, row, threadIdx.x & 63u);
 }
 
-template <int KIND, int N, int DB>
+template <int KIND, int N, int DB, bool Scaled>
 int launch(const NarrowArgs& a, int nframes, hipStream_t s) {
     uint32_t rows = 0;
     for (int k = 0; k < a.ngroups; ++k) rows = a.g[k].rows > rows ? a.g[k].rows : rows;
     if (a.ngroups <= 0 || nframes <= 0 || rows == 0) return hipSuccess;
     const dim3 grid((rows + 3) / 4, static_cast<uint32_t>(nframes), static_cast<uint32_t>(a.ngroups));
-    hipLaunchKernelGGL((narrow_samples_kernel<KIND, N, DB>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((narrow_samples_kernel<KIND, N, DB, Scaled>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-template <int KIND, int DB>
+template <int KIND, int DB, bool Scaled>
 int launch_by_step(const NarrowArgs& a, int step, int nframes, hipStream_t s) {
     switch (step) {
-        case 1: return launch<KIND, 1, DB>(a, nframes, s);
-        case 2: return launch<KIND, 2, DB>(a, nframes, s);
-        case 3: return launch<KIND, 3, DB>(a, nframes, s);
-        case 4: return launch<KIND, 4, DB>(a, nframes, s);
+        case 1: return launch<KIND, 1, DB, Scaled>(a, nframes, s);
+        case 2: return launch<KIND, 2, DB, Scaled>(a, nframes, s);
+        case 3: return launch<KIND, 3, DB, Scaled>(a, nframes, s);
+        case 4: return launch<KIND, 4, DB, Scaled>(a, nframes, s);
     }
     return hipErrorInvalidValue;
 }
 
-template <int KIND>
+template <int KIND, bool Scaled>
 int launch_by_size(const NarrowArgs& a, int step, int dst_bytes, int nframes, hipStream_t s) {
-    if (dst_bytes == 1) return launch_by_step<KIND, 1>(a, step, nframes, s);
-    if (dst_bytes == 2) return launch_by_step<KIND, 2>(a, step, nframes, s);
+    if (dst_bytes == 1) return launch_by_step<KIND, 1, Scaled>(a, step, nframes, s);
+    if (dst_bytes == 2) return launch_by_step<KIND, 2, Scaled>(a, step, nframes, s);
     return hipErrorInvalidValue;
+}
+
+template <bool Scaled>
+int launch_by_kind(const NarrowArgs& a, int in_kind, int step, int dst_bytes, int nframes, hipStream_t s) {
+    switch (in_kind) {
+        case 0: return launch_by_size<0, Scaled>(a, step, dst_bytes, nframes, s);
+        case kSampleHalf: return launch_by_size<kSampleHalf, Scaled>(a, step, dst_bytes, nframes, s);
+        case kSampleBFloat16: return launch_by_size<kSampleBFloat16, Scaled>(a, step, dst_bytes, nframes, s);
+    }
+    return hipErrorInvalidValue;  // (no kernel for this shape: an error, never a silent skip)
 }
 
 }  // namespace
 
-int launch_narrow_samples(const NarrowArgs& a, int in_kind, int step, int dst_bytes, int nframes, void* stream) {
+int launch_narrow_samples(const NarrowArgs& a, int in_kind, int step, int dst_bytes, int nframes, void* stream, bool scaled) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (a.ngroups > 4 || (dst_bytes != 1 && dst_bytes != 2)) return hipErrorInvalidValue;
     // the peak of a byte is 255 (round_sample_u8 saturates there); a word's lies in 511 .. 65535 and is 2^bits - 1
@@ -72,12 +84,7 @@ int launch_narrow_samples(const NarrowArgs& a, int in_kind, int step, int dst_by
             if (dst_bytes == 1 ? g.shift[c] != 0 : (static_cast<uint32_t>(a.peak) << g.shift[c]) > 65535u) return hipErrorInvalidValue;
         }
     }
-    switch (in_kind) {
-        case 0: return launch_by_size<0>(a, step, dst_bytes, nframes, s);
-        case kSampleHalf: return launch_by_size<kSampleHalf>(a, step, dst_bytes, nframes, s);
-        case kSampleBFloat16: return launch_by_size<kSampleBFloat16>(a, step, dst_bytes, nframes, s);
-    }
-    return hipErrorInvalidValue;  // (no kernel for this shape: an error, never a silent skip)
+    return scaled ? launch_by_kind<true>(a, in_kind, step, dst_bytes, nframes, s) : launch_by_kind<false>(a, in_kind, step, dst_bytes, nframes, s);
 }
 
 }  // namespace jinc

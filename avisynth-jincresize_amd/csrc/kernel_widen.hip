@@ -11,6 +11,9 @@
 // division or a modulo.  The row function is widen_rows.h: a lane owns 16 / SB whole pixels per step, N 16-byte loads (dwords where
 // the group's alignment allows no more) and OB / SB 16-byte stores per plane; tails, unaligned groups and the last pixel of a group
 // with a channel missing move sample by sample.  The source is read only.
+// The scaled forms (jinc_filter_process_device_widened_scaled) are the same kernel with one v_mul_f32 and one v_add_f32 per sample
+// behind the conversion (scale[c], offset[c] of the group's channel in scalar registers; -ffp-contract=off keeps them apart) and, for
+// 16-bit planes, the round-to-nearest-even conversions the resampling kernels store with: words go into bfloat16 planes there.
 //
 // Two more sources whose samples neither a step nor a shift addresses (jinc_filter_process_device_widened_packed10 / _v210;
 // dispatch.cpp enqueue_widened_packed10 / enqueue_widened_v210): 10:10:10:2 words -- Y410, R10G10B10A2 and kin, three 10-bit fields
@@ -31,30 +34,30 @@ namespace jinc {
 namespace {
 
 // Row blockIdx.x * 4 + wave of frame blockIdx.y of group blockIdx.z.
-template <int SB, int N, int OB, int KIND>
+template <int SB, int N, int OB, int KIND, bool Scaled>
 __global__ __launch_bounds__(256) void widen_samples_kernel(const WidenArgs a) {
     const WidenGroup& g = a.g[blockIdx.z];
     const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row < g.rows) widen::widen_row<SB, N, OB, KIND>(g, a.mask, blockIdx.y, row, threadIdx.x & 63u);
+    if (row < g.rows) widen::widen_row<SB, N, OB, KIND, Scaled>(g, a.mask, blockIdx.y, row, threadIdx.x & 63u);
 }
 
-template <int SB, int N, int OB, int KIND>
+template <int SB, int N, int OB, int KIND, bool Scaled>
 int launch(const WidenArgs& a, int nframes, hipStream_t s) {
     uint32_t rows = 0;
     for (int k = 0; k < a.ngroups; ++k) rows = a.g[k].rows > rows ? a.g[k].rows : rows;
     if (a.ngroups <= 0 || nframes <= 0 || rows == 0) return hipSuccess;
     const dim3 grid((rows + 3) / 4, static_cast<uint32_t>(nframes), static_cast<uint32_t>(a.ngroups));
-    hipLaunchKernelGGL((widen_samples_kernel<SB, N, OB, KIND>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((widen_samples_kernel<SB, N, OB, KIND, Scaled>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-template <int SB, int OB, int KIND = 0>
+template <int SB, int OB, int KIND = 0, bool Scaled = false>
 int launch_by_step(const WidenArgs& a, int step, int nframes, hipStream_t s) {
     switch (step) {
-        case 1: return launch<SB, 1, OB, KIND>(a, nframes, s);
-        case 2: return launch<SB, 2, OB, KIND>(a, nframes, s);
-        case 3: return launch<SB, 3, OB, KIND>(a, nframes, s);
-        case 4: return launch<SB, 4, OB, KIND>(a, nframes, s);
+        case 1: return launch<SB, 1, OB, KIND, Scaled>(a, nframes, s);
+        case 2: return launch<SB, 2, OB, KIND, Scaled>(a, nframes, s);
+        case 3: return launch<SB, 3, OB, KIND, Scaled>(a, nframes, s);
+        case 4: return launch<SB, 4, OB, KIND, Scaled>(a, nframes, s);
     }
     return hipErrorInvalidValue;
 }
@@ -109,7 +112,7 @@ int launch_widen_v210(const V210Args& a, int out_bytes, int nframes, void* strea
     return hipGetLastError();
 }
 
-int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int out_kind, int nframes, void* stream) {
+int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int out_kind, int nframes, void* stream, bool scaled) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (a.ngroups > 4) return hipErrorInvalidValue;
     for (int k = 0; k < a.ngroups; ++k) {
@@ -118,6 +121,22 @@ int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_by
         if (g.vec_pixels > g.width || g.vec_pixels % lane_pixels || (g.vec_pixels && g.unit != 16 && g.unit != 4)) return hipErrorInvalidValue;
         for (int c = 0; c < 4; ++c)
             if (src_bytes == 1 && g.shift[c]) return hipErrorInvalidValue;  // (a byte takes no shift)
+    }
+    if (scaled) {  // a defined rounding, no claim of exactness: every depth into every type
+        if (a.mask > 0xffffu || (src_bytes == 1 && a.mask != 0xffu)) return hipErrorInvalidValue;
+        if (out_kind == kSampleBFloat16) {
+            if (out_bytes != 2) return hipErrorInvalidValue;
+            if (src_bytes == 1) return launch_by_step<1, 2, kSampleBFloat16, true>(a, step, nframes, s);
+            if (src_bytes == 2) return launch_by_step<2, 2, kSampleBFloat16, true>(a, step, nframes, s);
+            return hipErrorInvalidValue;
+        }
+        switch (src_bytes * 8 + out_bytes) {
+            case 1 * 8 + 4: return launch_by_step<1, 4, 0, true>(a, step, nframes, s);
+            case 1 * 8 + 2: return launch_by_step<1, 2, 0, true>(a, step, nframes, s);
+            case 2 * 8 + 4: return launch_by_step<2, 4, 0, true>(a, step, nframes, s);
+            case 2 * 8 + 2: return launch_by_step<2, 2, 0, true>(a, step, nframes, s);
+        }
+        return hipErrorInvalidValue;
     }
     if (out_bytes == 2 && a.mask > 2047u) return hipErrorInvalidValue;  // (not exact in binary16)
     if (out_kind == kSampleBFloat16) {  // bytes only: nine bits are not exact in bfloat16

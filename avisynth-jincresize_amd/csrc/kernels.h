@@ -582,6 +582,7 @@ struct WidenGroup {
     size_t packed_frame_stride = 0, plane_frame_stride = 0;
     uint32_t packed_pitch = 0, plane_pitch = 0, width = 0, rows = 0, vec_pixels = 0, unit = 0;
     uint8_t shift[4] = {0, 0, 0, 0};
+    float scale[4] = {1.f, 1.f, 1.f, 1.f}, offset[4] = {0.f, 0.f, 0.f, 0.f};  // read by the scaled forms only
 };
 struct WidenArgs {
     WidenGroup g[4];
@@ -591,7 +592,10 @@ struct WidenArgs {
 // One launch over every group and frame of `a`: src_bytes 1 or 2 (a byte takes no shift: mask 0xff, shifts 0); step 1 .. 4 (the
 // same for all groups of a launch); out_bytes 4 (fp32) or 2 (out_kind 0 / kSampleHalf: binary16, every value must be <= 2047 to be
 // exact; out_kind kSampleBFloat16: bfloat16, src_bytes 1 only -- nine bits are not exact).
-int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int out_kind, int nframes, void* stream);
+// scaled (jinc_filter_process_device_widened_scaled): plane c holds fl32(fl32(float(value) * scale[c]) + offset[c]) -- two fp32
+// roundings, never an FMA -- narrowed round-to-nearest-even into 16-bit planes; the conversion is a defined rounding, so neither the
+// 2047 rule nor the bytes-only rule of bfloat16 applies.
+int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int out_kind, int nframes, void* stream, bool scaled = false);
 // 10:10:10:2 words / v210 blocks -> the three dense planes of an fp32 / binary16 filter (kernel_widen.hip, widen_fields_rows.h,
 // widen_v210_rows.h; jinc_filter_process_device_widened_packed10 / _v210).  The records are FieldArgs and V210Args as they are, read
 // with samples of out_bytes (4: fp32, 2: binary16) on the plane side: plane c holds float / binary16 of the 10-bit field value at
@@ -616,6 +620,7 @@ struct NarrowGroup {
     size_t packed_frame_stride = 0, plane_frame_stride = 0;
     uint32_t packed_pitch = 0, plane_pitch = 0, width = 0, rows = 0, vec_pixels = 0, unit = 0;
     uint8_t shift[4] = {0, 0, 0, 0};
+    float scale[4] = {1.f, 1.f, 1.f, 1.f}, offset[4] = {0.f, 0.f, 0.f, 0.f};  // read by the scaled forms only
 };
 struct NarrowArgs {
     NarrowGroup g[4];
@@ -624,7 +629,9 @@ struct NarrowArgs {
 };
 // One launch over every group and frame of `a`: in_kind 0 (fp32), kSampleHalf or kSampleBFloat16; step 1 .. 4 (the same for all
 // groups of a launch); dst_bytes 1 (peak 255, shifts 0) or 2 (peak 511 .. 65535, peak << shift below 65536).
-int launch_narrow_samples(const NarrowArgs& a, int in_kind, int step, int dst_bytes, int nframes, void* stream);
+// scaled (jinc_filter_process_device_narrowed_scaled): the stored sample is
+// lrintf(clamp(fl32(fl32(result * scale[c]) + offset[c]), 0, peak)) << shift[c] -- two fp32 roundings, never an FMA.
+int launch_narrow_samples(const NarrowArgs& a, int in_kind, int step, int dst_bytes, int nframes, void* stream, bool scaled = false);
 
 // Measurement hook (kernel_probe.hip): `samplers` single-lane workgroups stamp the shader clock counter and the 100 MHz
 // real-time counter until *stop_flag (device memory) becomes non-zero or max_seconds pass; out[2 k] = shader ticks,

@@ -16,6 +16,11 @@
 // What is left moves sample by sample under a width guard: a row's tail, groups whose base, pitch or frame stride is no multiple of
 // 4 bytes and groups with a channel missing (vec_pixels 0: only the given channels' samples may be stored to).  Nothing beyond
 // `width` samples is read from a plane or stored to a channel; the destination is never read, the planes are never written.
+//
+// The scaled form (trailing template parameter Scaled; jinc_filter_process_device_narrowed_scaled): channel c of a pixel is
+// lrintf(clamp(fl32(fl32(r * scale[c]) + offset[c]), 0, peak)) << shift[c] -- one multiply and one add in front of the same
+// conversions, two fp32 roundings, never an FMA, in the vector loop and in the sample-by-sample loop alike.  scale[c] and offset[c]
+// are the same in every lane, as shift[c]; the unscaled form reads neither.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -132,8 +137,21 @@ JINC_NARROW_HD uint32_t word_pair_of(float a, float b, float peak) {  // (a) in 
 #endif
 }
 
+// fl32(fl32(r * scale) + offset): a multiply and an add of their own (v_mul_f32, v_add_f32), whatever the build's contraction setting.
+JINC_NARROW_HD float scaled_value(float r, float scale, float offset) {
+#pragma clang fp contract(off)
+    const float product = r * scale;
+    return product + offset;
+}
+// Sample i of the loaded dwords / sample x of a row as the conversion takes it.
+template <int KIND, bool Scaled>
+JINC_NARROW_HD float result_at(const uint32_t* w, int i, float scale, float offset) {
+    if constexpr (Scaled) return scaled_value(value_at<KIND>(w, i), scale, offset);
+    else return value_at<KIND>(w, i);
+}
+
 // Lane `lane` of the wave that owns row `row` of frame `frame` of group g.
-template <int KIND, int N, int DB>
+template <int KIND, int N, int DB, bool Scaled = false>
 JINC_NARROW_HD void narrow_row(const NarrowGroup& g, float peak, uint32_t frame, uint32_t row, uint32_t lane) {
     static_assert((KIND == 0 || KIND == kSampleHalf || KIND == kSampleBFloat16) && N >= 1 && N <= 4 && (DB == 1 || DB == 2), "no such form");
     constexpr int IB = input_bytes(KIND);
@@ -149,19 +167,21 @@ JINC_NARROW_HD void narrow_row(const NarrowGroup& g, float peak, uint32_t frame,
         for (int c = 0; c < N; ++c) {
             uint32_t in[4 * kLoads];
             const char* plane = g.plane[c] + dense + static_cast<size_t>(x) * IB;
+            float sc = 1.f, of = 0.f;
+            if constexpr (Scaled) sc = g.scale[c], of = g.offset[c];
 #pragma unroll
             for (int k = 0; k < kLoads; ++k) load16(plane + 16 * k, in + 4 * k);
             if constexpr (DB == 1) {  // (a byte takes no shift)
 #pragma unroll
                 for (int p = 0; p < static_cast<int>(P); ++p) {
                     const int i = p * N + c;
-                    out[i >> 2] |= byte_of(value_at<KIND>(in, p)) << (8 * (i & 3));
+                    out[i >> 2] |= byte_of(result_at<KIND, Scaled>(in, p, sc, of)) << (8 * (i & 3));
                 }
             } else {
                 const uint32_t sh = g.shift[c];  // (peak << sh stays below 65536: nothing crosses from the low half into the high one)
 #pragma unroll
                 for (int p = 0; p < static_cast<int>(P); p += 2) {
-                    const uint32_t pair = word_pair_of(value_at<KIND>(in, p), value_at<KIND>(in, p + 1), peak) << sh;
+                    const uint32_t pair = word_pair_of(result_at<KIND, Scaled>(in, p, sc, of), result_at<KIND, Scaled>(in, p + 1, sc, of), peak) << sh;
                     if constexpr (N == 1) {
                         out[p >> 1] = pair;
                     } else {
@@ -178,7 +198,8 @@ JINC_NARROW_HD void narrow_row(const NarrowGroup& g, float peak, uint32_t frame,
 #pragma unroll
         for (int c = 0; c < N; ++c) {
             if (!g.plane[c]) continue;
-            const float r = value_in_row<KIND>(g.plane[c] + dense, x);
+            float r = value_in_row<KIND>(g.plane[c] + dense, x);
+            if constexpr (Scaled) r = scaled_value(r, g.scale[c], g.offset[c]);
             if constexpr (DB == 1) reinterpret_cast<uint8_t*>(packed)[static_cast<size_t>(x) * N + c] = static_cast<uint8_t>(byte_of(r));
             else reinterpret_cast<uint16_t*>(packed)[static_cast<size_t>(x) * N + c] = static_cast<uint16_t>(word_of(r, peak) << g.shift[c]);
         }

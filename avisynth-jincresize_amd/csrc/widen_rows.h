@@ -16,7 +16,15 @@
 // What is left moves sample by sample under a width guard: a row's tail, groups whose base, pitch or frame stride is no multiple of
 // 4 bytes (vec_pixels 0), and the last pixel of a group with a channel missing, whose missing samples may lie behind the end of the
 // caller's buffer.  Nothing beyond `width` samples is read from a given channel or stored to a plane; the source is never written.
+//
+// The scaled form (trailing template parameter Scaled; jinc_filter_process_device_widened_scaled): plane c holds
+// s = fl32(fl32(float(value) * scale[c]) + offset[c]) -- one multiply and one add behind the conversion, two fp32 roundings, never an
+// FMA -- and 16-bit planes hold s narrowed round-to-nearest-even (binary16: overflow to +-inf, subnormals kept) by the conversions
+// the resampling kernels store with (device_common.hpp round_pair_f16 / round_pair_bf16 / half_bits / bf16_bits; on the host the
+// same roundings in integer arithmetic).  The rounding is defined, not exact, so words go into bfloat16 planes too.  scale[c] and
+// offset[c] are the same in every lane, as shift[c]; the unscaled form reads neither.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -24,6 +32,7 @@
 #include "kernels.h"
 
 #if defined(__HIPCC__)
+#include "device_common.hpp"
 #define JINC_WIDEN_HD __host__ __device__ __forceinline__
 #else
 #define JINC_WIDEN_HD inline
@@ -94,11 +103,71 @@ JINC_WIDEN_HD uint32_t narrow_bits(float v) {
     else return half_bits(v);
 }
 
+// ---- the scaled form ----
+// fl32(fl32(v * scale) + offset): a multiply and an add of their own (v_mul_f32, v_add_f32), whatever the build's contraction setting.
+JINC_WIDEN_HD float scaled_value(float v, float scale, float offset) {
+#pragma clang fp contract(off)
+    const float product = v * scale;
+    return product + offset;
+}
+#if !defined(__HIP_DEVICE_COMPILE__)
+// fp32 -> binary16, round to nearest even (host: no half type needed): overflow to +-inf, subnormals kept, a NaN stays one.
+JINC_WIDEN_HD uint32_t host_half_rne(float v) {
+    const uint32_t f = float_bits(v), sign = (f >> 16) & 0x8000u, a = f & 0x7fffffffu;
+    if (a >= 0x7f800000u) return sign | 0x7c00u | (a > 0x7f800000u ? 0x200u : 0u);
+    if (a < 0x38800000u) {  // below 2^-14: a multiple of 2^-24 -- |v| x 2^24 is exact, nearbyintf rounds half to even (1024 is 2^-14)
+        float m;
+        memcpy(&m, &a, 4);
+        return sign | static_cast<uint32_t>(nearbyintf(m * 16777216.f));
+    }
+    const uint32_t r = a + 0xfffu + ((a >> 13) & 1u);  // (a carry out of the mantissa raises the exponent; past 65504 that is 0x7c00, inf)
+    const uint32_t h = (r - (112u << 23)) >> 13;
+    return sign | (h > 0x7c00u ? 0x7c00u : h);
+}
+// fp32 -> bfloat16, round to nearest even: the upper half of the bits plus the carry of the lower half (+-inf from 0x7f7f8000 on).
+JINC_WIDEN_HD uint32_t host_bf16_rne(float v) {
+    const uint32_t f = float_bits(v);
+    if ((f & 0x7fffffffu) > 0x7f800000u) return (f >> 16) | 0x40u;  // a NaN stays a NaN
+    return (f + 0x7fffu + ((f >> 16) & 1u)) >> 16;
+}
+#endif
+// The 16-bit sample of ANY fp32 value, rounded to nearest even.
+template <int KIND>
+JINC_WIDEN_HD uint32_t rounded_bits(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (KIND == kSampleBFloat16) return jinc::bf16_bits(v);
+    else return jinc::half_bits(v);
+#else
+    if constexpr (KIND == kSampleBFloat16) return host_bf16_rne(v);
+    else return host_half_rne(v);
+#endif
+}
+// Two 16-bit samples as one dword, (a) in the low half.
+template <int KIND, bool Scaled>
+JINC_WIDEN_HD uint32_t pair_bits(float a, float b) {
+    if constexpr (!Scaled) {
+        return narrow_bits<KIND>(a) | (narrow_bits<KIND>(b) << 16);
+    } else {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (KIND == kSampleBFloat16) return round_pair_bf16(a, b);
+        else return round_pair_f16(a, b);
+#else
+        return rounded_bits<KIND>(a) | (rounded_bits<KIND>(b) << 16);
+#endif
+    }
+}
+// Sample i of the loaded dwords as the plane holds it in fp32.
+template <int SB, bool Scaled>
+JINC_WIDEN_HD float sample_at(const uint32_t* w, int i, uint32_t shift, uint32_t mask, float scale, float offset) {
+    if constexpr (Scaled) return scaled_value(value_at<SB>(w, i, shift, mask), scale, offset);
+    else return value_at<SB>(w, i, shift, mask);
+}
+
 // Lane `lane` of the wave that owns row `row` of frame `frame` of group g.
-template <int SB, int N, int OB, int KIND = 0>
+template <int SB, int N, int OB, int KIND = 0, bool Scaled = false>
 JINC_WIDEN_HD void widen_row(const WidenGroup& g, uint32_t mask, uint32_t frame, uint32_t row, uint32_t lane) {
     static_assert((SB == 1 || SB == 2) && N >= 1 && N <= 4 && (OB == 4 || OB == 2), "no such form");
-    static_assert(KIND == 0 || KIND == kSampleHalf || (KIND == kSampleBFloat16 && OB == 2 && SB == 1), "no such form");
+    static_assert(KIND == 0 || KIND == kSampleHalf || (KIND == kSampleBFloat16 && OB == 2 && (SB == 1 || Scaled)), "no such form");
     constexpr uint32_t P = 16 / SB;          // pixels a lane owns per step
     constexpr int kVectors = OB / SB;        // 16-byte vectors of P converted samples
     constexpr int kPerVector = 16 / OB;      // samples in one of them
@@ -111,6 +180,8 @@ JINC_WIDEN_HD void widen_row(const WidenGroup& g, uint32_t mask, uint32_t frame,
         for (int c = 0; c < N; ++c) {
             if (!g.plane[c]) continue;
             const uint32_t sh = g.shift[c];
+            float sc = 1.f, of = 0.f;
+            if constexpr (Scaled) sc = g.scale[c], of = g.offset[c];
             char* out = g.plane[c] + dense + static_cast<size_t>(x) * OB;
 #pragma unroll
             for (int v = 0; v < kVectors; ++v) {
@@ -118,8 +189,8 @@ JINC_WIDEN_HD void widen_row(const WidenGroup& g, uint32_t mask, uint32_t frame,
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int p = v * kPerVector + (OB == 4 ? k : 2 * k);  // the pixel of dword k's (first) sample
-                    if constexpr (OB == 4) o[k] = float_bits(value_at<SB>(in, p * N + c, sh, mask));
-                    else o[k] = narrow_bits<KIND>(value_at<SB>(in, p * N + c, sh, mask)) | (narrow_bits<KIND>(value_at<SB>(in, (p + 1) * N + c, sh, mask)) << 16);
+                    if constexpr (OB == 4) o[k] = float_bits(sample_at<SB, Scaled>(in, p * N + c, sh, mask, sc, of));
+                    else o[k] = pair_bits<KIND, Scaled>(sample_at<SB, Scaled>(in, p * N + c, sh, mask, sc, of), sample_at<SB, Scaled>(in, (p + 1) * N + c, sh, mask, sc, of));
                 }
                 store16(out + 16 * v, o);
             }
@@ -132,8 +203,10 @@ JINC_WIDEN_HD void widen_row(const WidenGroup& g, uint32_t mask, uint32_t frame,
             uint32_t raw;
             if constexpr (SB == 1) raw = reinterpret_cast<const uint8_t*>(packed)[static_cast<size_t>(x) * N + c];
             else raw = reinterpret_cast<const uint16_t*>(packed)[static_cast<size_t>(x) * N + c];
-            const float v = value_of<SB>(raw, g.shift[c], mask);
+            float v = value_of<SB>(raw, g.shift[c], mask);
+            if constexpr (Scaled) v = scaled_value(v, g.scale[c], g.offset[c]);
             if constexpr (OB == 4) reinterpret_cast<float*>(g.plane[c] + dense)[x] = v;
+            else if constexpr (Scaled) reinterpret_cast<uint16_t*>(g.plane[c] + dense)[x] = static_cast<uint16_t>(rounded_bits<KIND>(v));
             else reinterpret_cast<uint16_t*>(g.plane[c] + dense)[x] = static_cast<uint16_t>(narrow_bits<KIND>(v));
         }
     }

@@ -442,7 +442,8 @@ JINC_API int jinc_filter_process_device_widened(jinc_filter *f, const void *cons
  *   CONSEQUENCE.  The integer filters convert every source sample to float before the multiply, so on an fp32 filter whose source
  *   planes hold integers in 0 .. peak, with dst_bits equal to an integer format's depth, the result equals that integer filter's
  *   jinc_filter_process_device output, bit for bit.
- *   No scale or offset lies between the float range and the code values, nothing is dithered, no colour is converted.
+ *   No scale or offset lies between the float range and the code values here (jinc_filter_process_device_narrowed_scaled below
+ *   has one), nothing is dithered, no colour is converted.
  * As in the shifted call: no destination byte is stored to unless it belongs to a sample of a given plane (the X of BGRX under a
  * three-component filter, row padding and gaps between frames keep their values), the destination is never read, and destination
  * planes may share a buffer.
@@ -463,6 +464,64 @@ JINC_API int jinc_filter_process_device_narrowed(jinc_filter *f, const void *con
                                                  const int src_sample_step[4], const size_t src_frame_stride[4], void *const dst[4],
                                                  const int dst_pitch[4], const int dst_sample_step[4], const int dst_sample_shift[4],
                                                  int dst_bits, const size_t dst_frame_stride[4], int nframes, void *hip_stream);
+
+/* The widened and the narrowed call with a SCALE and an OFFSET between code values and the float range: networks read 0 .. 1, or
+ * (v - 16) / 219 for limited-range luma and (v - 128) / 224 for chroma, not code values, and the arithmetic runs where the samples
+ * are in registers already instead of in a pass of the caller's over the float planes.
+ *   The argument lists are those of jinc_filter_process_device_widened / _narrowed plus two arrays of four floats in the
+ *   library's plane order (Y,U,V or G,B,R, then A).  A NULL scale array means all 1.0; a NULL offset array means all 0.0.
+ *   WIDENED.  Let v = (raw >> shift[i]) & ((1 << src_bits) - 1).  The sample of plane i is
+ *       s = fl32(fl32(float(v) * src_scale[i]) + src_offset[i]).
+ *   That is two fp32 roundings and never an FMA.  An fp32 filter holds s.  A binary16 filter holds s narrowed
+ *   round-to-nearest-even: overflow to +-inf, subnormals kept.  A bfloat16 filter holds s narrowed round-to-nearest-even, by the
+ *   rule its results are stored with (+-inf from 0x7f7f8000 on, subnormals kept).  The call's result is exactly what
+ *   jinc_filter_process_device computes on that filter for dense planes holding those samples.
+ *   NARROWED.  Let r be what jinc_filter_process_device stores for the same source planes, widened exactly to fp32.  The stored
+ *   sample is
+ *       lrintf(clamp(fl32(fl32(r * dst_scale[i]) + dst_offset[i]), 0, peak)) << shift[i].
+ *   Everything else is as in the narrowed call: NaN -> 0, +inf -> peak, padding bits zero, the destination is never read, no byte
+ *   outside a given sample is stored to.
+ *   BOTH ARRAYS NULL.  The call IS the existing call.  It makes the same launches, the same refusals and the same
+ *   jinc_debug_last_strided report.  The src_bits <= 11 and src_bits = 8 rules for half and bfloat16 filters still apply.
+ *   EITHER ARRAY NON-NULL.  The scaled form runs.  src_bits 8 .. 16 is accepted for all three float types, because the conversion
+ *   is a defined rounding and not a claim of exactness: P010 into bfloat16 planes and P016 into half planes, normalised.
+ *     NV12 into YUV420PH, limited range in 0 .. 1:  jinc_code_range(8, JINC_RANGE_LIMITED, JINC_PLANE_LUMA_OR_RGB, ...) gives
+ *     src_scale[0] / src_offset[0], JINC_PLANE_CHROMA those of planes 1 and 2; the to_code pair is the way back for the narrowed call.
+ * JINC_ERR_INVALID_ARG, each with a message of its own that names the side and the plane, before the device check and before
+ * anything is queued: a scale or offset of a used plane (index below the filter's number of components) that is NaN or infinite; a
+ * scale that is zero.  All refusals of the underlying call stay as they are, with the same texts, and come first.
+ * Stand-ins, slicing under strided_scratch_bytes, the order on the caller's stream and the jinc_debug_last_strided counts are exactly
+ * those of the unscaled calls: the scaled form adds no pass and no launch, only one multiply and one add per sample in the widening /
+ * narrowing kernel. */
+JINC_API int jinc_filter_process_device_widened_scaled(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                       const int src_sample_step[4], const int src_sample_shift[4], int src_bits,
+                                                       const float src_scale[4], const float src_offset[4],
+                                                       const size_t src_frame_stride[4], void *const dst[4], const int dst_pitch[4],
+                                                       const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
+                                                       void *hip_stream);
+JINC_API int jinc_filter_process_device_narrowed_scaled(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                        const int src_sample_step[4], const size_t src_frame_stride[4],
+                                                        void *const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
+                                                        const int dst_sample_shift[4], int dst_bits, const float dst_scale[4],
+                                                        const float dst_offset[4], const size_t dst_frame_stride[4], int nframes,
+                                                        void *hip_stream);
+
+/* Scale and offset between the code values of a `bits`-bit plane (8 .. 16) and the float range 0 .. 1 (luma, RGB) or -0.5 .. 0.5
+ * (chroma), for the two calls above.  Needs no device.  With k = 2^(bits - 8):
+ *       range, plane kind            den            zero
+ *       limited, luma or RGB         219 k          16 k
+ *       limited, chroma              224 k          128 k
+ *       full, luma or RGB            2^bits - 1     0
+ *       full, chroma                 2^bits - 1     2^(bits - 1)
+ *   to_float_scale = (float)(1.0 / den) and to_float_offset = (float)(-(double)zero / den): both are computed in double and
+ *   rounded once.  to_code_scale = (float)den and to_code_offset = (float)zero: both are exact.  Any pointer may be NULL.
+ * bits outside 8 .. 16, another range or another plane kind is JINC_ERR_INVALID_ARG. */
+#define JINC_RANGE_FULL 0
+#define JINC_RANGE_LIMITED 1
+#define JINC_PLANE_LUMA_OR_RGB 0
+#define JINC_PLANE_CHROMA 1
+JINC_API int jinc_code_range(int bits, int range, int plane_kind, float *to_float_scale, float *to_float_offset, float *to_code_scale,
+                             float *to_code_offset);
 
 /* 10:10:10:2 WORDS into an fp32 or binary16 filter: the HDR 4:4:4 surface of decoders and swap chains (Y410, R10G10B10A2, the DRM
  * 2101010 / 1010102 orders) resampled straight into the float or half planes a network reads, with nothing rounded to a code value

@@ -273,6 +273,16 @@ JINC_API int jinc_debug_convert_bfloat16(const float *sums, uint16_t *out, int n
  * patterns).  out receives n samples lrintf(clamp(value, 0, (1 << dst_bits) - 1)) << shift, bytes for dst_bits 8 and 16-bit words
  * for 9 .. 16 (shift in 0 .. 8 * bytes - dst_bits): whole lanes through the 16-byte accesses, the rest sample by sample. */
 JINC_API int jinc_debug_narrow(const void *in, int in_kind, void *out, int n, int dst_bits, int shift, int device);
+/* ... the scaled form of that pass (jinc_filter_process_device_narrowed_scaled): out receives
+ * lrintf(clamp(fl32(fl32(value * scale) + offset), 0, (1 << dst_bits) - 1)) << shift.  scale and offset finite, scale not zero. */
+JINC_API int jinc_debug_narrow_scaled(const void *in, int in_kind, void *out, int n, int dst_bits, int shift, float scale, float offset,
+                                      int device);
+/* ... and the scaled form of the widening pass (jinc_filter_process_device_widened_scaled): widen_samples_kernel with one sample
+ * per pixel on ONE dense row of `n` integer samples (bytes for src_bits 8, 16-bit words for 9 .. 16; shift in
+ * 0 .. 8 * bytes - src_bits).  out receives n samples fl32(fl32(float((raw >> shift) & mask) * scale) + offset) of out_kind:
+ * JINC_SAMPLE_DEFAULT fp32, JINC_SAMPLE_FLOAT16 / JINC_SAMPLE_BFLOAT16 the 16-bit patterns rounded to nearest even. */
+JINC_API int jinc_debug_widen_scaled(const void *in, int src_bits, int shift, float scale, float offset, int out_kind, void *out, int n,
+                                     int device);
 
 /* Test hook: 1 when the device's buffer range check covers the scalar offset of buffer loads (the premise of the
  * direct kernel's bounded segment fetches; probed once per device, the direct kernel is not used where it fails), 0 when
