@@ -73,6 +73,12 @@ class PlanInfo(C.Structure):
                [(n, C.c_int) for n in ("quasi", "quasi_period_x", "quasi_period_y", "quasi_step_x", "quasi_step_y")]
 
 
+class GroupInfo(C.Structure):
+    """jinc_group_info (test header): one channel group of the last widened / narrowed call as its launch got it."""
+    _fields_ = [(n, C.c_int) for n in ("direction", "n", "members", "sample_bytes", "sample_type", "scaled", "unit", "vec_pixels",
+                                       "width", "rows")]
+
+
 ARG_BITS = {"src_left": 1 << 0, "src_top": 1 << 1, "src_width": 1 << 2, "src_height": 1 << 3, "quant_x": 1 << 4,
             "quant_y": 1 << 5, "tap": 1 << 6, "blur": 1 << 7, "cplace": 1 << 8, "threads": 1 << 9, "opt": 1 << 10,
             "initial_capacity": 1 << 11, "initial_factor": 1 << 12}
@@ -86,7 +92,7 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_submit", "jinc_filter_wait", "jinc_shard_device", "jinc_batch_create", "jinc_batch_devices",
            "jinc_batch_device_of_frame", "jinc_batch_process", "jinc_batch_free", "jinc_batch_last_error",
            "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share",
-           "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided",
+           "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided", "jinc_debug_last_groups",
            "jinc_filter_process_device_shifted", "jinc_filter_process_device_packed10", "jinc_packed10_layout",
            "jinc_filter_process_device_v210", "jinc_v210_row_bytes", "jinc_filter_process_device_widened",
            "jinc_filter_process_device_widened_packed10", "jinc_filter_process_device_widened_v210",
@@ -141,6 +147,7 @@ def lib():
         L.jinc_v210_row_bytes.restype = C.c_size_t
         L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
         L.jinc_debug_last_strided.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+        L.jinc_debug_last_groups.argtypes = [C.POINTER(GroupInfo), C.c_int]
         L.jinc_filter_sync.argtypes = [C.c_void_p]
         L.jinc_filter_set_pipeline.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.jinc_filter_set_pipeline_group.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
@@ -331,6 +338,16 @@ def last_strided() -> Tuple[int, int, int, int]:
     a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
     lib().jinc_debug_last_strided(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
     return a.value, b.value, c.value, d.value
+
+
+def last_groups() -> List[Dict[str, int]]:
+    """The channel groups of the first slice of the calling thread's most recent process_device_widened / _narrowed call (scaled or
+    not) as the widening / narrowing launches got them (jinc_debug_last_groups, test header): one dict per group with direction
+    (0 widened, 1 narrowed), n (samples per pixel), members, sample_bytes, sample_type (SAMPLE_*), scaled, unit (16, 4 or 0),
+    vec_pixels (0: the whole row moved sample by sample), width and rows.  Empty after any other strided-family call."""
+    g = (GroupInfo * 4)()
+    count = int(lib().jinc_debug_last_groups(g, 4))
+    return [{name: int(getattr(g[i], name)) for name, _ in GroupInfo._fields_} for i in range(count)]
 
 
 def packed10_layout(name: str) -> Tuple[List[int], int]:
@@ -1105,6 +1122,7 @@ class Filter:
             arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
+    last_groups = staticmethod(last_groups)
     strided_groups = staticmethod(strided_groups)
 
     def periodic_support(self, table: int = 0) -> int:

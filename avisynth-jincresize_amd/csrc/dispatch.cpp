@@ -864,6 +864,20 @@ void enqueue_run(jinc_filter& f, const void* const src[4], const int src_pitch[4
 
 namespace {
 thread_local StridedReport t_last_strided;
+thread_local GroupsReport t_last_groups;  // cleared wherever t_last_strided is: what a call that widens or narrows nothing leaves
+
+// One entry of jinc_debug_last_groups: group e of a slice as its widening (direction 0) / narrowing (1) launch gets it.  Only the
+// call's first slice is kept: the later ones differ in their frames alone.
+template <class Group>
+void record_group(const jinc_filter& f, int direction, const Group& e, int step, int members, size_t sample_bytes, bool scaled,
+                  int first_frame) {
+    if (first_frame != 0 || t_last_groups.count >= 4) return;
+    GroupRecord& r = t_last_groups.g[t_last_groups.count++];
+    r.direction = direction, r.step = step, r.members = members, r.sample_bytes = static_cast<int>(sample_bytes);
+    r.sample_type = f.half ? JINC_SAMPLE_FLOAT16 : f.bf16 ? JINC_SAMPLE_BFLOAT16 : JINC_SAMPLE_DEFAULT;
+    r.scaled = scaled ? 1 : 0;
+    r.unit = e.unit, r.vec_pixels = e.vec_pixels, r.width = e.width, r.rows = e.rows;
+}
 
 // Dense planes behind a call: 1 GiB unless the knob says otherwise.  Derived, not measured: a 1080p -> 4K 4:2:0 frame has
 // 2 x 960 x 540 source and 2 x 1920 x 1080 result chroma samples, with rows padded to 256 bytes 2 x (1024 x 540 + 2048 x 1080)
@@ -1130,10 +1144,12 @@ int strided_groups(const void* const base[4], const int pitch[4], const int* ste
 }
 
 const StridedReport& last_strided_report() { return t_last_strided; }
+const GroupsReport& last_groups_report() { return t_last_groups; }
 
 void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
                      const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift,
                      const size_t* dst_fs, int nframes, hipStream_t stream) {
+    t_last_groups.count = 0;
     bool dense = true;
     for (int i = 0; i < f.planecount; ++i)
         dense &= step_of(src_step, i) == 1 && step_of(dst_step, i) == 1 && shift_of(src_shift, i) == 0 && shift_of(dst_shift, i) == 0;
@@ -1191,6 +1207,7 @@ void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pi
                       void* const dst[4], const int dst_pitch[4], const int* dst_fields, unsigned dst_fill, const size_t* dst_fs,
                       int nframes, hipStream_t stream) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    t_last_groups.count = 0;
     if (!src_fields && !dst_fields) {  // the call IS jinc_filter_process_device
         enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
         return;
@@ -1235,6 +1252,7 @@ void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pi
 void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], bool src_is_v210, const size_t* src_fs,
                   void* const dst[4], const int dst_pitch[4], bool dst_is_v210, const size_t* dst_fs, int nframes, hipStream_t stream) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    t_last_groups.count = 0;
     if (!src_is_v210 && !dst_is_v210) {  // the call IS jinc_filter_process_device
         enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
         return;
@@ -1311,6 +1329,7 @@ void fill_widen_args(const jinc_filter& f, const Side& s, const void* const base
         // (a group with a channel missing leaves the row's last pixel to the tail: its missing samples may lie behind the caller's buffer)
         const uint32_t vec_from = members == n ? e.width : e.width - 1;
         e.vec_pixels = e.unit ? vec_from / lane_pixels * lane_pixels : 0u;
+        record_group(f, 0, e, n, members, src_bytes, scale || offset, first_frame);
         WidenArgs& a_n = by_step[n];
         a_n.mask = mask;
         a_n.g[a_n.ngroups++] = e;
@@ -1338,6 +1357,7 @@ void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pit
                      int src_bits, const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step,
                      const size_t* dst_fs, int nframes, hipStream_t stream, const float* src_scale, const float* src_offset) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    t_last_groups.count = 0;
     const size_t sb = static_cast<size_t>(f.vi_in.component_size), src_bytes = src_bits > 8 ? 2 : 1;
     Side in, out;
     for (int i = 0; i < f.planecount; ++i) {
@@ -1404,6 +1424,7 @@ void widened_words_sides(const jinc_filter& f, void* const dst[4], const int dst
 void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, const int* src_fields, size_t src_fs, void* const dst[4],
                               const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    t_last_groups.count = 0;
     Side in, out;
     widened_words_sides(f, dst, dst_pitch, dst_step, dst_fs, nframes, in, out);
     check_packed10_side(src, src_pitch, &src_fs, in.w[0], nframes);  // (filter.cpp has refused these already, with messages of this call's own)
@@ -1425,6 +1446,7 @@ void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, co
 void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t src_fs, void* const dst[4], const int dst_pitch[4],
                           const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    t_last_groups.count = 0;
     Side in, out;
     widened_words_sides(f, dst, dst_pitch, dst_step, dst_fs, nframes, in, out);
     check_v210_side(src, src_pitch, &src_fs, in, nframes);  // (filter.cpp has refused these already, with messages of this call's own)
@@ -1487,6 +1509,7 @@ void fill_narrow_args(const jinc_filter& f, const Side& s, void* const base[4], 
         const uint32_t lane_pixels = static_cast<uint32_t>(16 / dst_bytes);
         // (a group with a channel missing stores sample by sample: only the given channels' samples may be stored to)
         e.vec_pixels = (e.unit && members == n) ? e.width / lane_pixels * lane_pixels : 0u;
+        record_group(f, 1, e, n, members, dst_bytes, scale || offset, first_frame);
         NarrowArgs& a_n = by_step[n];
         a_n.peak = peak;
         a_n.g[a_n.ngroups++] = e;
@@ -1500,6 +1523,7 @@ void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pi
                       void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift, int dst_bits,
                       const size_t* dst_fs, int nframes, hipStream_t stream, const float* dst_scale, const float* dst_offset) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    t_last_groups.count = 0;
     const size_t sb = static_cast<size_t>(f.vi_in.component_size), dst_bytes = dst_bits > 8 ? 2 : 1;
     Side in, out;
     for (int i = 0; i < f.planecount; ++i) {

@@ -641,6 +641,18 @@ int jinc_debug_last_strided(int* split_launches, int* merge_launches, int* slice
     return JINC_OK;
 }
 
+int jinc_debug_last_groups(jinc_group_info* groups, int capacity) {
+    const GroupsReport& r = last_groups_report();
+    for (int i = 0; groups && i < r.count && i < capacity; ++i) {
+        const GroupRecord& g = r.g[i];
+        groups[i].direction = g.direction, groups[i].n = g.step, groups[i].members = g.members, groups[i].sample_bytes = g.sample_bytes;
+        groups[i].sample_type = g.sample_type, groups[i].scaled = g.scaled;
+        groups[i].unit = static_cast<int>(g.unit), groups[i].vec_pixels = static_cast<int>(g.vec_pixels);
+        groups[i].width = static_cast<int>(g.width), groups[i].rows = static_cast<int>(g.rows);
+    }
+    return r.count;
+}
+
 int jinc_filter_sync(jinc_filter* f) {
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");

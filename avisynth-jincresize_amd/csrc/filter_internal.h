@@ -372,6 +372,18 @@ struct StridedReport {  // test header: jinc_debug_last_strided
     long long scratch_bytes = 0;
 };
 const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided / enqueue_packed10 / enqueue_v210 / enqueue_widened* / enqueue_narrowed
+// ... and the groups of that call's first slice as its widening / narrowing launches got them (test header: jinc_debug_last_groups;
+// a call has at most one group per plane).  Empty after every other call and after a refused one.
+struct GroupRecord {
+    int direction = 0;  // 0: widen_samples_kernel, 1: narrow_samples_kernel
+    int step = 0, members = 0, sample_bytes = 0, sample_type = 0, scaled = 0;  // sample_type: the filter's JINC_SAMPLE_*
+    uint32_t unit = 0, vec_pixels = 0, width = 0, rows = 0;
+};
+struct GroupsReport {
+    int count = 0;
+    GroupRecord g[4];
+};
+const GroupsReport& last_groups_report();
 int last_call_frames_in_process();
 const char* last_interior_instance_in_process();
 // pipeline.cpp: frames in flight on one instance

@@ -241,6 +241,22 @@ JINC_API int jinc_debug_strided_groups(const void *const base[4], const int pitc
  * call's frames cut into runs that fit the dense planes' cap) and the bytes of dense planes the filter holds.  All zero but the
  * bytes when every step was 1 (the call was jinc_filter_process_device).  Any pointer may be NULL. */
 JINC_API int jinc_debug_last_strided(int *split_launches, int *merge_launches, int *slices, long long *scratch_bytes);
+/* The most recent jinc_filter_process_device_widened / _narrowed call on the calling thread, scaled or not: the channel groups of its
+ * FIRST slice as the widening / narrowing launches got them, in the order of each group's first plane -- which loop of
+ * widen_samples_kernel / narrow_samples_kernel moved a group's samples is decided by these numbers and by nothing else.
+ * direction: 0 widened, 1 narrowed.  n: samples per pixel on the integer side (the step).  members: planes of the call in the group.
+ * sample_bytes: of the integer side (1 or 2).  sample_type: the filter's JINC_SAMPLE_*.  scaled: 1 when a scale or an offset array
+ * was given.  unit: the widest access the integer side allows (16, 4; 0: sample-sized accesses only).  vec_pixels: the leading pixels
+ * of every row that move by such accesses, 16 / sample_bytes per lane and step; the rest of the row (all of it when vec_pixels is 0)
+ * moves sample by sample.  width, rows: of the group's planes.
+ * Copies up to `capacity` entries to `groups` (may be NULL) and returns their number, at most 4.  The record is emptied wherever the
+ * counts of jinc_debug_last_strided are reset: by every strided, shifted, packed10, v210 and widened / narrowed call that reaches the
+ * device check, so that one refused behind it (a pitch, a frame stride) leaves 0 entries; a call refused on its arguments alone,
+ * in front of the device check, leaves both records as they were. */
+typedef struct jinc_group_info {
+    int direction, n, members, sample_bytes, sample_type, scaled, unit, vec_pixels, width, rows;
+} jinc_group_info;
+JINC_API int jinc_debug_last_groups(jinc_group_info *groups, int capacity);
 /* Border frame of exactly periodic plans: -1 (default) = by call size (strip kernels from ~5e9 taps per call on, one gather
  * launch below); 1 = rows and columns on the round-4 strip kernels (ewa_direct_kernel's row strips, ewa_colstrip_kernel or, in batches,
  * the frame-lane kernel), corners on the gather kernel; 2 = rows on the strip kernel, columns and corners on the gather kernel;

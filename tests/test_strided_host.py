@@ -13,11 +13,40 @@ INVALID_ARG, NO_DEVICE = -1, -2
 def test_the_strided_entry_is_exported_and_mirrored(pkg):
     header = open(pkg.HEADER_PATH).read()
     assert "jinc_filter_process_device_strided(" in header
-    for name in ("jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided"):
+    for name in ("jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided", "jinc_debug_last_groups"):
         assert name in pkg.EXPORTS and hasattr(pkg.lib(), name), name
+    test_header = open(pkg.TEST_HEADER_PATH).read()
+    for name in ("jinc_debug_strided_groups", "jinc_debug_last_strided", "jinc_debug_last_groups"):
+        assert name + "(" in test_header and name + "(" not in header, name
     assert hasattr(pkg.Filter, "process_device_strided") and hasattr(pkg.Filter, "last_strided") and hasattr(pkg.Filter, "strided_groups")
+    assert hasattr(pkg.Filter, "last_groups") and callable(pkg.last_groups)
     assert "strided_scratch_bytes" in pkg.knob_ids()
     assert pkg.last_strided()[:3] == (0, 0, 0)
+
+
+def test_the_groups_record_mirrors_the_header_and_is_empty_without_a_call(pkg):
+    """jinc_group_info field for field (the mirror reads the struct by position), a NULL array and a capacity of 0 are taken, and a
+    call refused for want of a device leaves the record empty, as it leaves the launch counts at zero."""
+    test_header = open(pkg.TEST_HEADER_PATH).read()
+    flat = " ".join(test_header.split())
+    fields = [n for n, _ in pkg.GroupInfo._fields_]
+    assert "typedef struct jinc_group_info { int " + ", ".join(fields) + "; } jinc_group_info;" in flat
+    assert C.sizeof(pkg.GroupInfo) == 4 * len(fields) == 40
+    L = pkg.lib()
+    assert L.jinc_debug_last_groups(None, 0) == 0 and L.jinc_debug_last_groups(None, 4) == 0
+    one = (pkg.GroupInfo * 1)()
+    assert L.jinc_debug_last_groups(one, 1) == 0 and L.jinc_debug_last_groups(one, 0) == 0
+    assert pkg.last_groups() == []
+    for fmt, call in (("YUV420PS", "widened"), ("YUV420PS", "narrowed")):
+        f = pkg.Filter(pkg.FORMATS[fmt], 40, 24, 80, 48, device=-1)
+        with pytest.raises(pkg.JincError) as e:
+            if call == "widened":
+                f.process_device_widened([4096, 8192, 8193], [64] * 3, [1, 2, 2], None, 8, [0] * 3, [1 << 20, 2 << 20, 3 << 20], [512] * 3, None, [0] * 3, 1)
+            else:
+                f.process_device_narrowed([4096, 8192, 12288], [512] * 3, None, [0] * 3, [1 << 20, 2 << 20, (2 << 20) + 1], [80] * 3, [1, 2, 2], None, 8, [0] * 3, 1)
+        assert e.value.code == NO_DEVICE
+        assert pkg.last_groups() == [] and pkg.last_strided()[:3] == (0, 0, 0)
+        f.close()
 
 
 def _call(pkg, f, src_steps, dst_steps, src=(256, 512, 768, 1024), dst=(4096, 8192, 12288, 16384)):
