@@ -74,9 +74,10 @@ class PlanInfo(C.Structure):
 
 
 class GroupInfo(C.Structure):
-    """jinc_group_info (test header): one channel group of the last widened / narrowed call as its launch got it."""
+    """jinc_group_info (test header): one pass of the last call with stand-ins (a channel group, a field or a block pass) as its
+    launch got it."""
     _fields_ = [(n, C.c_int) for n in ("direction", "n", "members", "sample_bytes", "sample_type", "scaled", "unit", "vec_pixels",
-                                       "width", "rows")]
+                                       "width", "rows", "shifted")]
 
 
 ARG_BITS = {"src_left": 1 << 0, "src_top": 1 << 1, "src_width": 1 << 2, "src_height": 1 << 3, "quant_x": 1 << 4,
@@ -341,12 +342,16 @@ def last_strided() -> Tuple[int, int, int, int]:
 
 
 def last_groups() -> List[Dict[str, int]]:
-    """The channel groups of the first slice of the calling thread's most recent process_device_widened / _narrowed call (scaled or
-    not) as the widening / narrowing launches got them (jinc_debug_last_groups, test header): one dict per group with direction
-    (0 widened, 1 narrowed), n (samples per pixel), members, sample_bytes, sample_type (SAMPLE_*), scaled, unit (16, 4 or 0),
-    vec_pixels (0: the whole row moved sample by sample), width and rows.  Empty after any other strided-family call."""
-    g = (GroupInfo * 4)()
-    count = int(lib().jinc_debug_last_groups(g, 4))
+    """The passes of the first slice of the calling thread's most recent strided / shifted / packed10 / v210 / widened / narrowed call
+    (scaled or not) as their launches got them (jinc_debug_last_groups, test header): one dict per channel group of the widening,
+    narrowing, split and merge launches and one per field or block pass, the source side's first, then the destination side's, each
+    side in the order of its groups' first planes.  Keys: direction (0 widened, 1 narrowed, 2 split, 3 merge, 4 / 5 / 6 unpack_fields /
+    pack_fields / widen_fields, 7 / 8 / 9 unpack_v210 / pack_v210 / widen_v210), n (samples per pixel), members, sample_bytes,
+    sample_type (SAMPLE_*), scaled, unit (16, 4 or 0), vec_pixels (0: the whole row moved sample by sample; v210: 6 x the blocks
+    that moved in pairs), width, rows and shifted (split / merge: the launch took the shifted form).  At most 8; empty after a call
+    on dense planes alone."""
+    g = (GroupInfo * 8)()
+    count = int(lib().jinc_debug_last_groups(g, 8))
     return [{name: int(getattr(g[i], name)) for name, _ in GroupInfo._fields_} for i in range(count)]
 
 

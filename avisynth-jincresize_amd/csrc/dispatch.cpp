@@ -9,6 +9,7 @@
 
 #include "filter_internal.h"
 #include "knobs.h"
+#include "v210_rows.h"
 
 namespace jinc {
 namespace host {
@@ -864,19 +865,42 @@ void enqueue_run(jinc_filter& f, const void* const src[4], const int src_pitch[4
 
 namespace {
 thread_local StridedReport t_last_strided;
-thread_local GroupsReport t_last_groups;  // cleared wherever t_last_strided is: what a call that widens or narrows nothing leaves
+thread_local GroupsReport t_last_groups;  // cleared wherever t_last_strided is: what a call that runs no pass leaves
 
-// One entry of jinc_debug_last_groups: group e of a slice as its widening (direction 0) / narrowing (1) launch gets it.  Only the
-// call's first slice is kept: the later ones differ in their frames alone.
-template <class Group>
-void record_group(const jinc_filter& f, int direction, const Group& e, int step, int members, size_t sample_bytes, bool scaled,
-                  int first_frame) {
-    if (first_frame != 0 || t_last_groups.count >= 4) return;
+// GroupRecord::direction
+enum : int { kWiden = 0, kNarrow = 1, kSplit = 2, kMerge = 3, kUnpackFields = 4, kPackFields = 5, kWidenFields = 6, kUnpackV210 = 7, kPackV210 = 8, kWidenV210 = 9 };
+
+// One entry of jinc_debug_last_groups: a pass of a slice by the numbers its launch gets.  Only the call's first slice is kept: the
+// later ones differ in their frames alone.  The split lambda of a slice runs in front of its merge lambda and each fills its
+// arguments group by group, so the entries stand source side first, each side in the order of its groups' first planes.
+void record_pass(const jinc_filter& f, int direction, int step, int members, size_t sample_bytes, bool scaled, uint32_t unit,
+                 uint32_t vec_pixels, uint32_t width, uint32_t rows, int first_frame) {
+    if (first_frame != 0 || t_last_groups.count >= GroupsReport::kCapacity) return;
     GroupRecord& r = t_last_groups.g[t_last_groups.count++];
     r.direction = direction, r.step = step, r.members = members, r.sample_bytes = static_cast<int>(sample_bytes);
     r.sample_type = f.half ? JINC_SAMPLE_FLOAT16 : f.bf16 ? JINC_SAMPLE_BFLOAT16 : JINC_SAMPLE_DEFAULT;
     r.scaled = scaled ? 1 : 0;
-    r.unit = e.unit, r.vec_pixels = e.vec_pixels, r.width = e.width, r.rows = e.rows;
+    r.unit = unit, r.vec_pixels = vec_pixels, r.width = width, r.rows = rows;
+    r.shifted = 0;
+}
+// Group e as its widening / narrowing / split / merge launch gets it.
+template <class Group>
+void record_group(const jinc_filter& f, int direction, const Group& e, int step, int members, size_t sample_bytes, bool scaled,
+                  int first_frame) {
+    record_pass(f, direction, step, members, sample_bytes, scaled, e.unit, e.vec_pixels, e.width, e.rows, first_frame);
+}
+// The split / merge entries from `from` on whose groups travelled in the launch of `step`: what launch_by_shape decided for it.
+void record_shifted(int from, int direction, int step, bool shifted, int first_frame) {
+    if (first_frame != 0) return;
+    for (int i = from; i < t_last_groups.count; ++i)
+        if (t_last_groups.g[i].direction == direction && t_last_groups.g[i].step == step) t_last_groups.g[i].shifted = shifted ? 1 : 0;
+}
+// The field and block passes: the three planes of the filter as one group (step and members 3), samples of the filter's size.
+void record_fields(const jinc_filter& f, int direction, const jinc::FieldArgs& a, int first_frame) {
+    record_pass(f, direction, 3, 3, static_cast<size_t>(f.vi_in.component_size), false, a.unit, a.vec_pixels, a.width, a.rows, first_frame);
+}
+void record_v210(const jinc_filter& f, int direction, const jinc::V210Args& a, int first_frame) {  // (vec_pixels: the pixels of the blocks that move in pairs)
+    record_pass(f, direction, 3, 3, static_cast<size_t>(f.vi_in.component_size), false, a.unit, 6u * jinc::v210::paired_blocks(a), a.width, a.rows, first_frame);
 }
 
 // Dense planes behind a call: 1 GiB unless the knob says otherwise.  Derived, not measured: a 1080p -> 4K 4:2:0 frame has
@@ -947,6 +971,7 @@ void fill_args(const jinc_filter& f, const Side& s, const void* const base[4], c
         // (kernels.h: the merge of an incomplete group stores sample by sample; the split of one leaves the row's last pixel to the tail)
         const uint32_t vec_from = complete ? e.width : merge ? 0u : e.width - 1;
         e.vec_pixels = e.unit ? vec_from / lane_pixels * lane_pixels : 0u;
+        record_group(f, merge ? kMerge : kSplit, e, n, members, sb, false, first_frame);
         InterleaveArgs& a_n = by_step[n];
         a_n.g[a_n.ngroups++] = e;
     }
@@ -1173,22 +1198,28 @@ void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pit
         f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
             InterleaveArgs split[5];
+            const int recorded = t_last_groups.count;
             fill_args(f, in, src, src_pitch, src_step, src_shift, src_fs, scratch, k0, slice, nframes, false, split);
             int launches = 0;
             for (int step = 1; step <= 4; ++step)  // (step 1: shifted dense planes)
                 if (split[step].ngroups) {
-                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream)), "split launch");
+                    bool shifted = false;
+                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream, &shifted)), "split launch");
+                    record_shifted(recorded, kSplit, step, shifted, k0);
                     ++launches;
                 }
             return launches;
         },
         [&](char* scratch, int k0, int slice, int n) {
             InterleaveArgs merge[5];
+            const int recorded = t_last_groups.count;
             fill_args(f, out, dst_c, dst_pitch, dst_step, dst_shift, dst_fs, scratch, k0, slice, nframes, true, merge);
             int launches = 0;
             for (int step = 1; step <= 4; ++step)
                 if (merge[step].ngroups) {
-                    hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], static_cast<int>(sb), step, n, stream)), "merge launch");
+                    bool shifted = false;
+                    hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], static_cast<int>(sb), step, n, stream, &shifted)), "merge launch");
+                    record_shifted(recorded, kMerge, step, shifted, k0);
                     ++launches;
                 }
             return launches;
@@ -1228,12 +1259,14 @@ void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pi
         [&](char* scratch, int k0, int slice, int n) {
             if (!src_fields) return 0;
             const jinc::FieldArgs a = field_args(in, src[0], src_pitch[0], src_fs, src_fields, 0u, scratch, k0, slice, nframes);
+            record_fields(f, kUnpackFields, a, k0);
             hip_check(static_cast<hipError_t>(jinc::launch_unpack_fields(a, n, stream)), "unpack launch");
             return 1;
         },
         [&](char* scratch, int k0, int slice, int n) {
             if (!dst_fields) return 0;
             const jinc::FieldArgs a = field_args(out, dst[0], dst_pitch[0], dst_fs, dst_fields, dst_fill, scratch, k0, slice, nframes);
+            record_fields(f, kPackFields, a, k0);
             hip_check(static_cast<hipError_t>(jinc::launch_pack_fields(a, n, stream)), "pack launch");
             return 1;
         });
@@ -1273,12 +1306,14 @@ void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[
         [&](char* scratch, int k0, int slice, int n) {
             if (!src_is_v210) return 0;
             const jinc::V210Args a = v210_args(in, src[0], src_pitch[0], src_fs, scratch, k0, slice, nframes);
+            record_v210(f, kUnpackV210, a, k0);
             hip_check(static_cast<hipError_t>(jinc::launch_unpack_v210(a, n, stream)), "v210 unpack launch");
             return 1;
         },
         [&](char* scratch, int k0, int slice, int n) {
             if (!dst_is_v210) return 0;
             const jinc::V210Args a = v210_args(out, dst[0], dst_pitch[0], dst_fs, scratch, k0, slice, nframes);
+            record_v210(f, kPackV210, a, k0);
             hip_check(static_cast<hipError_t>(jinc::launch_pack_v210(a, n, stream)), "v210 pack launch");
             return 1;
         });
@@ -1329,7 +1364,7 @@ void fill_widen_args(const jinc_filter& f, const Side& s, const void* const base
         // (a group with a channel missing leaves the row's last pixel to the tail: its missing samples may lie behind the caller's buffer)
         const uint32_t vec_from = members == n ? e.width : e.width - 1;
         e.vec_pixels = e.unit ? vec_from / lane_pixels * lane_pixels : 0u;
-        record_group(f, 0, e, n, members, src_bytes, scale || offset, first_frame);
+        record_group(f, kWiden, e, n, members, src_bytes, scale || offset, first_frame);
         WidenArgs& a_n = by_step[n];
         a_n.mask = mask;
         a_n.g[a_n.ngroups++] = e;
@@ -1340,11 +1375,14 @@ void fill_widen_args(const jinc_filter& f, const Side& s, const void* const base
 int merge_widened(const jinc_filter& f, const Side& out, const void* const dst_c[4], const int dst_pitch[4], const int* dst_step,
                   const size_t* dst_fs, char* scratch, int k0, int slice, int n, int nframes, hipStream_t stream) {
     InterleaveArgs merge[5];
+    const int recorded = t_last_groups.count;
     fill_args(f, out, dst_c, dst_pitch, dst_step, nullptr, dst_fs, scratch, k0, slice, nframes, true, merge);
     int launches = 0;
     for (int step = 1; step <= 4; ++step)
         if (merge[step].ngroups) {
-            hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], f.vi_in.component_size, step, n, stream)), "merge launch");
+            bool shifted = false;
+            hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], f.vi_in.component_size, step, n, stream, &shifted)), "merge launch");
+            record_shifted(recorded, kMerge, step, shifted, k0);
             ++launches;
         }
     return launches;
@@ -1437,6 +1475,7 @@ void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, co
         f, in, out, src_planes, src_pitches, src_strides, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
             const jinc::FieldArgs a = field_args(in, src, src_pitch, src_strides, src_fields, 0u, scratch, k0, slice, nframes);
+            record_fields(f, kWidenFields, a, k0);
             hip_check(static_cast<hipError_t>(jinc::launch_widen_fields(a, f.vi_in.component_size, n, stream)), "widen fields launch");
             return 1;
         },
@@ -1458,6 +1497,7 @@ void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t
         f, in, out, src_planes, src_pitches, src_strides, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
             const jinc::V210Args a = v210_args(in, src, src_pitch, src_strides, scratch, k0, slice, nframes);
+            record_v210(f, kWidenV210, a, k0);
             hip_check(static_cast<hipError_t>(jinc::launch_widen_v210(a, f.vi_in.component_size, n, stream)), "widen v210 launch");
             return 1;
         },
@@ -1509,7 +1549,7 @@ void fill_narrow_args(const jinc_filter& f, const Side& s, void* const base[4], 
         const uint32_t lane_pixels = static_cast<uint32_t>(16 / dst_bytes);
         // (a group with a channel missing stores sample by sample: only the given channels' samples may be stored to)
         e.vec_pixels = (e.unit && members == n) ? e.width / lane_pixels * lane_pixels : 0u;
-        record_group(f, 1, e, n, members, dst_bytes, scale || offset, first_frame);
+        record_group(f, kNarrow, e, n, members, dst_bytes, scale || offset, first_frame);
         NarrowArgs& a_n = by_step[n];
         a_n.peak = peak;
         a_n.g[a_n.ngroups++] = e;
@@ -1548,11 +1588,14 @@ void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pi
         f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
             InterleaveArgs split[5];
+            const int recorded = t_last_groups.count;
             fill_args(f, in, src, src_pitch, src_step, nullptr, src_fs, scratch, k0, slice, nframes, false, split);
             int launches = 0;
             for (int step = 2; step <= 4; ++step)
                 if (split[step].ngroups) {
-                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream)), "split launch");
+                    bool shifted = false;
+                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream, &shifted)), "split launch");
+                    record_shifted(recorded, kSplit, step, shifted, k0);
                     ++launches;
                 }
             return launches;

@@ -649,6 +649,7 @@ int jinc_debug_last_groups(jinc_group_info* groups, int capacity) {
         groups[i].sample_type = g.sample_type, groups[i].scaled = g.scaled;
         groups[i].unit = static_cast<int>(g.unit), groups[i].vec_pixels = static_cast<int>(g.vec_pixels);
         groups[i].width = static_cast<int>(g.width), groups[i].rows = static_cast<int>(g.rows);
+        groups[i].shifted = g.shifted;
     }
     return r.count;
 }

@@ -372,16 +372,22 @@ struct StridedReport {  // test header: jinc_debug_last_strided
     long long scratch_bytes = 0;
 };
 const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided / enqueue_packed10 / enqueue_v210 / enqueue_widened* / enqueue_narrowed
-// ... and the groups of that call's first slice as its widening / narrowing launches got them (test header: jinc_debug_last_groups;
-// a call has at most one group per plane).  Empty after every other call and after a refused one.
+// ... and the passes of that call's first slice as their launches got them (test header: jinc_debug_last_groups): the channel
+// groups of the widening / narrowing / split / merge launches and one entry per field or block pass, source side first, then the
+// destination side, each in the order of the groups' first planes (a side has at most one group per plane: 8 entries hold any
+// call).  Empty after a call that ran on the caller's dense planes alone and after a refused one.
 struct GroupRecord {
-    int direction = 0;  // 0: widen_samples_kernel, 1: narrow_samples_kernel
+    // 0: widen_samples_kernel, 1: narrow_samples_kernel, 2: split_samples_kernel, 3: merge_samples_kernel, 4 / 5 / 6: unpack_fields /
+    // pack_fields / widen_fields, 7 / 8 / 9: unpack_v210 / pack_v210 / widen_v210
+    int direction = 0;
     int step = 0, members = 0, sample_bytes = 0, sample_type = 0, scaled = 0;  // sample_type: the filter's JINC_SAMPLE_*
     uint32_t unit = 0, vec_pixels = 0, width = 0, rows = 0;
+    int shifted = 0;  // split / merge: what launch_by_shape decided for the launch this group travelled in
 };
 struct GroupsReport {
+    static constexpr int kCapacity = 8;
     int count = 0;
-    GroupRecord g[4];
+    GroupRecord g[kCapacity];
 };
 const GroupsReport& last_groups_report();
 int last_call_frames_in_process();

@@ -204,11 +204,12 @@ int launch(const InterleaveArgs& a, int nframes, hipStream_t s) {
 }
 
 template <bool Merge>
-int launch_by_shape(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream) {
+int launch_by_shape(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream, bool* took_shifted) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     bool shifted = false;  // one shifted channel makes the launch a shifted one (its other channels shift by 0)
     for (int k = 0; k < a.ngroups; ++k)
         for (int c = 0; c < 4; ++c) shifted |= a.g[k].shift[c] != 0;
+    if (took_shifted) *took_shifted = shifted;
     if (shifted) {
         if (sample_bytes != 2) return hipErrorInvalidValue;
         switch (step) {
@@ -382,12 +383,12 @@ int launch_unpack_fields(const FieldArgs& a, int nframes, void* stream) { return
 
 int launch_pack_fields(const FieldArgs& a, int nframes, void* stream) { return launch_fields<true>(a, nframes, stream); }
 
-int launch_split_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream) {
-    return launch_by_shape<false>(a, sample_bytes, step, nframes, stream);
+int launch_split_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream, bool* shifted) {
+    return launch_by_shape<false>(a, sample_bytes, step, nframes, stream, shifted);
 }
 
-int launch_merge_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream) {
-    return launch_by_shape<true>(a, sample_bytes, step, nframes, stream);
+int launch_merge_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream, bool* shifted) {
+    return launch_by_shape<true>(a, sample_bytes, step, nframes, stream, shifted);
 }
 
 }  // namespace jinc

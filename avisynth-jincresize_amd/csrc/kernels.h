@@ -525,8 +525,9 @@ struct InterleaveArgs {
 };
 // One launch over every group and frame of `a`: sample_bytes 1, 2 or 4; step 2, 3 or 4 (the same for all groups of a launch).
 // With a non-zero shift in any group the launch takes the shifted forms: sample_bytes 2 only, step 1 .. 4.
-int launch_split_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream);
-int launch_merge_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream);
+// shifted (may be nullptr) receives that decision: true when the launch took a shifted form (jinc_debug_last_groups).
+int launch_split_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream, bool* shifted = nullptr);
+int launch_merge_samples(const InterleaveArgs& a, int sample_bytes, int step, int nframes, void* stream, bool* shifted = nullptr);
 
 // 10:10:10:2 words <-> three dense 16-bit planes (kernel_interleave.hip; jinc_filter_process_device_packed10).  One little-endian
 // 32-bit word per pixel: pixel x of row y of frame n at packed + n * packed_frame_stride + y * packed_pitch + 4 * x, its value of

@@ -241,20 +241,29 @@ JINC_API int jinc_debug_strided_groups(const void *const base[4], const int pitc
  * call's frames cut into runs that fit the dense planes' cap) and the bytes of dense planes the filter holds.  All zero but the
  * bytes when every step was 1 (the call was jinc_filter_process_device).  Any pointer may be NULL. */
 JINC_API int jinc_debug_last_strided(int *split_launches, int *merge_launches, int *slices, long long *scratch_bytes);
-/* The most recent jinc_filter_process_device_widened / _narrowed call on the calling thread, scaled or not: the channel groups of its
- * FIRST slice as the widening / narrowing launches got them, in the order of each group's first plane -- which loop of
- * widen_samples_kernel / narrow_samples_kernel moved a group's samples is decided by these numbers and by nothing else.
- * direction: 0 widened, 1 narrowed.  n: samples per pixel on the integer side (the step).  members: planes of the call in the group.
- * sample_bytes: of the integer side (1 or 2).  sample_type: the filter's JINC_SAMPLE_*.  scaled: 1 when a scale or an offset array
- * was given.  unit: the widest access the integer side allows (16, 4; 0: sample-sized accesses only).  vec_pixels: the leading pixels
- * of every row that move by such accesses, 16 / sample_bytes per lane and step; the rest of the row (all of it when vec_pixels is 0)
- * moves sample by sample.  width, rows: of the group's planes.
- * Copies up to `capacity` entries to `groups` (may be NULL) and returns their number, at most 4.  The record is emptied wherever the
+/* The most recent strided, shifted, packed10, v210, widened or narrowed call on the calling thread, scaled or not: the passes of its
+ * FIRST slice that moved samples between the caller's frames and the filter's dense stand-ins, by the numbers their launches got --
+ * which loop of a pass moved a group's samples is decided by these numbers and by nothing else.  One entry per channel group of the
+ * widening / narrowing / split / merge launches and one per field or block pass.  Order: the source side's passes first, then the
+ * destination side's, each side in the order of its groups' first planes (a narrowed call: the source's split groups, then the
+ * narrowing groups; a widened call: the widening groups or the field / block pass, then the destination's merge groups).
+ * direction: 0 widen_samples_kernel, 1 narrow_samples_kernel, 2 split_samples_kernel, 3 merge_samples_kernel, 4 unpack_fields,
+ * 5 pack_fields, 6 widen_fields, 7 unpack_v210, 8 pack_v210, 9 widen_v210.  n: samples per pixel on the caller's side (the step;
+ * 3 for the field and block passes).  members: planes of the call in the group.  sample_bytes: of the integer side (1 or 2) for
+ * directions 0 and 1, else the filter's component size.  sample_type: the filter's JINC_SAMPLE_*.  scaled: 1 when a scale or an
+ * offset array was given (directions 0 and 1 only).  unit: the widest access the caller's side allows (16, 4; 0: sample-sized accesses
+ * only).  vec_pixels: the leading pixels of every row that move by such accesses -- 16 / sample_bytes per lane and step in the
+ * group passes, 8 in the field passes, and for the v210 passes 6 x the blocks that move in pairs; the rest of the row (all of it
+ * when vec_pixels is 0) moves sample by sample, word by word or block by block.  width, rows: of the group's planes (v210: of the
+ * luma plane).  shifted: 1 when the split / merge launch a group travelled in took the shifted form -- decided per launch, over all
+ * groups of one step: a group without a shift beside a shifted one of the same step shows 1 -- else 0.
+ * Copies up to `capacity` entries to `groups` (may be NULL) and returns their number, at most 8.  The record is emptied wherever the
  * counts of jinc_debug_last_strided are reset: by every strided, shifted, packed10, v210 and widened / narrowed call that reaches the
- * device check, so that one refused behind it (a pitch, a frame stride) leaves 0 entries; a call refused on its arguments alone,
- * in front of the device check, leaves both records as they were. */
+ * device check, so that one refused behind it (a pitch, a frame stride) leaves 0 entries, as does a call whose every step is 1
+ * and every shift 0 (it is jinc_filter_process_device); a call refused on its arguments alone, in front of the device check, leaves
+ * both records as they were. */
 typedef struct jinc_group_info {
-    int direction, n, members, sample_bytes, sample_type, scaled, unit, vec_pixels, width, rows;
+    int direction, n, members, sample_bytes, sample_type, scaled, unit, vec_pixels, width, rows, shifted;
 } jinc_group_info;
 JINC_API int jinc_debug_last_groups(jinc_group_info *groups, int capacity);
 /* Border frame of exactly periodic plans: -1 (default) = by call size (strip kernels from ~5e9 taps per call on, one gather

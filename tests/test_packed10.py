@@ -194,6 +194,21 @@ def test_multiples_of_4_only(gpu_pkg, O, src_align, dst_align, geom, n):
     """Lead 68, pitch and frame stride 4 mod 16: dword accesses on that side.  (Multiples of 16 on both sides: every other test.)"""
     torch = pytest.importorskip("torch")
     check_call(torch, O, gpu_pkg, "YUV444P10", geom, n, Y410, Y410, src_align=src_align, dst_align=dst_align)
+    # the record (jinc_debug_last_groups): unpack_fields is direction 4, pack_fields 5; a lane moves 8 pixels per step
+    unpack, pack = gpu_pkg.last_groups()
+    assert (unpack["direction"], unpack["unit"], unpack["vec_pixels"], unpack["width"], unpack["rows"]) == (4, src_align, geom[0] // 8 * 8, geom[0], geom[1]), unpack
+    assert (pack["direction"], pack["unit"], pack["vec_pixels"], pack["width"], pack["rows"]) == (5, dst_align, geom[2] // 8 * 8, geom[2], geom[3]), pack
+
+
+def test_rows_longer_than_one_trip_of_the_wave_on_both_sides(gpu_pkg, O):
+    """526 x 7 -> 1052 x 14: a lane owns 8 pixels and a wave's trip is 512, so the source's 520 + 6 send lane 0 on a second trip of the
+    vector loop in unpack_fields_kernel, and the destination's 1048 + 4 are two whole trips and three lanes of a third in
+    pack_fields_kernel."""
+    torch = pytest.importorskip("torch")
+    check_call(torch, O, gpu_pkg, "YUV444P10", (526, 7, 1052, 14), 2, Y410, Y410)
+    unpack, pack = gpu_pkg.last_groups()
+    assert (unpack["direction"], unpack["unit"], unpack["vec_pixels"], unpack["width"]) == (4, 16, 520, 526) and unpack["vec_pixels"] > 512
+    assert (pack["direction"], pack["unit"], pack["vec_pixels"], pack["width"]) == (5, 16, 1048, 1052) and pack["vec_pixels"] > 512
 
 
 def test_the_smallest_pitch_is_accepted(gpu_pkg, O):

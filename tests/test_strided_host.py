@@ -3,6 +3,7 @@ the grouping of strided planes into channel groups (csrc/dispatch.cpp strided_gr
 needed."""
 import ctypes as C
 import itertools
+import threading
 
 import numpy as np
 import pytest
@@ -31,22 +32,35 @@ def test_the_groups_record_mirrors_the_header_and_is_empty_without_a_call(pkg):
     flat = " ".join(test_header.split())
     fields = [n for n, _ in pkg.GroupInfo._fields_]
     assert "typedef struct jinc_group_info { int " + ", ".join(fields) + "; } jinc_group_info;" in flat
-    assert C.sizeof(pkg.GroupInfo) == 4 * len(fields) == 40
-    L = pkg.lib()
-    assert L.jinc_debug_last_groups(None, 0) == 0 and L.jinc_debug_last_groups(None, 4) == 0
-    one = (pkg.GroupInfo * 1)()
-    assert L.jinc_debug_last_groups(one, 1) == 0 and L.jinc_debug_last_groups(one, 0) == 0
-    assert pkg.last_groups() == []
-    for fmt, call in (("YUV420PS", "widened"), ("YUV420PS", "narrowed")):
-        f = pkg.Filter(pkg.FORMATS[fmt], 40, 24, 80, 48, device=-1)
-        with pytest.raises(pkg.JincError) as e:
-            if call == "widened":
-                f.process_device_widened([4096, 8192, 8193], [64] * 3, [1, 2, 2], None, 8, [0] * 3, [1 << 20, 2 << 20, 3 << 20], [512] * 3, None, [0] * 3, 1)
-            else:
-                f.process_device_narrowed([4096, 8192, 12288], [512] * 3, None, [0] * 3, [1 << 20, 2 << 20, (2 << 20) + 1], [80] * 3, [1, 2, 2], None, 8, [0] * 3, 1)
-        assert e.value.code == NO_DEVICE
-        assert pkg.last_groups() == [] and pkg.last_strided()[:3] == (0, 0, 0)
-        f.close()
+    assert C.sizeof(pkg.GroupInfo) == 4 * len(fields) == 44 and fields[-1] == "shifted"
+    # (both records are the calling thread's: a thread of its own has made no call, whatever the tests before this one left)
+    failures = []
+
+    def in_a_fresh_thread():
+        try:
+            L = pkg.lib()
+            assert L.jinc_debug_last_groups(None, 0) == 0 and L.jinc_debug_last_groups(None, 8) == 0
+            one = (pkg.GroupInfo * 1)()
+            assert L.jinc_debug_last_groups(one, 1) == 0 and L.jinc_debug_last_groups(one, 0) == 0
+            assert pkg.last_groups() == []
+            for fmt, call in (("YUV420PS", "widened"), ("YUV420PS", "narrowed")):
+                f = pkg.Filter(pkg.FORMATS[fmt], 40, 24, 80, 48, device=-1)
+                with pytest.raises(pkg.JincError) as e:
+                    if call == "widened":
+                        f.process_device_widened([4096, 8192, 8193], [64] * 3, [1, 2, 2], None, 8, [0] * 3, [1 << 20, 2 << 20, 3 << 20], [512] * 3, None, [0] * 3, 1)
+                    else:
+                        f.process_device_narrowed([4096, 8192, 12288], [512] * 3, None, [0] * 3, [1 << 20, 2 << 20, (2 << 20) + 1], [80] * 3, [1, 2, 2], None, 8, [0] * 3, 1)
+                assert e.value.code == NO_DEVICE
+                assert pkg.last_groups() == [] and pkg.last_strided()[:3] == (0, 0, 0)
+                f.close()
+        except BaseException as e:   # noqa: B036 (handed to the test's thread below)
+            failures.append(e)
+
+    t = threading.Thread(target=in_a_fresh_thread)
+    t.start()
+    t.join()
+    if failures:
+        raise failures[0]
 
 
 def _call(pkg, f, src_steps, dst_steps, src=(256, 512, 768, 1024), dst=(4096, 8192, 12288, 16384)):

@@ -233,6 +233,20 @@ def test_multiples_of_4_only(gpu_pkg, O, src_align, dst_align, geom, n):
     """Lead 68, pitch and frame stride 4 mod 16: dword accesses on that side.  (Multiples of 16 on both sides: every other test.)"""
     torch = pytest.importorskip("torch")
     check_call(torch, O, gpu_pkg, geom, n, src_align=src_align, dst_align=dst_align)
+    # the record (jinc_debug_last_groups): unpack_v210 is direction 7, pack_v210 8; vec_pixels: 6 pixels x the blocks that move in pairs
+    unpack, pack = gpu_pkg.last_groups()
+    assert (unpack["direction"], unpack["unit"], unpack["vec_pixels"], unpack["width"], unpack["rows"]) == (7, src_align, 6 * (geom[0] // 6 // 2 * 2), geom[0], geom[1]), unpack
+    assert (pack["direction"], pack["unit"], pack["vec_pixels"], pack["width"], pack["rows"]) == (8, dst_align, 6 * (geom[2] // 6 // 2 * 2), geom[2], geom[3]), pack
+
+
+def test_source_rows_longer_than_one_trip_of_the_wave(gpu_pkg, O):
+    """782 x 7 -> 1564 x 14: 130 whole blocks and a 2-pixel partial one on the source, so lanes 0 and 1 make a second trip of the
+    paired loop of unpack_v210_kernel, DPP exchange included; the destination's 260 whole blocks are four trips and four lanes."""
+    torch = pytest.importorskip("torch")
+    check_call(torch, O, gpu_pkg, (782, 7, 1564, 14), 2)
+    unpack, pack = gpu_pkg.last_groups()
+    assert (unpack["direction"], unpack["unit"], unpack["vec_pixels"], unpack["width"]) == (7, 16, 780, 782) and unpack["vec_pixels"] > 6 * 128
+    assert (pack["direction"], pack["unit"], pack["vec_pixels"], pack["width"]) == (8, 16, 1560, 1564)
 
 
 # ---- 5. / 6. pitches ---------------------------------------------------------------------------------------------------------------------

@@ -100,6 +100,15 @@ def test_word_rows_longer_than_one_trip_of_the_wave(gpu_pkg):
     check_call(torch, gpu_pkg, "packed10", "YUV444PS", (1030, 8, 2060, 16), 1)
 
 
+def test_v210_rows_longer_than_one_trip_of_the_wave(gpu_pkg):
+    """782 pixels a row: 130 whole blocks and a 2-pixel partial one, so lanes 0 and 1 make a second trip of the paired loop of
+    widen_v210_kernel, DPP exchange included."""
+    torch = pytest.importorskip("torch")
+    check_call(torch, gpu_pkg, "v210", "YUV422PS", (782, 7, 1564, 14), 2)
+    (widen,) = gpu_pkg.last_groups()
+    assert (widen["direction"], widen["unit"], widen["vec_pixels"], widen["width"]) == (9, 16, 780, 782) and widen["vec_pixels"] > 6 * 128
+
+
 # ---- 3. against the oracle and the integer filter ------------------------------------------------------------------------------------------
 
 KINDS = [("packed10", "YUV444P", WORDS_WIDE), ("v210", "YUV422P", V210_WIDE)]
@@ -183,6 +192,12 @@ def test_alignment_classes(gpu_pkg, kind, name, geom, align):
     dwords)."""
     torch = pytest.importorskip("torch")
     check_call(torch, gpu_pkg, kind, name, geom, 3, align=align)
+    # the record (jinc_debug_last_groups): widen_fields is direction 6 (8 pixels a lane and step), widen_v210 9 (vec_pixels: 6 pixels x
+    # the blocks that move in pairs); the destination's planes are dense and leave no entry
+    (widen,) = gpu_pkg.last_groups()
+    vec = geom[0] // 8 * 8 if kind == "packed10" else 6 * (geom[0] // 6 // 2 * 2)
+    assert (widen["direction"], widen["unit"], widen["vec_pixels"], widen["width"], widen["rows"]) == (6 if kind == "packed10" else 9, align, vec, geom[0], geom[1]), widen
+    assert widen["sample_bytes"] == gpu_pkg.FORMATS[name].sample_bytes and widen["sample_type"] == gpu_pkg.FORMATS[name].sample_type
 
 
 @pytest.mark.parametrize("kind,name,geom", [("packed10", "YUV444PS", WORDS_SHORT), ("v210", "YUV422PS", V210_WIDE), ("v210", "YUV422PH", V210_SHORT)],
