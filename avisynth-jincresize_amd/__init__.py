@@ -99,7 +99,9 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_process_device_widened_packed10", "jinc_filter_process_device_widened_v210",
            "jinc_filter_process_device_narrowed", "jinc_debug_narrow",
            "jinc_filter_process_device_widened_scaled", "jinc_filter_process_device_narrowed_scaled", "jinc_code_range",
-           "jinc_debug_widen_scaled", "jinc_debug_narrow_scaled"]
+           "jinc_debug_widen_scaled", "jinc_debug_narrow_scaled",
+           "jinc_filter_process_device_narrowed_packed10", "jinc_filter_process_device_narrowed_v210",
+           "jinc_debug_narrow_fields", "jinc_debug_narrow_v210"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -191,6 +193,10 @@ def lib():
         L.jinc_debug_convert_bfloat16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.jinc_debug_narrow.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.jinc_debug_narrow_scaled.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int]
+        L.jinc_filter_process_device_narrowed_packed10.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_narrowed_v210.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.jinc_debug_narrow_fields.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_int]
+        L.jinc_debug_narrow_v210.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.jinc_debug_widen_scaled.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.jinc_filter_set_profiling.argtypes = [C.c_void_p, C.c_int]
         L.jinc_filter_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int),
@@ -346,7 +352,7 @@ def last_groups() -> List[Dict[str, int]]:
     (scaled or not) as their launches got them (jinc_debug_last_groups, test header): one dict per channel group of the widening,
     narrowing, split and merge launches and one per field or block pass, the source side's first, then the destination side's, each
     side in the order of its groups' first planes.  Keys: direction (0 widened, 1 narrowed, 2 split, 3 merge, 4 / 5 / 6 unpack_fields /
-    pack_fields / widen_fields, 7 / 8 / 9 unpack_v210 / pack_v210 / widen_v210), n (samples per pixel), members, sample_bytes,
+    pack_fields / widen_fields, 7 / 8 / 9 unpack_v210 / pack_v210 / widen_v210, 10 / 11 narrow_fields / narrow_v210), n (samples per pixel), members, sample_bytes,
     sample_type (SAMPLE_*), scaled, unit (16, 4 or 0), vec_pixels (0: the whole row moved sample by sample; v210: 6 x the blocks
     that moved in pairs), width, rows and shifted (split / merge: the launch took the shifted form).  At most 8; empty after a call
     on dense planes alone."""
@@ -559,6 +565,57 @@ def debug_narrow_scaled(values: np.ndarray, dst_bits: int, shift: int, scale: fl
     out = np.zeros(values.shape, dtype=np.uint8 if dst_bits == 8 else np.uint16)
     rc = lib().jinc_debug_narrow_scaled(values.ctypes.data, kind, out.ctypes.data, values.size, int(dst_bits), int(shift), float(scale),
                                         float(offset), device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return out
+
+
+def _hook_planes(planes, bfloat16):
+    """The three rows of debug_narrow_fields / debug_narrow_v210 as contiguous arrays of one kind, and that kind."""
+    planes = [np.ascontiguousarray(p) for p in planes]
+    if len(planes) != 3:
+        raise ValueError("three planes are needed")
+    if bfloat16:
+        if any(p.dtype != np.uint16 for p in planes):
+            raise TypeError("bfloat16 values are given as uint16 bit patterns")
+        return planes, SAMPLE_BFLOAT16
+    if all(p.dtype == np.float16 for p in planes):
+        return planes, SAMPLE_FLOAT16
+    return [np.ascontiguousarray(p, dtype=np.float32) for p in planes], SAMPLE_DEFAULT
+
+
+def _three_floats(values):
+    return None if values is None else (C.c_float * 3)(*[float(v) for v in values])
+
+
+def debug_narrow_fields(planes, offsets, fill: int = 0, scale=None, offset=None, bfloat16: bool = False, device: int = 0) -> np.ndarray:
+    """The pass of process_device_narrowed_packed10 applied to one dense row per plane on the device (test hook): `planes` are three
+    rows of one length, float32 or float16 values, or with bfloat16=True uint16 bit patterns; scale / offset are three floats each or
+    None.  Returns the words (v0 << offsets[0]) | (v1 << offsets[1]) | (v2 << offsets[2]) | (fill & ~fields) as uint32."""
+    planes, kind = _hook_planes(planes, bfloat16)
+    n = planes[0].size
+    if planes[1].size != n or planes[2].size != n:
+        raise ValueError("the three planes must have one length")
+    out = np.zeros(n, dtype=np.uint32)
+    rc = lib().jinc_debug_narrow_fields((C.c_void_p * 3)(*[p.ctypes.data for p in planes]), kind, out.ctypes.data, n,
+                                        (C.c_int * 3)(*[int(o) for o in offsets]), int(fill) & 0xFFFFFFFF, _three_floats(scale),
+                                        _three_floats(offset), device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return out
+
+
+def debug_narrow_v210(planes, scale=None, offset=None, bfloat16: bool = False, device: int = 0) -> np.ndarray:
+    """The pass of process_device_narrowed_v210 applied to one dense row on the device (test hook): planes[0] holds `width` (even) luma
+    values, planes[1] and planes[2] width / 2 chroma values each, kinds as for debug_narrow_fields.  Returns the row's blocks as
+    uint32 words, four per block."""
+    planes, kind = _hook_planes(planes, bfloat16)
+    width = planes[0].size
+    if width % 2 or planes[1].size != width // 2 or planes[2].size != width // 2:
+        raise ValueError("an even number of luma values and half as many of each chroma plane are needed")
+    out = np.zeros(4 * ((width + 5) // 6), dtype=np.uint32)
+    rc = lib().jinc_debug_narrow_v210((C.c_void_p * 3)(*[p.ctypes.data for p in planes]), kind, out.ctypes.data, width, _three_floats(scale),
+                                      _three_floats(offset), device)
     if rc != 0:
         raise JincError(rc, lib().jinc_last_error().decode())
     return out
@@ -1125,6 +1182,49 @@ class Filter:
             self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_S4, src_strides), arr(_P4, dst_ptrs),
             arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_I4, dst_shifts), int(dst_bits), arr(_F4, dst_scales), arr(_F4, dst_offsets),
             arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
+
+    def process_device_narrowed_packed10(self, src_ptrs, src_pitches, src_steps, src_strides, dst_ptr: int, dst_pitch: int, dst_offsets,
+                                         dst_fill: int, dst_scales, dst_offsets_add, dst_stride: int, nframes: int, stream: int = 0) -> None:
+        """This fp32 / binary16 / bfloat16 filter's results into 10:10:10:2 words (jinc_filter_process_device_narrowed_packed10; three
+        components, no sub-sampling): the source side is process_device_strided's on this filter; the destination is ONE buffer of
+        32-bit words, one per pixel, and a stored word is (v0 << dst_offsets[0]) | (v1 << dst_offsets[1]) | (v2 << dst_offsets[2]) |
+        (dst_fill & ~fields) with v_i = rint(clip(fl32(fl32(r_i * dst_scales[i]) + dst_offsets_add[i]), 0, 1023)) and r_i what
+        process_device stores (packed10_layout names the usual words).  dst_scales None means all 1.0, dst_offsets_add None all 0.0;
+        steps and source frame strides may be None."""
+        n = self.fmt.planes
+
+        def arr(kind, values, count=n):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(min(count, len(values))):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_narrowed_packed10(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_S4, src_strides), C.c_void_p(dst_ptr),
+            int(dst_pitch), arr(C.c_int * 3, dst_offsets, 3), int(dst_fill) & 0xFFFFFFFF, arr(C.c_float * 3, dst_scales, 3),
+            arr(C.c_float * 3, dst_offsets_add, 3), C.c_size_t(int(dst_stride or 0)), int(nframes), C.c_void_p(stream)))
+
+    def process_device_narrowed_v210(self, src_ptrs, src_pitches, src_steps, src_strides, dst_ptr: int, dst_pitch: int, dst_scales,
+                                     dst_offsets_add, dst_stride: int, nframes: int, stream: int = 0) -> None:
+        """This fp32 / binary16 / bfloat16 4:2:2 filter's results into v210 blocks (jinc_filter_process_device_narrowed_v210;
+        YUV422PS, YUV422PH, YUV422PBF): the source side is process_device_strided's on this filter; the destination is ONE buffer of
+        16-byte blocks of six pixels, a row is v210_row_bytes(width) bytes, every field rint(clip(fl32(fl32(r * dst_scales[i]) +
+        dst_offsets_add[i]), 0, 1023)) of its plane i.  dst_scales None means all 1.0, dst_offsets_add None all 0.0; steps and source
+        frame strides may be None."""
+        n = self.fmt.planes
+
+        def arr(kind, values, count=n):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(min(count, len(values))):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_narrowed_v210(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_S4, src_strides), C.c_void_p(dst_ptr),
+            int(dst_pitch), arr(C.c_float * 3, dst_scales, 3), arr(C.c_float * 3, dst_offsets_add, 3), C.c_size_t(int(dst_stride or 0)),
+            int(nframes), C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
     last_groups = staticmethod(last_groups)

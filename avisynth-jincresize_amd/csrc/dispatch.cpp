@@ -868,7 +868,7 @@ thread_local StridedReport t_last_strided;
 thread_local GroupsReport t_last_groups;  // cleared wherever t_last_strided is: what a call that runs no pass leaves
 
 // GroupRecord::direction
-enum : int { kWiden = 0, kNarrow = 1, kSplit = 2, kMerge = 3, kUnpackFields = 4, kPackFields = 5, kWidenFields = 6, kUnpackV210 = 7, kPackV210 = 8, kWidenV210 = 9 };
+enum : int { kWiden = 0, kNarrow = 1, kSplit = 2, kMerge = 3, kUnpackFields = 4, kPackFields = 5, kWidenFields = 6, kUnpackV210 = 7, kPackV210 = 8, kWidenV210 = 9, kNarrowFields = 10, kNarrowV210 = 11 };
 
 // One entry of jinc_debug_last_groups: a pass of a slice by the numbers its launch gets.  Only the call's first slice is kept: the
 // later ones differ in their frames alone.  The split lambda of a slice runs in front of its merge lambda and each fills its
@@ -896,11 +896,11 @@ void record_shifted(int from, int direction, int step, bool shifted, int first_f
         if (t_last_groups.g[i].direction == direction && t_last_groups.g[i].step == step) t_last_groups.g[i].shifted = shifted ? 1 : 0;
 }
 // The field and block passes: the three planes of the filter as one group (step and members 3), samples of the filter's size.
-void record_fields(const jinc_filter& f, int direction, const jinc::FieldArgs& a, int first_frame) {
-    record_pass(f, direction, 3, 3, static_cast<size_t>(f.vi_in.component_size), false, a.unit, a.vec_pixels, a.width, a.rows, first_frame);
+void record_fields(const jinc_filter& f, int direction, const jinc::FieldArgs& a, int first_frame, bool scaled = false) {
+    record_pass(f, direction, 3, 3, static_cast<size_t>(f.vi_in.component_size), scaled, a.unit, a.vec_pixels, a.width, a.rows, first_frame);
 }
-void record_v210(const jinc_filter& f, int direction, const jinc::V210Args& a, int first_frame) {  // (vec_pixels: the pixels of the blocks that move in pairs)
-    record_pass(f, direction, 3, 3, static_cast<size_t>(f.vi_in.component_size), false, a.unit, 6u * jinc::v210::paired_blocks(a), a.width, a.rows, first_frame);
+void record_v210(const jinc_filter& f, int direction, const jinc::V210Args& a, int first_frame, bool scaled = false) {  // (vec_pixels: the pixels of the blocks that move in pairs)
+    record_pass(f, direction, 3, 3, static_cast<size_t>(f.vi_in.component_size), scaled, a.unit, 6u * jinc::v210::paired_blocks(a), a.width, a.rows, first_frame);
 }
 
 // Dense planes behind a call: 1 GiB unless the knob says otherwise.  Derived, not measured: a 1080p -> 4K 4:2:0 frame has
@@ -1610,6 +1610,100 @@ void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pi
                     ++launches;
                 }
             return launches;
+        });
+}
+
+// ---- jinc_filter_process_device_narrowed_packed10 / _v210: an fp32 / binary16 / bfloat16 filter's results into Y410 / RGB10A2 words and v210 blocks ----
+// The mirror image of enqueue_widened_packed10 / _v210: the destination is ONE group of the filter's three planes, as the packed side
+// of enqueue_packed10 or the v210 side of enqueue_v210, and every destination plane takes a dense stand-in of the FILTER's type;
+// narrow_fields_kernel / narrow_v210_kernel (kernel_narrow.hip) store lrintf(clamp(r, 0, 1023)) from them -- behind the scaled calls'
+// multiply and add where an array was given -- as whole words / blocks: ONE launch per slice, which the report counts as a merge
+// launch.  The source side and its split are enqueue_narrowed's, and everything else is run_on_stand_ins, so these calls alternate
+// with strided, shifted, packed10, v210, widened and narrowed ones on one filter.
+// Dense planes per frame of a 4K destination (rows padded to 256 bytes: 3840 x 4 = 15 360, 1920 x 4 = 3840 x 2 = 7680 and 1920 x 2 =
+// 3840 are multiples already), planar source: Y410 from fp32 3 x 15 360 x 2160 = 99 532 800 bytes, floor(1 073 741 824 /
+// 99 532 800) = 10 frames under the 1 GiB default; from binary16 / bfloat16 3 x 7680 x 2160 = 49 766 400 bytes, 21 frames.  v210 from
+// fp32 (15 360 + 2 x 7680) x 2160 = 66 355 200 bytes, 16 frames; from the 16-bit types (7680 + 2 x 3840) x 2160 = 33 177 600 bytes,
+// 32 frames.  All below kSliceFrames, so no rounding: a call of 128 runs as 12 x 10 + 8, 6 x 21 + 2, 8 x 16 and 4 x 32.
+namespace {
+// The sides of such a call: the source enqueue_narrowed's, the destination one group of three stand-ins.
+void narrowed_words_sides(const jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
+                          int nframes, Side& in, Side& out) {
+    for (int i = 0; i < f.planecount; ++i) {
+        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
+        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
+        out.group_of[i] = out.channel_of[i] = 0;
+    }
+    out.ngroups = 1;
+    in.ngroups = groups_of_side(src, src_pitch, src_step, nullptr, nframes > 1 ? src_fs : nullptr, in.w, in.h, f.vi_in.component_size, f.planecount, in.group_of, in.channel_of);
+    check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
+}
+// The split of such a call's source side (enqueue_narrowed's): planes with a step other than 1 into their stand-ins.
+int split_narrowed(const jinc_filter& f, const Side& in, const void* const src[4], const int src_pitch[4], const int* src_step,
+                   const size_t* src_fs, char* scratch, int k0, int slice, int n, int nframes, hipStream_t stream) {
+    InterleaveArgs split[5];
+    const int recorded = t_last_groups.count;
+    fill_args(f, in, src, src_pitch, src_step, nullptr, src_fs, scratch, k0, slice, nframes, false, split);
+    int launches = 0;
+    for (int step = 2; step <= 4; ++step)
+        if (split[step].ngroups) {
+            bool shifted = false;
+            hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], f.vi_in.component_size, step, n, stream, &shifted)), "split launch");
+            record_shifted(recorded, kSplit, step, shifted, k0);
+            ++launches;
+        }
+    return launches;
+}
+}  // namespace
+
+void enqueue_narrowed_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
+                               void* dst, int dst_pitch, const int* dst_fields, unsigned dst_fill, const float* dst_scale,
+                               const float* dst_offset, size_t dst_fs, int nframes, hipStream_t stream) {
+    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    t_last_groups.count = 0;
+    Side in, out;
+    narrowed_words_sides(f, src, src_pitch, src_step, src_fs, nframes, in, out);
+    check_packed10_side(dst, dst_pitch, &dst_fs, out.w[0], nframes);  // (filter.cpp has refused these already, with messages of this call's own)
+    // (every destination plane has a stand-in: run_on_stand_ins reads none of these)
+    void* const dst_planes[4] = {dst, dst, dst, nullptr};
+    const int dst_pitches[4] = {dst_pitch, dst_pitch, dst_pitch, 0};
+    const size_t dst_strides[4] = {dst_fs, dst_fs, dst_fs, 0};
+    const bool scaled = dst_scale || dst_offset;
+    run_on_stand_ins(
+        f, in, out, src, src_pitch, src_fs, dst_planes, dst_pitches, dst_strides, nframes, stream,
+        [&](char* scratch, int k0, int slice, int n) { return split_narrowed(f, in, src, src_pitch, src_step, src_fs, scratch, k0, slice, n, nframes, stream); },
+        [&](char* scratch, int k0, int slice, int n) {
+            jinc::NarrowFieldArgs a;
+            static_cast<jinc::FieldArgs&>(a) = field_args(out, dst, dst_pitch, dst_strides, dst_fields, dst_fill, scratch, k0, slice, nframes);
+            for (int c = 0; c < 3; ++c) a.value_scale[c] = dst_scale ? dst_scale[c] : 1.f, a.value_offset[c] = dst_offset ? dst_offset[c] : 0.f;
+            record_fields(f, kNarrowFields, a, k0, scaled);
+            hip_check(static_cast<hipError_t>(jinc::launch_narrow_fields(a, f.sample_kind(), n, stream, scaled)), "narrow fields launch");
+            return 1;
+        });
+}
+
+void enqueue_narrowed_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
+                           void* dst, int dst_pitch, const float* dst_scale, const float* dst_offset, size_t dst_fs, int nframes,
+                           hipStream_t stream) {
+    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    t_last_groups.count = 0;
+    Side in, out;
+    narrowed_words_sides(f, src, src_pitch, src_step, src_fs, nframes, in, out);
+    check_v210_side(dst, dst_pitch, &dst_fs, out, nframes);  // (filter.cpp has refused these already, with messages of this call's own)
+    void* const dst_planes[4] = {dst, dst, dst, nullptr};
+    const int dst_pitches[4] = {dst_pitch, dst_pitch, dst_pitch, 0};
+    const size_t dst_strides[4] = {dst_fs, dst_fs, dst_fs, 0};
+    const bool scaled = dst_scale || dst_offset;
+    run_on_stand_ins(
+        f, in, out, src, src_pitch, src_fs, dst_planes, dst_pitches, dst_strides, nframes, stream,
+        [&](char* scratch, int k0, int slice, int n) { return split_narrowed(f, in, src, src_pitch, src_step, src_fs, scratch, k0, slice, n, nframes, stream); },
+        [&](char* scratch, int k0, int slice, int n) {
+            jinc::NarrowV210Args a;
+            static_cast<jinc::V210Args&>(a) = v210_args(out, dst, dst_pitch, dst_strides, scratch, k0, slice, nframes);
+            for (int c = 0; c < 3; ++c) a.value_scale[c] = dst_scale ? dst_scale[c] : 1.f, a.value_offset[c] = dst_offset ? dst_offset[c] : 0.f;
+            record_v210(f, kNarrowV210, a, k0, scaled);
+            hip_check(static_cast<hipError_t>(jinc::launch_narrow_v210(a, f.sample_kind(), n, stream, scaled)), "narrow v210 launch");
+            return 1;
         });
 }
 

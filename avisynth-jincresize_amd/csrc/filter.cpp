@@ -71,6 +71,25 @@ std::string refuse_widened_words(const jinc_filter* f, const char* what, const v
     return std::string();
 }
 
+// What the two narrowed calls for words and blocks refuse alike, behind the checks of the filter and the offsets: the source steps,
+// then base, pitch and frame stride of the one destination buffer (`what`: "packed 10-bit words" / "v210 blocks"; row_bytes: what a
+// row occupies).  Returns a message, empty when there is nothing to refuse.
+std::string refuse_narrowed_words(const jinc_filter* f, const char* what, const void* dst, int dst_pitch, size_t dst_frame_stride,
+                                  size_t row_bytes, const char* row_text, const int* src_sample_step, int nframes) {
+    for (int i = 0; src_sample_step && i < f->planecount; ++i)
+        if (src_sample_step[i] < 1 || src_sample_step[i] > 4)
+            return "JincResize: source sample step of a narrowed call for " + std::string(what) + " must be in 1..4 (got " +
+                   std::to_string(src_sample_step[i]) + ").";
+    if (reinterpret_cast<uintptr_t>(dst) % 4) return "JincResize: narrowed " + std::string(what) + " are not aligned to 4 bytes.";
+    if (dst_pitch % 4) return "JincResize: pitch " + std::to_string(dst_pitch) + " of narrowed " + what + " is not a multiple of 4.";
+    if (nframes > 1 && dst_frame_stride % 4)
+        return "JincResize: frame stride " + std::to_string(dst_frame_stride) + " of narrowed " + what + " is not a multiple of 4.";
+    if (dst_pitch <= 0 || static_cast<size_t>(dst_pitch) < row_bytes)
+        return "JincResize: pitch " + std::to_string(dst_pitch) + " of narrowed " + what + " is smaller than the row's " + std::to_string(row_bytes) +
+               " bytes (" + row_text + ").";
+    return std::string();
+}
+
 // What the two scaled calls refuse of their own: a scale or offset of a used plane that is NaN or infinite, a scale that is zero.
 // `side` is "source" (widened) or "destination" (narrowed).  Empty: nothing to refuse.
 std::string refuse_scale_offset(const char* side, const float* scale, const float* offset, int planes) {
@@ -594,6 +613,76 @@ int jinc_filter_process_device_widened_v210(jinc_filter* f, const void* src, int
     });
 }
 
+int jinc_filter_process_device_narrowed_packed10(jinc_filter* f, const void* const src[4], const int src_pitch[4],
+                                                 const int src_sample_step[4], const size_t src_frame_stride[4], void* dst, int dst_pitch,
+                                                 const int dst_field_offset[3], unsigned dst_fill, const float dst_scale[3],
+                                                 const float dst_offset[3], size_t dst_frame_stride, int nframes, void* hip_stream) {
+    // the filter, the offsets, the source steps, the destination's base, pitch and frame stride and the scales first (they need no
+    // device), then the checks of jinc_filter_process_device_shifted in its order
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (!f->float_samples())
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed packed 10:10:10:2 words need an fp32, binary16 or bfloat16 filter; this filter has " +
+                                              std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_packed10).");
+    if (f->planecount != 3 || f->subsampled)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed packed 10:10:10:2 words need a float filter with three components and no sub-sampling "
+                                          "(YUV444PS, YUV444PH, RGBPS, RGBPH and their bfloat16 twins); this filter has " + std::to_string(f->planecount) +
+                                              " component(s), sub_w " + std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
+    for (int i = 0; dst_field_offset && i < 3; ++i)
+        if (dst_field_offset[i] < 0 || dst_field_offset[i] > 22)
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: a field offset of a narrowed packed 10:10:10:2 word must be in 0..22 (got " +
+                                                  std::to_string(dst_field_offset[i]) + ").");
+    for (int i = 0; dst_field_offset && i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (dst_field_offset[i] - dst_field_offset[j] < 10 && dst_field_offset[j] - dst_field_offset[i] < 10)
+                return fail(JINC_ERR_INVALID_ARG, "JincResize: two fields of a narrowed packed 10:10:10:2 word overlap (offsets " +
+                                                      std::to_string(dst_field_offset[i]) + " and " + std::to_string(dst_field_offset[j]) + ").");
+    int w = 0, h = 0;
+    f->plane_dims(f->vi_out, 0, w, h);
+    std::string refusal = refuse_narrowed_words(f, "packed 10-bit words", dst, dst_pitch, dst_frame_stride, 4 * static_cast<size_t>(w), "4 * width",
+                                                src_sample_step, nframes);
+    if (refusal.empty()) refusal = refuse_scale_offset("packed 10-bit destination", dst_scale, dst_offset, 3);
+    if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
+    if (!src || !src_pitch || !dst || !dst_field_offset) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && !src_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_narrowed_packed10(*f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_field_offset, dst_fill, dst_scale,
+                                  dst_offset, dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int jinc_filter_process_device_narrowed_v210(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                                             const size_t src_frame_stride[4], void* dst, int dst_pitch, const float dst_scale[3],
+                                             const float dst_offset[3], size_t dst_frame_stride, int nframes, void* hip_stream) {
+    // the filter, the source steps, the destination's base, pitch and frame stride and the scales first (they need no device), then
+    // the checks of jinc_filter_process_device_shifted in its order
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (!f->float_samples())
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed v210 blocks need an fp32, binary16 or bfloat16 filter; this filter has " +
+                                              std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_v210).");
+    if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed v210 blocks need a float filter with three components and 4:2:2 sub-sampling "
+                                          "(YUV422PS, YUV422PH and their bfloat16 twin: sub_w 1, sub_h 0); this filter has " + std::to_string(f->planecount) +
+                                              " component(s), sub_w " + std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
+    int w = 0, h = 0;
+    f->plane_dims(f->vi_out, 0, w, h);
+    std::string refusal = refuse_narrowed_words(f, "v210 blocks", dst, dst_pitch, dst_frame_stride, v210_row_bytes(w), "16 * ceil(width / 6)",
+                                                src_sample_step, nframes);
+    if (refusal.empty()) refusal = refuse_scale_offset("v210 destination", dst_scale, dst_offset, 3);
+    if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
+    if (!src || !src_pitch || !dst) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && !src_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_narrowed_v210(*f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_scale, dst_offset, dst_frame_stride,
+                              nframes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
 int jinc_packed10_layout(const char* name, int field_offset[3], unsigned* opaque_fill) {
     // offsets of the library's planes (Y, U, V or G, B, R) in the word
     static const struct {
@@ -912,6 +1001,88 @@ int jinc_debug_narrow_scaled(const void* in, int in_kind, void* out, int n, int 
         hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
         bounce_download(out, d_out, dst_bytes * n, "download of the samples");
         (void)hipFree(d_in);
+        (void)hipFree(d_out);
+    });
+}
+
+namespace {
+// What the two hooks below share: the kind, the pair per plane (finite, scale not zero) and the upload of ONE dense row per plane,
+// samples[c] of them in plane c, into buffers of the device's own (256-byte aligned, as the stand-ins are).
+int kernel_kind(int in_kind) { return in_kind == JINC_SAMPLE_FLOAT16 ? jinc::kSampleHalf : in_kind == JINC_SAMPLE_BFLOAT16 ? jinc::kSampleBFloat16 : 0; }
+bool hook_pairs_ok(const float* scale, const float* offset) {
+    for (int c = 0; c < 3; ++c) {
+        if (scale && (!std::isfinite(scale[c]) || scale[c] == 0.f)) return false;
+        if (offset && !std::isfinite(offset[c])) return false;
+    }
+    return true;
+}
+}  // namespace
+
+int jinc_debug_narrow_fields(const void* const in[3], int in_kind, uint32_t* out_words, int n, const int field_offset[3], unsigned fill,
+                             const float* scale, const float* offset, int device) {
+    const bool kind_ok = in_kind == JINC_SAMPLE_DEFAULT || in_kind == JINC_SAMPLE_FLOAT16 || in_kind == JINC_SAMPLE_BFLOAT16;
+    if (!in || !in[0] || !in[1] || !in[2] || !out_words || n < 0 || !kind_ok || !field_offset || !hook_pairs_ok(scale, offset))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    for (int i = 0; i < 3; ++i) {
+        if (field_offset[i] < 0 || field_offset[i] > 22) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+        for (int j = i + 1; j < 3; ++j)
+            if (field_offset[i] - field_offset[j] < 10 && field_offset[j] - field_offset[i] < 10) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    }
+    if (n == 0) return JINC_OK;
+    const size_t in_bytes = in_kind == JINC_SAMPLE_DEFAULT ? 4 : 2;
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        char *d_in[3] = {nullptr, nullptr, nullptr}, *d_out = nullptr;
+        jinc::NarrowFieldArgs a;  // one dense row: whole lanes of 8 pixels by 16-byte accesses, the rest word by word
+        uint32_t mask = 0;
+        for (int c = 0; c < 3; ++c) {
+            hip_check(hipMalloc(&d_in[c], in_bytes * (n + 1)), "hipMalloc");
+            bounce_upload(d_in[c], in[c], in_bytes * n, "upload of the values");
+            a.plane[c] = d_in[c];
+            a.offset[c] = static_cast<uint32_t>(field_offset[c]);
+            mask |= 1023u << field_offset[c];
+            a.value_scale[c] = scale ? scale[c] : 1.f, a.value_offset[c] = offset ? offset[c] : 0.f;
+        }
+        hip_check(hipMalloc(&d_out, 4 * static_cast<size_t>(n + 1)), "hipMalloc");
+        a.packed = d_out;
+        a.packed_pitch = static_cast<uint32_t>(4 * n), a.plane_pitch = static_cast<uint32_t>(in_bytes * n);
+        a.width = static_cast<uint32_t>(n), a.rows = 1, a.unit = 16, a.vec_pixels = a.width / 8u * 8u;
+        a.fill = fill & ~mask;
+        hip_check(static_cast<hipError_t>(jinc::launch_narrow_fields(a, kernel_kind(in_kind), 1, nullptr, scale || offset)), "narrow fields launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bounce_download(out_words, d_out, 4 * static_cast<size_t>(n), "download of the words");
+        for (int c = 0; c < 3; ++c) (void)hipFree(d_in[c]);
+        (void)hipFree(d_out);
+    });
+}
+
+int jinc_debug_narrow_v210(const void* const in[3], int in_kind, void* out_blocks, int width, const float* scale, const float* offset,
+                           int device) {
+    const bool kind_ok = in_kind == JINC_SAMPLE_DEFAULT || in_kind == JINC_SAMPLE_FLOAT16 || in_kind == JINC_SAMPLE_BFLOAT16;
+    if (!in || !in[0] || !in[1] || !in[2] || !out_blocks || width < 0 || (width & 1) || !kind_ok || !hook_pairs_ok(scale, offset))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    if (width == 0) return JINC_OK;
+    const size_t in_bytes = in_kind == JINC_SAMPLE_DEFAULT ? 4 : 2, row_bytes = v210_row_bytes(width);
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        char *d_in[3] = {nullptr, nullptr, nullptr}, *d_out = nullptr;
+        jinc::NarrowV210Args a;  // one dense row: the blocks in pairs, the odd whole block and the partial one sample by sample
+        for (int c = 0; c < 3; ++c) {
+            const size_t samples = static_cast<size_t>(c == 0 ? width : width / 2);
+            hip_check(hipMalloc(&d_in[c], in_bytes * (samples + 1)), "hipMalloc");
+            bounce_upload(d_in[c], in[c], in_bytes * samples, "upload of the values");
+            a.plane[c] = d_in[c];
+            a.value_scale[c] = scale ? scale[c] : 1.f, a.value_offset[c] = offset ? offset[c] : 0.f;
+        }
+        hip_check(hipMalloc(&d_out, row_bytes), "hipMalloc");
+        a.blocks = d_out;
+        a.block_pitch = static_cast<uint32_t>(row_bytes);
+        a.luma_pitch = static_cast<uint32_t>(in_bytes * width), a.chroma_pitch = static_cast<uint32_t>(in_bytes * (width / 2));
+        a.width = static_cast<uint32_t>(width), a.rows = 1, a.whole_blocks = a.width / 6, a.unit = 16;
+        hip_check(static_cast<hipError_t>(jinc::launch_narrow_v210(a, kernel_kind(in_kind), 1, nullptr, scale || offset)), "narrow v210 launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        bounce_download(out_blocks, d_out, row_bytes, "download of the blocks");
+        for (int c = 0; c < 3; ++c) (void)hipFree(d_in[c]);
         (void)hipFree(d_out);
     });
 }

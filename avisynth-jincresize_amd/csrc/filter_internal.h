@@ -1,7 +1,7 @@
 // filter_internal.h -- types and internal interfaces shared by the host translation units of libjincresize_hip.so:
 //   filter_args.cpp   Create_JincResize's argument handling and geometry derivation (configure)
 //   device_plan.cpp   device-resident plans: upload, launch planning for every kernel family (init_device)
-//   dispatch.cpp      per-call kernel selection and launches (enqueue; enqueue_strided: planes with a sample step; enqueue_packed10: 10:10:10:2 words; enqueue_v210: v210 blocks; enqueue_widened: integer samples into float / half filters; enqueue_widened_packed10 / _v210: 10:10:10:2 words and v210 blocks into them; enqueue_narrowed: their results into integer samples)
+//   dispatch.cpp      per-call kernel selection and launches (enqueue; enqueue_strided: planes with a sample step; enqueue_packed10: 10:10:10:2 words; enqueue_v210: v210 blocks; enqueue_widened: integer samples into float / half filters; enqueue_widened_packed10 / _v210: 10:10:10:2 words and v210 blocks into them; enqueue_narrowed: their results into integer samples; enqueue_narrowed_packed10 / _v210: their results into 10:10:10:2 words and v210 blocks)
 //   pipeline.cpp      frames in flight: device staging slots, pinned host ranges, H2D -> kernels -> D2H
 //   filter.cpp        the C ABI of include/jincresize_hip.h
 // Nothing here crosses the C ABI.
@@ -364,6 +364,18 @@ void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pi
                       void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift, int dst_bits,
                       const size_t* dst_fs, int nframes, hipStream_t stream, const float* dst_scale = nullptr,
                       const float* dst_offset = nullptr);
+// ... enqueue on an fp32 / binary16 / bfloat16 filter whose DESTINATION is one buffer of 10:10:10:2 words (fields: the three bit
+// offsets in plane order; fill: the bits outside them) or of v210 blocks: the three destination planes take dense stand-ins of the
+// filter's sample type and narrow_fields_kernel / narrow_v210_kernel store lrintf(clamp(r, 0, 1023)) -- behind the multiply and add
+// of dst_scale / dst_offset (three floats in plane order, either may be nullptr; both nullptr: the unscaled call) -- into the words
+// / blocks; the source side is enqueue_strided's (no shifts).  Filter, offsets, source steps, scales and the destination's base,
+// pitch and frame stride have been checked by filter.cpp.
+void enqueue_narrowed_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
+                               void* dst, int dst_pitch, const int* dst_fields, unsigned dst_fill, const float* dst_scale,
+                               const float* dst_offset, size_t dst_fs, int nframes, hipStream_t stream);
+void enqueue_narrowed_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
+                           void* dst, int dst_pitch, const float* dst_scale, const float* dst_offset, size_t dst_fs, int nframes,
+                           hipStream_t stream);
 // ... the channel groups of one side's planes (pure: test header jinc_debug_strided_groups); returns their number
 int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
                    const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]);
@@ -371,14 +383,14 @@ struct StridedReport {  // test header: jinc_debug_last_strided
     int split_launches = 0, merge_launches = 0, slices = 0;
     long long scratch_bytes = 0;
 };
-const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided / enqueue_packed10 / enqueue_v210 / enqueue_widened* / enqueue_narrowed
+const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided / enqueue_packed10 / enqueue_v210 / enqueue_widened* / enqueue_narrowed*
 // ... and the passes of that call's first slice as their launches got them (test header: jinc_debug_last_groups): the channel
 // groups of the widening / narrowing / split / merge launches and one entry per field or block pass, source side first, then the
 // destination side, each in the order of the groups' first planes (a side has at most one group per plane: 8 entries hold any
 // call).  Empty after a call that ran on the caller's dense planes alone and after a refused one.
 struct GroupRecord {
     // 0: widen_samples_kernel, 1: narrow_samples_kernel, 2: split_samples_kernel, 3: merge_samples_kernel, 4 / 5 / 6: unpack_fields /
-    // pack_fields / widen_fields, 7 / 8 / 9: unpack_v210 / pack_v210 / widen_v210
+    // pack_fields / widen_fields, 7 / 8 / 9: unpack_v210 / pack_v210 / widen_v210, 10 / 11: narrow_fields / narrow_v210
     int direction = 0;
     int step = 0, members = 0, sample_bytes = 0, sample_type = 0, scaled = 0;  // sample_type: the filter's JINC_SAMPLE_*
     uint32_t unit = 0, vec_pixels = 0, width = 0, rows = 0;

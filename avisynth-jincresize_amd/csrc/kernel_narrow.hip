@@ -14,10 +14,21 @@
 // assembly, no LDS, no scratch.
 // The scaled forms (jinc_filter_process_device_narrowed_scaled) are the same kernel with one v_mul_f32 and one v_add_f32 per sample
 // in front of the conversion (scale[c], offset[c] of the group's channel in scalar registers; -ffp-contract=off keeps them apart).
+//
+// Two more destinations whose samples neither a step nor a shift addresses (jinc_filter_process_device_narrowed_packed10 / _v210;
+// dispatch.cpp enqueue_narrowed_packed10 / enqueue_narrowed_v210): 10:10:10:2 words -- Y410, R10G10B10A2 and kin -- and v210 blocks.
+// narrow_fields_kernel has the shape of pack_fields_kernel and narrow_v210_kernel that of pack_v210_kernel (kernel_interleave.hip):
+// one launch over every row and frame of a slice, grid = row blocks x frames, a wave owns a row; they read float samples where those
+// read 16-bit integers and convert them -- lrintf(clamp(r, 0, 1023)), behind the scaled forms' multiply and add -- in front of the
+// packing.  The row functions are narrow_fields_rows.h and narrow_v210_rows.h; the exchange between the two lanes of a block pair is
+// v210_exchange.h's, 10-bit CODES behind the conversion.  Plain C++ and that one DPP builtin: no assembly, no LDS, no scratch.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "narrow_fields_rows.h"
 #include "narrow_rows.h"
+#include "narrow_v210_rows.h"
+#include "v210_exchange.h"
 
 namespace jinc {
 namespace {
@@ -68,7 +79,73 @@ int launch_by_kind(const NarrowArgs& a, int in_kind, int step, int dst_bytes, in
     return hipErrorInvalidValue;  // (no kernel for this shape: an error, never a silent skip)
 }
 
+// ---- 10:10:10:2 words (kernels.h NarrowFieldArgs; the row function: narrow_fields_rows.h) ----
+// Row blockIdx.x * 4 + wave of frame blockIdx.y.
+template <int KIND, bool Scaled>
+__global__ __launch_bounds__(256) void narrow_fields_kernel(const NarrowFieldArgs a) {
+    const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row < a.rows) narrow::narrow_fields_row<KIND, Scaled>(a, blockIdx.y, row, threadIdx.x & 63u);
+}
+
+// ---- v210 blocks (kernels.h NarrowV210Args; the row functions: narrow_v210_rows.h, v210_rows.h; the exchange: v210_exchange.h) ----
+// Row blockIdx.x * 4 + wave of frame blockIdx.y (the wave's number through a scalar register: the row's addresses are wave-uniform).
+template <int KIND, bool Scaled>
+__global__ __launch_bounds__(256) void narrow_v210_kernel(const NarrowV210Args a) {
+    const uint32_t row = blockIdx.x * 4 + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+    if (row >= a.rows) return;
+    const uint32_t lane = threadIdx.x & 63u, paired = v210::paired_blocks(a), blocks = v210::row_blocks(a);
+    const v210::RowOf r = v210::row_of(a, blockIdx.y, row);
+    for (uint32_t b = lane; b < paired; b += 64) {
+        v210::LaneState s;
+        uint32_t y[3];
+        v210::narrow_pair_begin<KIND, Scaled>(a, r, b, y, s);  // (codes, not samples, cross the lanes)
+        v210::pack_pair_end(a, r, b, y, s, v210::from_partner(s.send));
+    }
+    for (uint32_t b = paired + lane; b < blocks; b += 64) v210::narrow_tail<KIND, Scaled>(a, r, b);
+}
+
+template <int KIND, bool Scaled>
+int launch_fields(const NarrowFieldArgs& a, const dim3& grid, hipStream_t s) {
+    hipLaunchKernelGGL((narrow_fields_kernel<KIND, Scaled>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+template <int KIND, bool Scaled>
+int launch_v210(const NarrowV210Args& a, const dim3& grid, hipStream_t s) {
+    hipLaunchKernelGGL((narrow_v210_kernel<KIND, Scaled>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+int launch_narrow_fields(const NarrowFieldArgs& a, int in_kind, int nframes, void* stream, bool scaled) {
+    if (in_kind != 0 && in_kind != kSampleHalf && in_kind != kSampleBFloat16) return hipErrorInvalidValue;  // (never a silent skip)
+    if (nframes <= 0 || a.rows == 0 || a.width == 0) return hipSuccess;
+    if ((a.unit != 16 && a.unit != 4) || a.vec_pixels > a.width || a.vec_pixels % 8u) return hipErrorInvalidValue;  // (a word is the smallest access)
+    for (int c = 0; c < 3; ++c)
+        if (a.offset[c] > 22u || !a.plane[c]) return hipErrorInvalidValue;
+    if (!a.packed) return hipErrorInvalidValue;
+    const dim3 grid((a.rows + 3) / 4, static_cast<uint32_t>(nframes));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (in_kind) {
+        case 0: return scaled ? launch_fields<0, true>(a, grid, s) : launch_fields<0, false>(a, grid, s);
+        case kSampleHalf: return scaled ? launch_fields<kSampleHalf, true>(a, grid, s) : launch_fields<kSampleHalf, false>(a, grid, s);
+        default: return scaled ? launch_fields<kSampleBFloat16, true>(a, grid, s) : launch_fields<kSampleBFloat16, false>(a, grid, s);
+    }
+}
+
+int launch_narrow_v210(const NarrowV210Args& a, int in_kind, int nframes, void* stream, bool scaled) {
+    if (in_kind != 0 && in_kind != kSampleHalf && in_kind != kSampleBFloat16) return hipErrorInvalidValue;  // (never a silent skip)
+    if (nframes <= 0 || a.rows == 0 || a.width == 0) return hipSuccess;
+    if ((a.unit != 16 && a.unit != 4) || a.whole_blocks != a.width / 6 || (a.width & 1u)) return hipErrorInvalidValue;
+    if (!a.blocks || !a.plane[0] || !a.plane[1] || !a.plane[2]) return hipErrorInvalidValue;
+    const dim3 grid((a.rows + 3) / 4, static_cast<uint32_t>(nframes));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (in_kind) {
+        case 0: return scaled ? launch_v210<0, true>(a, grid, s) : launch_v210<0, false>(a, grid, s);
+        case kSampleHalf: return scaled ? launch_v210<kSampleHalf, true>(a, grid, s) : launch_v210<kSampleHalf, false>(a, grid, s);
+        default: return scaled ? launch_v210<kSampleBFloat16, true>(a, grid, s) : launch_v210<kSampleBFloat16, false>(a, grid, s);
+    }
+}
 
 int launch_narrow_samples(const NarrowArgs& a, int in_kind, int step, int dst_bytes, int nframes, void* stream, bool scaled) {
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -633,6 +633,23 @@ struct NarrowArgs {
 // scaled (jinc_filter_process_device_narrowed_scaled): the stored sample is
 // lrintf(clamp(fl32(fl32(result * scale[c]) + offset[c]), 0, peak)) << shift[c] -- two fp32 roundings, never an FMA.
 int launch_narrow_samples(const NarrowArgs& a, int in_kind, int step, int dst_bytes, int nframes, void* stream, bool scaled = false);
+// The three dense planes of an fp32 / binary16 / bfloat16 filter -> 10:10:10:2 words / v210 blocks (kernel_narrow.hip,
+// narrow_fields_rows.h, narrow_v210_rows.h; jinc_filter_process_device_narrowed_packed10 / _v210).  The records are FieldArgs and
+// V210Args with the scaled calls' pair per plane behind them; the plane side is READ only, with samples of in_bytes (4: fp32; 2:
+// binary16 or bfloat16) at plane[c] + n * frame stride + y * pitch + x * in_bytes (pitches and frame strides stay in bytes), and the
+// word / block side is written only: field c of a word or block holds lrintf(clamp(result, 0, 1023)) -- or, in the scaled forms,
+// lrintf(clamp(fl32(fl32(result * value_scale[c]) + value_offset[c]), 0, 1023)): two fp32 roundings, never an FMA.  Words are stored
+// whole with `fill` in the bits outside the fields; blocks are stored whole with zeros in bits 30 - 31 and in the fields of a partial
+// last block beyond `width`.
+struct NarrowFieldArgs : FieldArgs {
+    float value_scale[3] = {1.f, 1.f, 1.f}, value_offset[3] = {0.f, 0.f, 0.f};  // read by the scaled forms only
+};
+struct NarrowV210Args : V210Args {
+    float value_scale[3] = {1.f, 1.f, 1.f}, value_offset[3] = {0.f, 0.f, 0.f};  // read by the scaled forms only
+};
+// One launch over every row and frame of `a`: in_kind 0 (fp32), kSampleHalf or kSampleBFloat16.
+int launch_narrow_fields(const NarrowFieldArgs& a, int in_kind, int nframes, void* stream, bool scaled = false);
+int launch_narrow_v210(const NarrowV210Args& a, int in_kind, int nframes, void* stream, bool scaled = false);
 
 // Measurement hook (kernel_probe.hip): `samplers` single-lane workgroups stamp the shader clock counter and the 100 MHz
 // real-time counter until *stop_flag (device memory) becomes non-zero or max_seconds pass; out[2 k] = shader ticks,

@@ -459,7 +459,7 @@ JINC_API int jinc_filter_process_device_widened(jinc_filter *f, const void *cons
  * 1080p -> 4K from planar fp32 into NV12: 3840 x 4 = 15 360 and 1920 x 4 = 7680 bytes per row are multiples of 256 already, so a
  * frame needs 15 360 x 2160 + 2 x 7680 x 1080 = 49 766 400 bytes and the 1 GiB default holds floor(1 073 741 824 / 49 766 400) = 21
  * frames (a call of 128 runs as 6 x 21 + 2); from binary16 or bfloat16 half of that, 24 883 200 bytes, 43 frames (43 + 43 + 42).
- * 10:10:10:2 words and v210 blocks are no destinations of this call. */
+ * 10:10:10:2 words and v210 blocks are destinations of jinc_filter_process_device_narrowed_packed10 / _narrowed_v210 below. */
 JINC_API int jinc_filter_process_device_narrowed(jinc_filter *f, const void *const src[4], const int src_pitch[4],
                                                  const int src_sample_step[4], const size_t src_frame_stride[4], void *const dst[4],
                                                  const int dst_pitch[4], const int dst_sample_step[4], const int dst_sample_shift[4],
@@ -579,6 +579,65 @@ JINC_API int jinc_filter_process_device_widened_packed10(jinc_filter *f, const v
 JINC_API int jinc_filter_process_device_widened_v210(jinc_filter *f, const void *src, int src_pitch, size_t src_frame_stride,
                                                      void *const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
                                                      const size_t dst_frame_stride[4], int nframes, void *hip_stream);
+
+/* The results of an fp32, binary16 or bfloat16 filter into 10:10:10:2 WORDS or v210 BLOCKS: the way back out of the float planes
+ * for the two 10-bit surfaces that no step and no shift describes -- a swap chain's or encoder's Y410 / R10G10B10A2 frame, a
+ * playout card's v210 frame -- with the optional scale and offset of the scaled calls built in, so that no clamp / round / pack
+ * pass of the caller's and no rounding to 10 bits in front of an integer filter is needed.
+ *   `f` is an fp32, binary16 (JINC_SAMPLE_FLOAT16) or bfloat16 (JINC_SAMPLE_BFLOAT16) filter with three components.  Words take a
+ *   filter with no sub-sampling (YUV444PS / PH, RGBPS / PH and their bfloat16 twins); blocks take one with sub_w 1 and sub_h 0
+ *   (YUV422PS / PH / bfloat16).  bfloat16 is accepted here, unlike in the widened word calls: the conversion to a code value is a
+ *   defined rounding, not a claim of exactness, exactly as in jinc_filter_process_device_narrowed.
+ *   The SOURCE is exactly the src side of jinc_filter_process_device_narrowed, which is the strided call's: planes of the filter's
+ *   own type with steps 1 .. 4 (NULL: all ones).  The source is never written.
+ *   The DESTINATION is ONE buffer, given as scalars and addressed exactly as the packed side of
+ *   jinc_filter_process_device_packed10 (pixel x of row y of frame n is the word at dst + n * dst_frame_stride + y * dst_pitch +
+ *   4 * x) or the v210 side of jinc_filter_process_device_v210 (a row is jinc_v210_row_bytes(out_width) bytes of 16-byte blocks;
+ *   the field table is above).  dst_frame_stride is read only for nframes > 1.
+ *   DEFINITION.  Let r_i be what jinc_filter_process_device stores on that filter for plane i (library order Y,U,V / G,B,R),
+ *   widened exactly to fp32 -- for binary16 / bfloat16 the already narrowed result, so such a call rounds twice, as the narrowed
+ *   call does.  t_i = r_i when both arrays are NULL, otherwise t_i = fl32(fl32(r_i * dst_scale[i]) + dst_offset[i]) (a NULL scale
+ *   array means 1.0, a NULL offset array 0.0): two fp32 roundings and never an FMA.  v_i = lrintf(clamp(t_i, 0, 1023)), round half
+ *   to even; a NaN, -inf and -0 become 0, +inf becomes 1023.
+ *   WORDS: the stored word is (v0 << o0) | (v1 << o1) | (v2 << o2) | (dst_fill & ~fields), o_i = dst_field_offset[i]
+ *   (jinc_packed10_layout gives offsets and the opaque fill).  The word is stored whole; nothing outside the `width` words of a row
+ *   is stored to.
+ *   BLOCKS: every block of the row is built in registers and stored whole, bits 30 - 31 zero, the fields of a partial last block
+ *   beyond `width` zero.  Nothing outside the row's blocks is stored to: the conventional 128-byte padding keeps its bytes.
+ *   The destination is never read.
+ *   CONSEQUENCES.  (a) On an fp32 filter whose planes hold integers in 0 .. 1023, with no scale and no offset, the buffer equals what
+ *   jinc_filter_process_device_packed10 on YUV444P10 / RGBP10, or jinc_filter_process_device_v210 on YUV422P10, stores for the same
+ *   values with the same offsets and fill, bit for bit.  (b) For every filter type the field values equal what
+ *   jinc_filter_process_device_narrowed (or _narrowed_scaled when arrays are given) stores with dst_bits 10, steps 1 and shifts 0
+ *   into planar words.
+ * JINC_ERR_INVALID_ARG, each with a message of its own, before the null checks of the plane arrays, before the device check and
+ * before anything is queued: an integer filter; a float filter of another shape (four components, a single plane, the wrong
+ * sub-sampling); an offset outside 0 .. 22; two fields that overlap; a source step outside 1 .. 4; a destination base, a destination
+ * pitch or (with nframes > 1) a destination frame stride that is no multiple of 4; a destination pitch below 4 * width (words) or
+ * jinc_v210_row_bytes(width) (blocks); a scale that is NaN, infinite or zero and an offset that is NaN or infinite (the message
+ * names the plane).  Then null arguments, nframes and frame strides as for jinc_filter_process_device_shifted.  Base, pitch and
+ * frame stride that are all multiples of 16 get 16-byte stores, others dwords.
+ * The three destination planes take dense stand-ins of the filter's own type (the scratch of the strided call: same knob
+ * strided_scratch_bytes, same slicing of long calls, same ordering between calls, so these calls may alternate with strided,
+ * shifted, packed10, v210, widened and narrowed ones on one filter), rows padded to 256 bytes; a source plane takes one only where
+ * its step is not 1.  jinc_debug_last_strided counts the pass as one merge launch per slice.  1080p -> 4K from a planar source
+ * (4K rows of 15 360, 7680 and 3840 bytes are multiples of 256 already; every count is below the 128-frame rounding of long
+ * slices, so none is rounded):
+ *     Y410 from fp32              3 x 15 360 x 2160 = 99 532 800 bytes        floor(1 073 741 824 / 99 532 800) = 10 frames (128 = 12 x 10 + 8)
+ *     Y410 from a 16-bit type     3 x 7680 x 2160 = 49 766 400 bytes          21 frames (6 x 21 + 2)
+ *     v210 from fp32              (15 360 + 2 x 7680) x 2160 = 66 355 200     16 frames (8 x 16)
+ *     v210 from a 16-bit type     (7680 + 2 x 3840) x 2160 = 33 177 600       32 frames (4 x 32)
+ * Not covered: host-plane surfaces and the plugin shells, the 2-bit alpha as a resampled plane (it comes from dst_fill),
+ * four-component filters, colour conversion and dithering. */
+JINC_API int jinc_filter_process_device_narrowed_packed10(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                          const int src_sample_step[4], const size_t src_frame_stride[4], void *dst,
+                                                          int dst_pitch, const int dst_field_offset[3], unsigned dst_fill,
+                                                          const float dst_scale[3], const float dst_offset[3],
+                                                          size_t dst_frame_stride, int nframes, void *hip_stream);
+JINC_API int jinc_filter_process_device_narrowed_v210(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                      const int src_sample_step[4], const size_t src_frame_stride[4], void *dst,
+                                                      int dst_pitch, const float dst_scale[3], const float dst_offset[3],
+                                                      size_t dst_frame_stride, int nframes, void *hip_stream);
 
 /* The field offsets of a named 10:10:10:2 word in the library's plane order, and the fill that sets every spare bit (an opaque
  * pixel); opaque_fill may be NULL.  Needs no device.  Names match without regard to case; an unknown one is

@@ -248,10 +248,11 @@ JINC_API int jinc_debug_last_strided(int *split_launches, int *merge_launches, i
  * destination side's, each side in the order of its groups' first planes (a narrowed call: the source's split groups, then the
  * narrowing groups; a widened call: the widening groups or the field / block pass, then the destination's merge groups).
  * direction: 0 widen_samples_kernel, 1 narrow_samples_kernel, 2 split_samples_kernel, 3 merge_samples_kernel, 4 unpack_fields,
- * 5 pack_fields, 6 widen_fields, 7 unpack_v210, 8 pack_v210, 9 widen_v210.  n: samples per pixel on the caller's side (the step;
+ * 5 pack_fields, 6 widen_fields, 7 unpack_v210, 8 pack_v210, 9 widen_v210, 10 narrow_fields, 11 narrow_v210 (the passes of
+ * jinc_filter_process_device_narrowed_packed10 / _narrowed_v210: unit, vec_pixels, width and rows as for 5 / 8).  n: samples per pixel on the caller's side (the step;
  * 3 for the field and block passes).  members: planes of the call in the group.  sample_bytes: of the integer side (1 or 2) for
  * directions 0 and 1, else the filter's component size.  sample_type: the filter's JINC_SAMPLE_*.  scaled: 1 when a scale or an
- * offset array was given (directions 0 and 1 only).  unit: the widest access the caller's side allows (16, 4; 0: sample-sized accesses
+ * offset array was given (directions 0, 1, 10 and 11 only).  unit: the widest access the caller's side allows (16, 4; 0: sample-sized accesses
  * only).  vec_pixels: the leading pixels of every row that move by such accesses -- 16 / sample_bytes per lane and step in the
  * group passes, 8 in the field passes, and for the v210 passes 6 x the blocks that move in pairs; the rest of the row (all of it
  * when vec_pixels is 0) moves sample by sample, word by word or block by block.  width, rows: of the group's planes (v210: of the
@@ -302,6 +303,18 @@ JINC_API int jinc_debug_narrow(const void *in, int in_kind, void *out, int n, in
  * lrintf(clamp(fl32(fl32(value * scale) + offset), 0, (1 << dst_bits) - 1)) << shift.  scale and offset finite, scale not zero. */
 JINC_API int jinc_debug_narrow_scaled(const void *in, int in_kind, void *out, int n, int dst_bits, int shift, float scale, float offset,
                                       int device);
+/* ... the narrowing passes of jinc_filter_process_device_narrowed_packed10 / _narrowed_v210 themselves: narrow_fields_kernel on ONE
+ * dense row of `n` caller-given values per plane (in[0 .. 2], of in_kind as above), out_words receives n words
+ * (v0 << field_offset[0]) | (v1 << field_offset[1]) | (v2 << field_offset[2]) | (fill & ~fields) with
+ * v = lrintf(clamp(fl32(fl32(value * scale[c]) + offset[c]), 0, 1023)) -- scale / offset: three floats each, finite, scale not
+ * zero; a NULL array means 1.0 / 0.0 and both NULL the unscaled form; and narrow_v210_kernel on ONE dense row of `width` (even)
+ * luma values in in[0] and width / 2 chroma values in each of in[1] and in[2]: out_blocks receives the row's
+ * jinc_v210_row_bytes(width) bytes.  Whole lanes of 8 pixels / pairs of blocks through the vector paths, the rest word by word /
+ * sample by sample. */
+JINC_API int jinc_debug_narrow_fields(const void *const in[3], int in_kind, uint32_t *out_words, int n, const int field_offset[3],
+                                      unsigned fill, const float *scale, const float *offset, int device);
+JINC_API int jinc_debug_narrow_v210(const void *const in[3], int in_kind, void *out_blocks, int width, const float *scale,
+                                    const float *offset, int device);
 /* ... and the scaled form of the widening pass (jinc_filter_process_device_widened_scaled): widen_samples_kernel with one sample
  * per pixel on ONE dense row of `n` integer samples (bytes for src_bits 8, 16-bit words for 9 .. 16; shift in
  * 0 .. 8 * bytes - src_bits).  out receives n samples fl32(fl32(float((raw >> shift) & mask) * scale) + offset) of out_kind:
