@@ -101,7 +101,9 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_process_device_widened_scaled", "jinc_filter_process_device_narrowed_scaled", "jinc_code_range",
            "jinc_debug_widen_scaled", "jinc_debug_narrow_scaled",
            "jinc_filter_process_device_narrowed_packed10", "jinc_filter_process_device_narrowed_v210",
-           "jinc_debug_narrow_fields", "jinc_debug_narrow_v210"]
+           "jinc_debug_narrow_fields", "jinc_debug_narrow_v210",
+           "jinc_filter_process_device_widened_packed10_scaled", "jinc_filter_process_device_widened_v210_scaled",
+           "jinc_debug_widen_fields", "jinc_debug_widen_v210"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -198,6 +200,10 @@ def lib():
         L.jinc_debug_narrow_fields.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_int]
         L.jinc_debug_narrow_v210.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.jinc_debug_widen_scaled.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.jinc_filter_process_device_widened_packed10_scaled.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+        L.jinc_filter_process_device_widened_v210_scaled.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+        L.jinc_debug_widen_fields.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.jinc_debug_widen_v210.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         L.jinc_filter_set_profiling.argtypes = [C.c_void_p, C.c_int]
         L.jinc_filter_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int),
                                                C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -634,6 +640,40 @@ def debug_widen_scaled(raw: np.ndarray, src_bits: int, shift: int, scale: float,
     if rc != 0:
         raise JincError(rc, lib().jinc_last_error().decode())
     return out.view(np.float16) if out_kind == SAMPLE_FLOAT16 else out
+
+
+def _widen_hook_out(n_luma: int, n_chroma: int, out_kind: int):
+    dtype = np.float32 if out_kind == SAMPLE_DEFAULT else np.uint16
+    return [np.zeros(n_luma, dtype=dtype), np.zeros(n_chroma, dtype=dtype), np.zeros(n_chroma, dtype=dtype)]
+
+
+def debug_widen_fields(words: np.ndarray, offsets, scale=None, offset=None, out_kind: int = 0, device: int = 0):
+    """The pass of process_device_widened_packed10(_scaled) applied to one row of 32-bit words on the device (test hook): returns the
+    three planes fl32(fl32(float((word >> offsets[c]) & 1023) * scale[c]) + offset[c]) as float32 (out_kind SAMPLE_DEFAULT), float16
+    (SAMPLE_FLOAT16) or uint16 bfloat16 bit patterns (SAMPLE_BFLOAT16), the 16-bit types rounded to nearest even.  scale / offset
+    are three floats each or None; both None runs the unscaled form (no bfloat16 there)."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    out = _widen_hook_out(words.size, words.size, out_kind)
+    rc = lib().jinc_debug_widen_fields(words.ctypes.data, words.size, (C.c_int * 3)(*[int(o) for o in offsets]), _three_floats(scale),
+                                       _three_floats(offset), int(out_kind), (C.c_void_p * 3)(*[p.ctypes.data for p in out]), device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return [p.view(np.float16) if out_kind == SAMPLE_FLOAT16 else p for p in out]
+
+
+def debug_widen_v210(blocks: np.ndarray, width: int, scale=None, offset=None, out_kind: int = 0, device: int = 0):
+    """The pass of process_device_widened_v210(_scaled) applied to one row of blocks (uint32 words, four per block,
+    4 * ceil(width / 6) of them; width even) on the device (test hook): returns `width` luma samples and width / 2 samples of Cb and
+    of Cr, kinds and pairs as for debug_widen_fields."""
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint32)
+    if width % 2 or blocks.size != 4 * ((width + 5) // 6):
+        raise ValueError("an even width and 4 * ceil(width / 6) words are needed")
+    out = _widen_hook_out(width, width // 2, out_kind)
+    rc = lib().jinc_debug_widen_v210(blocks.ctypes.data, int(width), _three_floats(scale), _three_floats(offset), int(out_kind),
+                                     (C.c_void_p * 3)(*[p.ctypes.data for p in out]), device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return [p.view(np.float16) if out_kind == SAMPLE_FLOAT16 else p for p in out]
 
 
 RANGE_FULL, RANGE_LIMITED = 0, 1          # jinc_code_range: range
@@ -1121,6 +1161,44 @@ class Filter:
         self._check(lib().jinc_filter_process_device_widened_v210(
             self._h, C.c_void_p(src_ptr), int(src_pitch), C.c_size_t(int(src_stride or 0)), arr(_P4, dst_ptrs), arr(_I4, dst_pitches),
             arr(_I4, dst_steps), arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
+
+    def process_device_widened_packed10_scaled(self, src_ptr: int, src_pitch: int, src_offsets, src_scales, src_offsets_add, src_stride: int,
+                                               dst_ptrs, dst_pitches, dst_steps, dst_strides, nframes: int, stream: int = 0) -> None:
+        """process_device_widened_packed10 with a scale and an offset per plane (jinc_filter_process_device_widened_packed10_scaled):
+        plane i holds fl32(fl32(float((word >> src_offsets[i]) & 1023) * src_scales[i]) + src_offsets_add[i]), rounded to nearest even
+        for half and bfloat16 filters -- bfloat16 filters are accepted here.  src_scales None means all 1.0, src_offsets_add None all
+        0.0; both None IS process_device_widened_packed10.  code_range(10, ...) gives the usual pairs."""
+        n = self.fmt.planes
+
+        def arr(kind, values, count=n):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(min(count, len(values))):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_widened_packed10_scaled(
+            self._h, C.c_void_p(src_ptr), int(src_pitch), arr(C.c_int * 3, src_offsets, 3), _three_floats(src_scales),
+            _three_floats(src_offsets_add), C.c_size_t(int(src_stride or 0)), arr(_P4, dst_ptrs), arr(_I4, dst_pitches), arr(_I4, dst_steps),
+            arr(_S4, dst_strides), int(nframes), C.c_void_p(stream)))
+
+    def process_device_widened_v210_scaled(self, src_ptr: int, src_pitch: int, src_scales, src_offsets_add, src_stride: int, dst_ptrs,
+                                           dst_pitches, dst_steps, dst_strides, nframes: int, stream: int = 0) -> None:
+        """process_device_widened_v210 with a scale and an offset per plane (jinc_filter_process_device_widened_v210_scaled; planes
+        Y, Cb, Cr): as process_device_widened_packed10_scaled, on 4:2:2 filters -- fp32, half and bfloat16."""
+        n = self.fmt.planes
+
+        def arr(kind, values):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(min(n, len(values))):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_widened_v210_scaled(
+            self._h, C.c_void_p(src_ptr), int(src_pitch), _three_floats(src_scales), _three_floats(src_offsets_add),
+            C.c_size_t(int(src_stride or 0)), arr(_P4, dst_ptrs), arr(_I4, dst_pitches), arr(_I4, dst_steps), arr(_S4, dst_strides),
+            int(nframes), C.c_void_p(stream)))
 
     def process_device_narrowed(self, src_ptrs, src_pitches, src_steps, src_strides, dst_ptrs, dst_pitches, dst_steps, dst_shifts,
                                 dst_bits: int, dst_strides, nframes: int, stream: int = 0) -> None:

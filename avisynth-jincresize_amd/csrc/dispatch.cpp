@@ -1432,7 +1432,7 @@ void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pit
         [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });
 }
 
-// ---- jinc_filter_process_device_widened_packed10 / _v210: Y410 / RGB10A2 words and v210 blocks into an fp32 / binary16 filter ----
+// ---- jinc_filter_process_device_widened_packed10 / _v210 (and their _scaled forms): Y410 / RGB10A2 words and v210 blocks into an fp32 / binary16 (scaled: bfloat16 too) filter ----
 // The source is ONE group of the filter's three planes, as the packed side of enqueue_packed10 or the v210 side of enqueue_v210, and
 // every source plane takes a stand-in of the FILTER's type: widen_fields_kernel / widen_v210_kernel (kernel_widen.hip) fill them
 // with float(field) -- ten bits, exact in fp32 and in binary16.  The destination side and its merge are enqueue_widened's, and
@@ -1459,8 +1459,12 @@ void widened_words_sides(const jinc_filter& f, void* const dst[4], const int dst
 }
 }  // namespace
 
+// src_scale / src_offset (jinc_filter_process_device_widened_packed10_scaled / _widened_v210_scaled; three floats in plane order, both
+// nullptr: the unscaled calls): the same stand-ins, the same launches, the same report -- the kernels' scaled forms store
+// fl32(fl32(float(field) * scale) + offset), rounded to nearest even into 16-bit planes, so bfloat16 filters come this way too.
 void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, const int* src_fields, size_t src_fs, void* const dst[4],
-                              const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream) {
+                              const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream,
+                              const float* src_scale, const float* src_offset) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
     t_last_groups.count = 0;
     Side in, out;
@@ -1471,19 +1475,23 @@ void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, co
     const int src_pitches[4] = {src_pitch, src_pitch, src_pitch, 0};
     const size_t src_strides[4] = {src_fs, src_fs, src_fs, 0};
     const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
+    const bool scaled = src_scale || src_offset;
     run_on_stand_ins(
         f, in, out, src_planes, src_pitches, src_strides, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
-            const jinc::FieldArgs a = field_args(in, src, src_pitch, src_strides, src_fields, 0u, scratch, k0, slice, nframes);
-            record_fields(f, kWidenFields, a, k0);
-            hip_check(static_cast<hipError_t>(jinc::launch_widen_fields(a, f.vi_in.component_size, n, stream)), "widen fields launch");
+            jinc::WidenFieldArgs a;
+            static_cast<jinc::FieldArgs&>(a) = field_args(in, src, src_pitch, src_strides, src_fields, 0u, scratch, k0, slice, nframes);
+            for (int c = 0; c < 3; ++c) a.value_scale[c] = src_scale ? src_scale[c] : 1.f, a.value_offset[c] = src_offset ? src_offset[c] : 0.f;
+            record_fields(f, kWidenFields, a, k0, scaled);
+            hip_check(static_cast<hipError_t>(jinc::launch_widen_fields(a, f.sample_kind(), n, stream, scaled)), "widen fields launch");
             return 1;
         },
         [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });
 }
 
 void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t src_fs, void* const dst[4], const int dst_pitch[4],
-                          const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream) {
+                          const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream, const float* src_scale,
+                          const float* src_offset) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
     t_last_groups.count = 0;
     Side in, out;
@@ -1493,12 +1501,15 @@ void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t
     const int src_pitches[4] = {src_pitch, src_pitch, src_pitch, 0};
     const size_t src_strides[4] = {src_fs, src_fs, src_fs, 0};
     const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
+    const bool scaled = src_scale || src_offset;
     run_on_stand_ins(
         f, in, out, src_planes, src_pitches, src_strides, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
-            const jinc::V210Args a = v210_args(in, src, src_pitch, src_strides, scratch, k0, slice, nframes);
-            record_v210(f, kWidenV210, a, k0);
-            hip_check(static_cast<hipError_t>(jinc::launch_widen_v210(a, f.vi_in.component_size, n, stream)), "widen v210 launch");
+            jinc::WidenV210Args a;
+            static_cast<jinc::V210Args&>(a) = v210_args(in, src, src_pitch, src_strides, scratch, k0, slice, nframes);
+            for (int c = 0; c < 3; ++c) a.value_scale[c] = src_scale ? src_scale[c] : 1.f, a.value_offset[c] = src_offset ? src_offset[c] : 0.f;
+            record_v210(f, kWidenV210, a, k0, scaled);
+            hip_check(static_cast<hipError_t>(jinc::launch_widen_v210(a, f.sample_kind(), n, stream, scaled)), "widen v210 launch");
             return 1;
         },
         [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });

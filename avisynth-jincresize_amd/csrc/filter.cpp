@@ -539,17 +539,19 @@ int jinc_code_range(int bits, int range, int plane_kind, float* to_float_scale, 
     return JINC_OK;
 }
 
-int jinc_filter_process_device_widened_packed10(jinc_filter* f, const void* src, int src_pitch, const int src_field_offset[3],
-                                                size_t src_frame_stride, void* const dst[4], const int dst_pitch[4],
-                                                const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
-                                                void* hip_stream) {
-    // the filter, the offsets, the destination steps and the source's base, pitch and frame stride first (they need no device),
-    // then the checks of jinc_filter_process_device_shifted in its order
+namespace {
+// jinc_filter_process_device_widened_packed10 and, with a scale or an offset array given, jinc_filter_process_device_widened_packed10_scaled.
+int process_device_widened_packed10(jinc_filter* f, const void* src, int src_pitch, const int src_field_offset[3], const float* src_scale,
+                                    const float* src_offset, size_t src_frame_stride, void* const dst[4], const int dst_pitch[4],
+                                    const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    // the filter, the offsets, the destination steps, the source's base, pitch and frame stride and the pairs first (they need no
+    // device), then the checks of jinc_filter_process_device_shifted in its order
+    const bool scaled = src_scale || src_offset;  // (a defined rounding, no claim of exactness: bfloat16 filters too)
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (!f->float_samples())
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words need an fp32 or binary16 filter; this filter has " +
                                               std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_packed10).");
-    if (f->bf16)
+    if (!scaled && f->bf16)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words do not go into a bfloat16 filter: 10-bit fields are not exact in "
                                           "bfloat16 (at most 8 bits); widen them into an fp32 or binary16 filter.");
     if (f->planecount != 3 || f->subsampled)
@@ -567,8 +569,9 @@ int jinc_filter_process_device_widened_packed10(jinc_filter* f, const void* src,
                                                       std::to_string(src_field_offset[i]) + " and " + std::to_string(src_field_offset[j]) + ").");
     int w = 0, h = 0;
     f->plane_dims(f->vi_in, 0, w, h);
-    const std::string refusal = refuse_widened_words(f, "packed 10-bit words", src, src_pitch, src_frame_stride, 4 * static_cast<size_t>(w),
-                                                     "4 * width", dst_sample_step, nframes);
+    std::string refusal = refuse_widened_words(f, "packed 10-bit words", src, src_pitch, src_frame_stride, 4 * static_cast<size_t>(w),
+                                               "4 * width", dst_sample_step, nframes);
+    if (refusal.empty()) refusal = refuse_scale_offset("packed 10-bit source", src_scale, src_offset, 3);
     if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
     if (!src || !src_field_offset || !dst || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
@@ -577,20 +580,40 @@ int jinc_filter_process_device_widened_packed10(jinc_filter* f, const void* src,
     return guarded([&] {
         hip_check(hipSetDevice(f->device), "hipSetDevice");
         enqueue_widened_packed10(*f, src, src_pitch, src_field_offset, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_frame_stride,
-                                 nframes, static_cast<hipStream_t>(hip_stream));
+                                 nframes, static_cast<hipStream_t>(hip_stream), src_scale, src_offset);
     });
 }
+}  // namespace
 
-int jinc_filter_process_device_widened_v210(jinc_filter* f, const void* src, int src_pitch, size_t src_frame_stride, void* const dst[4],
-                                            const int dst_pitch[4], const int dst_sample_step[4], const size_t dst_frame_stride[4],
-                                            int nframes, void* hip_stream) {
-    // the filter, the destination steps and the source's base, pitch and frame stride first (they need no device), then the checks
-    // of jinc_filter_process_device_shifted in its order
+int jinc_filter_process_device_widened_packed10(jinc_filter* f, const void* src, int src_pitch, const int src_field_offset[3],
+                                                size_t src_frame_stride, void* const dst[4], const int dst_pitch[4],
+                                                const int dst_sample_step[4], const size_t dst_frame_stride[4], int nframes,
+                                                void* hip_stream) {
+    return process_device_widened_packed10(f, src, src_pitch, src_field_offset, nullptr, nullptr, src_frame_stride, dst, dst_pitch,
+                                           dst_sample_step, dst_frame_stride, nframes, hip_stream);
+}
+
+int jinc_filter_process_device_widened_packed10_scaled(jinc_filter* f, const void* src, int src_pitch, const int src_field_offset[3],
+                                                       const float src_scale[3], const float src_offset[3], size_t src_frame_stride,
+                                                       void* const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
+                                                       const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    return process_device_widened_packed10(f, src, src_pitch, src_field_offset, src_scale, src_offset, src_frame_stride, dst, dst_pitch,
+                                           dst_sample_step, dst_frame_stride, nframes, hip_stream);
+}
+
+namespace {
+// jinc_filter_process_device_widened_v210 and, with a scale or an offset array given, jinc_filter_process_device_widened_v210_scaled.
+int process_device_widened_v210(jinc_filter* f, const void* src, int src_pitch, const float* src_scale, const float* src_offset,
+                                size_t src_frame_stride, void* const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
+                                const size_t dst_frame_stride[4], int nframes, void* hip_stream) {
+    // the filter, the destination steps, the source's base, pitch and frame stride and the pairs first (they need no device), then
+    // the checks of jinc_filter_process_device_shifted in its order
+    const bool scaled = src_scale || src_offset;  // (a defined rounding, no claim of exactness: bfloat16 filters too)
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (!f->float_samples())
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened v210 blocks need an fp32 or binary16 filter; this filter has " +
                                               std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_v210).");
-    if (f->bf16)
+    if (!scaled && f->bf16)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened v210 blocks do not go into a bfloat16 filter: 10-bit samples are not exact in bfloat16 "
                                           "(at most 8 bits); widen them into an fp32 or binary16 filter.");
     if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0)
@@ -599,8 +622,9 @@ int jinc_filter_process_device_widened_v210(jinc_filter* f, const void* src, int
                                               std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
     int w = 0, h = 0;
     f->plane_dims(f->vi_in, 0, w, h);
-    const std::string refusal = refuse_widened_words(f, "v210 blocks", src, src_pitch, src_frame_stride, v210_row_bytes(w),
-                                                     "16 * ceil(width / 6)", dst_sample_step, nframes);
+    std::string refusal = refuse_widened_words(f, "v210 blocks", src, src_pitch, src_frame_stride, v210_row_bytes(w), "16 * ceil(width / 6)",
+                                               dst_sample_step, nframes);
+    if (refusal.empty()) refusal = refuse_scale_offset("v210 source", src_scale, src_offset, 3);
     if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
     if (!src || !dst || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
@@ -609,8 +633,24 @@ int jinc_filter_process_device_widened_v210(jinc_filter* f, const void* src, int
     return guarded([&] {
         hip_check(hipSetDevice(f->device), "hipSetDevice");
         enqueue_widened_v210(*f, src, src_pitch, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_frame_stride, nframes,
-                             static_cast<hipStream_t>(hip_stream));
+                             static_cast<hipStream_t>(hip_stream), src_scale, src_offset);
     });
+}
+}  // namespace
+
+int jinc_filter_process_device_widened_v210(jinc_filter* f, const void* src, int src_pitch, size_t src_frame_stride, void* const dst[4],
+                                            const int dst_pitch[4], const int dst_sample_step[4], const size_t dst_frame_stride[4],
+                                            int nframes, void* hip_stream) {
+    return process_device_widened_v210(f, src, src_pitch, nullptr, nullptr, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_frame_stride,
+                                       nframes, hip_stream);
+}
+
+int jinc_filter_process_device_widened_v210_scaled(jinc_filter* f, const void* src, int src_pitch, const float src_scale[3],
+                                                   const float src_offset[3], size_t src_frame_stride, void* const dst[4],
+                                                   const int dst_pitch[4], const int dst_sample_step[4], const size_t dst_frame_stride[4],
+                                                   int nframes, void* hip_stream) {
+    return process_device_widened_v210(f, src, src_pitch, src_scale, src_offset, src_frame_stride, dst, dst_pitch, dst_sample_step,
+                                       dst_frame_stride, nframes, hip_stream);
 }
 
 int jinc_filter_process_device_narrowed_packed10(jinc_filter* f, const void* const src[4], const int src_pitch[4],
@@ -1116,6 +1156,78 @@ int jinc_debug_widen_scaled(const void* in, int src_bits, int shift, float scale
         bounce_download(out, d_out, out_bytes * n, "download of the samples");
         (void)hipFree(d_in);
         (void)hipFree(d_out);
+    });
+}
+
+int jinc_debug_widen_fields(const uint32_t* words, int n, const int field_offset[3], const float* scale, const float* offset, int out_kind,
+                            void* const out[3], int device) {
+    const bool kind_ok = out_kind == JINC_SAMPLE_DEFAULT || out_kind == JINC_SAMPLE_FLOAT16 || out_kind == JINC_SAMPLE_BFLOAT16;
+    if (!words || !out || !out[0] || !out[1] || !out[2] || n < 0 || !kind_ok || !field_offset || !hook_pairs_ok(scale, offset))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    if (out_kind == JINC_SAMPLE_BFLOAT16 && !scale && !offset) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");  // (the unscaled form has no bfloat16 planes)
+    for (int i = 0; i < 3; ++i) {
+        if (field_offset[i] < 0 || field_offset[i] > 22) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+        for (int j = i + 1; j < 3; ++j)
+            if (field_offset[i] - field_offset[j] < 10 && field_offset[j] - field_offset[i] < 10) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    }
+    if (n == 0) return JINC_OK;
+    const size_t out_bytes = out_kind == JINC_SAMPLE_DEFAULT ? 4 : 2;
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        char *d_out[3] = {nullptr, nullptr, nullptr}, *d_in = nullptr;
+        jinc::WidenFieldArgs a;  // one dense row: whole lanes of 8 pixels by 16-byte accesses, the rest word by word
+        hip_check(hipMalloc(&d_in, 4 * static_cast<size_t>(n + 1)), "hipMalloc");
+        bounce_upload(d_in, words, 4 * static_cast<size_t>(n), "upload of the words");
+        for (int c = 0; c < 3; ++c) {
+            hip_check(hipMalloc(&d_out[c], out_bytes * (n + 1)), "hipMalloc");
+            a.plane[c] = d_out[c];
+            a.offset[c] = static_cast<uint32_t>(field_offset[c]);
+            a.value_scale[c] = scale ? scale[c] : 1.f, a.value_offset[c] = offset ? offset[c] : 0.f;
+        }
+        a.packed = d_in;
+        a.packed_pitch = static_cast<uint32_t>(4 * n), a.plane_pitch = static_cast<uint32_t>(out_bytes * n);
+        a.width = static_cast<uint32_t>(n), a.rows = 1, a.unit = 16, a.vec_pixels = a.width / 8u * 8u;
+        hip_check(static_cast<hipError_t>(jinc::launch_widen_fields(a, kernel_kind(out_kind), 1, nullptr, scale || offset)), "widen fields launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        for (int c = 0; c < 3; ++c) {
+            bounce_download(out[c], d_out[c], out_bytes * n, "download of the samples");
+            (void)hipFree(d_out[c]);
+        }
+        (void)hipFree(d_in);
+    });
+}
+
+int jinc_debug_widen_v210(const void* blocks, int width, const float* scale, const float* offset, int out_kind, void* const out[3], int device) {
+    const bool kind_ok = out_kind == JINC_SAMPLE_DEFAULT || out_kind == JINC_SAMPLE_FLOAT16 || out_kind == JINC_SAMPLE_BFLOAT16;
+    if (!blocks || !out || !out[0] || !out[1] || !out[2] || width < 0 || (width & 1) || !kind_ok || !hook_pairs_ok(scale, offset))
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    if (out_kind == JINC_SAMPLE_BFLOAT16 && !scale && !offset) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");  // (the unscaled form has no bfloat16 planes)
+    if (width == 0) return JINC_OK;
+    const size_t out_bytes = out_kind == JINC_SAMPLE_DEFAULT ? 4 : 2, row_bytes = v210_row_bytes(width);
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        char *d_out[3] = {nullptr, nullptr, nullptr}, *d_in = nullptr;
+        jinc::WidenV210Args a;  // one dense row: the blocks in pairs, the odd whole block and the partial one sample by sample
+        hip_check(hipMalloc(&d_in, row_bytes), "hipMalloc");
+        bounce_upload(d_in, blocks, row_bytes, "upload of the blocks");
+        for (int c = 0; c < 3; ++c) {
+            const size_t samples = static_cast<size_t>(c == 0 ? width : width / 2);
+            hip_check(hipMalloc(&d_out[c], out_bytes * (samples + 1)), "hipMalloc");
+            a.plane[c] = d_out[c];
+            a.value_scale[c] = scale ? scale[c] : 1.f, a.value_offset[c] = offset ? offset[c] : 0.f;
+        }
+        a.blocks = d_in;
+        a.block_pitch = static_cast<uint32_t>(row_bytes);
+        a.luma_pitch = static_cast<uint32_t>(out_bytes * width), a.chroma_pitch = static_cast<uint32_t>(out_bytes * (width / 2));
+        a.width = static_cast<uint32_t>(width), a.rows = 1, a.whole_blocks = a.width / 6, a.unit = 16;
+        hip_check(static_cast<hipError_t>(jinc::launch_widen_v210(a, kernel_kind(out_kind), 1, nullptr, scale || offset)), "widen v210 launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        for (int c = 0; c < 3; ++c) {
+            const size_t samples = static_cast<size_t>(c == 0 ? width : width / 2);
+            bounce_download(out[c], d_out[c], out_bytes * samples, "download of the samples");
+            (void)hipFree(d_out[c]);
+        }
+        (void)hipFree(d_in);
     });
 }
 

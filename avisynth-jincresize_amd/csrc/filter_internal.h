@@ -351,10 +351,15 @@ void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pit
 // order) or of v210 blocks: the three source planes are widened into dense stand-ins of the filter's sample type
 // (widen_fields_kernel / widen_v210_kernel); the destination side is enqueue_strided's.  Filter, offsets, destination steps and the
 // source's base, pitch and frame stride have been checked by filter.cpp.
+// src_scale / src_offset (three floats in plane order -- v210: Y, Cb, Cr -- either may be nullptr; both nullptr: the unscaled call):
+// the stand-ins hold fl32(fl32(float(field) * scale) + offset) rounded to the filter's type, bfloat16 included -- same stand-ins,
+// same launches, same report (jinc_filter_process_device_widened_packed10_scaled / _widened_v210_scaled).
 void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, const int* src_fields, size_t src_fs, void* const dst[4],
-                              const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream);
+                              const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream,
+                              const float* src_scale = nullptr, const float* src_offset = nullptr);
 void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t src_fs, void* const dst[4], const int dst_pitch[4],
-                          const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream);
+                          const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream, const float* src_scale = nullptr,
+                          const float* src_offset = nullptr);
 // ... enqueue on an fp32 / binary16 / bfloat16 filter whose results go into INTEGER samples of dst_bits bits (8: bytes; 9 .. 16:
 // 16-bit words) at `shift` in their container: every destination plane takes a dense stand-in of the filter's sample type and
 // narrow_samples_kernel stores lrintf(clamp(r, 0, peak)) << shift from it; the source side is enqueue_strided's (no shifts).

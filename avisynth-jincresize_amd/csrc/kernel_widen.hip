@@ -22,7 +22,13 @@
 // frame of a slice, grid = row blocks x frames, a wave owns a row; they store the field values converted instead of 16-bit
 // integers.  The row functions are widen_fields_rows.h and widen_v210_rows.h; the exchange between the two lanes of a block pair
 // is v210_exchange.h's, RAW samples in front of the conversion.  Plain C++ and that one DPP builtin: no assembly, no scratch.
+// Their scaled forms (jinc_filter_process_device_widened_packed10_scaled / _widened_v210_scaled; kernels.h WidenFieldArgs /
+// WidenV210Args) are the same kernels with widen_rows.h's scaled_value behind the conversion and its round-to-nearest-even pair
+// conversions for 16-bit planes, bfloat16 among them; the pairs of the three planes are kernel arguments in scalar registers, and
+// the v210 lane that stores a pair's chroma row selects between plane 1's and plane 2's pair by the parity of its block.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "kernels.h"
 #include "v210_exchange.h"
@@ -62,54 +68,74 @@ int launch_by_step(const WidenArgs& a, int step, int nframes, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-// ---- 10:10:10:2 words (kernels.h FieldArgs; the row function: widen_fields_rows.h) ----
-// Row blockIdx.x * 4 + wave of frame blockIdx.y.
-template <int OB>
-__global__ __launch_bounds__(256) void widen_fields_kernel(const FieldArgs a) {
+// ---- 10:10:10:2 words (kernels.h FieldArgs / WidenFieldArgs; the row function: widen_fields_rows.h) ----
+// Row blockIdx.x * 4 + wave of frame blockIdx.y.  The unscaled forms take FieldArgs as it is; the scaled forms (KIND: the plane's
+// type, bfloat16 among them) take the record with the three pairs behind it.
+template <int OB, int KIND, bool Scaled>
+__global__ __launch_bounds__(256) void widen_fields_kernel(const std::conditional_t<Scaled, WidenFieldArgs, FieldArgs> a) {
     const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row < a.rows) widen::widen_fields_row<OB>(a, blockIdx.y, row, threadIdx.x & 63u);
+    if (row < a.rows) widen::widen_fields_row<OB, KIND, Scaled>(a, blockIdx.y, row, threadIdx.x & 63u);
 }
 
-// ---- v210 blocks (kernels.h V210Args; the row functions: widen_v210_rows.h) ----
+// ---- v210 blocks (kernels.h V210Args / WidenV210Args; the row functions: widen_v210_rows.h) ----
 // Row blockIdx.x * 4 + wave of frame blockIdx.y (the wave's number through a scalar register: the row's addresses are wave-uniform).
-template <int OB>
-__global__ __launch_bounds__(256) void widen_v210_kernel(const V210Args a) {
+template <int OB, int KIND, bool Scaled>
+__global__ __launch_bounds__(256) void widen_v210_kernel(const std::conditional_t<Scaled, WidenV210Args, V210Args> a) {
     const uint32_t row = blockIdx.x * 4 + static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
     if (row >= a.rows) return;
     const uint32_t lane = threadIdx.x & 63u, paired = v210::paired_blocks(a), blocks = v210::row_blocks(a);
     const v210::RowOf r = v210::row_of(a, blockIdx.y, row);
     for (uint32_t b = lane; b < paired; b += 64) {
         v210::LaneState s;
-        v210::widen_pair_begin<OB>(a, r, b, s);
-        v210::widen_pair_end<OB>(a, r, b, s, v210::from_partner(s.send));
+        v210::widen_pair_begin<OB, KIND, Scaled>(a, r, b, s);
+        v210::widen_pair_end<OB, KIND, Scaled>(a, r, b, s, v210::from_partner(s.send));  // (RAW samples cross the lanes; scale and convert behind)
     }
-    for (uint32_t b = paired + lane; b < blocks; b += 64) v210::widen_tail<OB>(a, r, b);
+    for (uint32_t b = paired + lane; b < blocks; b += 64) v210::widen_tail<OB, KIND, Scaled>(a, r, b);
+}
+
+template <int OB, int KIND, bool Scaled>
+int launch_fields(const WidenFieldArgs& a, const dim3& grid, hipStream_t s) {
+    if constexpr (Scaled) hipLaunchKernelGGL((widen_fields_kernel<OB, KIND, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((widen_fields_kernel<OB, KIND, false>), grid, dim3(256), 0, s, static_cast<const FieldArgs&>(a));
+    return hipGetLastError();
+}
+template <int OB, int KIND, bool Scaled>
+int launch_v210(const WidenV210Args& a, const dim3& grid, hipStream_t s) {
+    if constexpr (Scaled) hipLaunchKernelGGL((widen_v210_kernel<OB, KIND, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((widen_v210_kernel<OB, KIND, false>), grid, dim3(256), 0, s, static_cast<const V210Args&>(a));
+    return hipGetLastError();
 }
 
 }  // namespace
 
-int launch_widen_fields(const FieldArgs& a, int out_bytes, int nframes, void* stream) {
+int launch_widen_fields(const WidenFieldArgs& a, int out_kind, int nframes, void* stream, bool scaled) {
+    if (out_kind != 0 && out_kind != kSampleHalf && out_kind != kSampleBFloat16) return hipErrorInvalidValue;  // (never a silent skip)
+    if (out_kind == kSampleBFloat16 && !scaled) return hipErrorInvalidValue;  // (ten bits are not exact in bfloat16)
     if (nframes <= 0 || a.rows == 0 || a.width == 0) return hipSuccess;
     if ((a.unit != 16 && a.unit != 4) || a.vec_pixels > a.width || a.vec_pixels % 8u) return hipErrorInvalidValue;  // (a word is the smallest access)
     for (int c = 0; c < 3; ++c)
         if (a.offset[c] > 22u) return hipErrorInvalidValue;
     const dim3 grid((a.rows + 3) / 4, static_cast<uint32_t>(nframes));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (out_bytes == 4) hipLaunchKernelGGL(widen_fields_kernel<4>, grid, dim3(256), 0, s, a);
-    else if (out_bytes == 2) hipLaunchKernelGGL(widen_fields_kernel<2>, grid, dim3(256), 0, s, a);
-    else return hipErrorInvalidValue;  // (no kernel for this shape: an error, never a silent skip)
-    return hipGetLastError();
+    switch (out_kind) {
+        case 0: return scaled ? launch_fields<4, 0, true>(a, grid, s) : launch_fields<4, 0, false>(a, grid, s);
+        case kSampleHalf: return scaled ? launch_fields<2, kSampleHalf, true>(a, grid, s) : launch_fields<2, 0, false>(a, grid, s);
+        default: return launch_fields<2, kSampleBFloat16, true>(a, grid, s);
+    }
 }
 
-int launch_widen_v210(const V210Args& a, int out_bytes, int nframes, void* stream) {
+int launch_widen_v210(const WidenV210Args& a, int out_kind, int nframes, void* stream, bool scaled) {
+    if (out_kind != 0 && out_kind != kSampleHalf && out_kind != kSampleBFloat16) return hipErrorInvalidValue;  // (never a silent skip)
+    if (out_kind == kSampleBFloat16 && !scaled) return hipErrorInvalidValue;  // (ten bits are not exact in bfloat16)
     if (nframes <= 0 || a.rows == 0 || a.width == 0) return hipSuccess;
     if ((a.unit != 16 && a.unit != 4) || a.whole_blocks != a.width / 6 || (a.width & 1u)) return hipErrorInvalidValue;
     const dim3 grid((a.rows + 3) / 4, static_cast<uint32_t>(nframes));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (out_bytes == 4) hipLaunchKernelGGL(widen_v210_kernel<4>, grid, dim3(256), 0, s, a);
-    else if (out_bytes == 2) hipLaunchKernelGGL(widen_v210_kernel<2>, grid, dim3(256), 0, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    switch (out_kind) {
+        case 0: return scaled ? launch_v210<4, 0, true>(a, grid, s) : launch_v210<4, 0, false>(a, grid, s);
+        case kSampleHalf: return scaled ? launch_v210<2, kSampleHalf, true>(a, grid, s) : launch_v210<2, 0, false>(a, grid, s);
+        default: return launch_v210<2, kSampleBFloat16, true>(a, grid, s);
+    }
 }
 
 int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_bytes, int out_kind, int nframes, void* stream, bool scaled) {

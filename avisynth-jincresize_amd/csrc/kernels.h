@@ -602,8 +602,20 @@ int launch_widen_samples(const WidenArgs& a, int src_bytes, int step, int out_by
 // with samples of out_bytes (4: fp32, 2: binary16) on the plane side: plane c holds float / binary16 of the 10-bit field value at
 // plane[c] + n * frame stride + y * pitch + x * out_bytes (pitches and frame strides stay in bytes).  The word / block side is read
 // only; `fill` is not read.  One launch over every row and frame of `a`.
-int launch_widen_fields(const FieldArgs& a, int out_bytes, int nframes, void* stream);
-int launch_widen_v210(const V210Args& a, int out_bytes, int nframes, void* stream);
+// The scaled forms (jinc_filter_process_device_widened_packed10_scaled / _widened_v210_scaled): the records carry one pair per plane
+// (library order; v210: Y, Cb, Cr) behind FieldArgs / V210Args, as NarrowFieldArgs / NarrowV210Args below do, and plane c holds
+// fl32(fl32(float(field) * value_scale[c]) + value_offset[c]) -- two fp32 roundings, never an FMA -- narrowed round-to-nearest-even
+// into 16-bit planes: a defined rounding, so bfloat16 planes are filled too.  The pairs are kernel arguments, the same in every lane.
+struct WidenFieldArgs : FieldArgs {
+    float value_scale[3] = {1.f, 1.f, 1.f}, value_offset[3] = {0.f, 0.f, 0.f};  // read by the scaled forms only
+};
+struct WidenV210Args : V210Args {
+    float value_scale[3] = {1.f, 1.f, 1.f}, value_offset[3] = {0.f, 0.f, 0.f};  // read by the scaled forms only
+};
+// out_kind 0 (fp32), kSampleHalf or kSampleBFloat16; bfloat16 with scaled only (ten bits are not exact in it): every other shape
+// is hipErrorInvalidValue, never a silent skip.
+int launch_widen_fields(const WidenFieldArgs& a, int out_kind, int nframes, void* stream, bool scaled = false);
+int launch_widen_v210(const WidenV210Args& a, int out_kind, int nframes, void* stream, bool scaled = false);
 
 // The dense planes of an fp32 / binary16 / bfloat16 filter -> INTEGER samples (kernel_narrow.hip, narrow_rows.h;
 // jinc_filter_process_device_narrowed): the mirror of WidenGroup.  A channel group as in InterleaveGroup, written only: `step`

@@ -580,6 +580,43 @@ JINC_API int jinc_filter_process_device_widened_v210(jinc_filter *f, const void 
                                                      void *const dst[4], const int dst_pitch[4], const int dst_sample_step[4],
                                                      const size_t dst_frame_stride[4], int nframes, void *hip_stream);
 
+/* The two calls above with a SCALE and an OFFSET per plane between the 10-bit code values and the float range, as
+ * jinc_filter_process_device_widened_scaled has them: a Y410 swap-chain frame or a v210 capture frame straight into float, half or
+ * bfloat16 planes in the range a network reads, with no pass of the caller's over three float planes per frame.
+ *   The argument lists are those of jinc_filter_process_device_widened_packed10 / _widened_v210 plus two arrays of THREE floats in
+ *   the library's plane order (Y,U,V / G,B,R; v210: Y, Cb, Cr).  A NULL scale array means all 1.0; a NULL offset array all 0.0.
+ *   DEFINITION.  Let v = (word >> src_field_offset[i]) & 1023 (words) or the 10-bit field of the block (v210).  The sample of
+ *   plane i is
+ *       s = fl32(fl32(float(v) * src_scale[i]) + src_offset[i]).
+ *   That is two fp32 roundings and never an FMA.  An fp32 filter holds s.  A binary16 filter holds s rounded to nearest even
+ *   (overflow to +-inf, subnormals kept).  A bfloat16 filter holds s rounded to nearest even by the rule its results are stored
+ *   with.  The call's result is exactly what jinc_filter_process_device computes on that filter for dense planes holding those
+ *   samples.
+ *   BOTH ARRAYS NULL.  The call IS the unscaled call: the same launches, the same jinc_debug_last_strided report, the same
+ *   refusals with the same texts -- bfloat16 filters included.
+ *   EITHER ARRAY NON-NULL.  fp32, binary16 AND bfloat16 filters of the right shape are accepted (words: three components, no
+ *   sub-sampling; blocks: 4:2:2), because the conversion is a defined rounding and not a claim of exactness.
+ *     Y410 limited range into YUV444PH in 0 .. 1: jinc_code_range(10, JINC_RANGE_LIMITED, JINC_PLANE_LUMA_OR_RGB, ...) gives
+ *     src_scale[0] / src_offset[0], JINC_PLANE_CHROMA those of planes 1 and 2; the to_code pairs are dst_scale / dst_offset of
+ *     jinc_filter_process_device_narrowed_packed10 / _narrowed_v210, the way back.
+ * JINC_ERR_INVALID_ARG: every refusal of the unscaled call stays, with its text, and comes first.  Then, before the null checks of
+ * the plane arrays, before the device check and before anything is queued: a scale that is NaN, infinite or zero and an offset that
+ * is NaN or infinite (the message names the plane).
+ * Stand-ins, slicing under strided_scratch_bytes, the order on the caller's stream and the jinc_debug_last_strided counts are those
+ * of the unscaled calls: the scaled form adds no pass and no launch, only one multiply and one add per sample in the widening
+ * kernel.  A bfloat16 filter's stand-ins have the binary16 sizes.
+ * Not covered: host-plane surfaces and the plugin shells, the 2-bit alpha, four-component filters, colour conversion. */
+JINC_API int jinc_filter_process_device_widened_packed10_scaled(jinc_filter *f, const void *src, int src_pitch,
+                                                                const int src_field_offset[3], const float src_scale[3],
+                                                                const float src_offset[3], size_t src_frame_stride,
+                                                                void *const dst[4], const int dst_pitch[4],
+                                                                const int dst_sample_step[4], const size_t dst_frame_stride[4],
+                                                                int nframes, void *hip_stream);
+JINC_API int jinc_filter_process_device_widened_v210_scaled(jinc_filter *f, const void *src, int src_pitch, const float src_scale[3],
+                                                            const float src_offset[3], size_t src_frame_stride, void *const dst[4],
+                                                            const int dst_pitch[4], const int dst_sample_step[4],
+                                                            const size_t dst_frame_stride[4], int nframes, void *hip_stream);
+
 /* The results of an fp32, binary16 or bfloat16 filter into 10:10:10:2 WORDS or v210 BLOCKS: the way back out of the float planes
  * for the two 10-bit surfaces that no step and no shift describes -- a swap chain's or encoder's Y410 / R10G10B10A2 frame, a
  * playout card's v210 frame -- with the optional scale and offset of the scaled calls built in, so that no clamp / round / pack

@@ -252,7 +252,8 @@ JINC_API int jinc_debug_last_strided(int *split_launches, int *merge_launches, i
  * jinc_filter_process_device_narrowed_packed10 / _narrowed_v210: unit, vec_pixels, width and rows as for 5 / 8).  n: samples per pixel on the caller's side (the step;
  * 3 for the field and block passes).  members: planes of the call in the group.  sample_bytes: of the integer side (1 or 2) for
  * directions 0 and 1, else the filter's component size.  sample_type: the filter's JINC_SAMPLE_*.  scaled: 1 when a scale or an
- * offset array was given (directions 0, 1, 10 and 11 only).  unit: the widest access the caller's side allows (16, 4; 0: sample-sized accesses
+ * offset array was given (directions 0, 1, 6, 9, 10 and 11 only; 6 and 9: jinc_filter_process_device_widened_packed10_scaled /
+ * _widened_v210_scaled).  unit: the widest access the caller's side allows (16, 4; 0: sample-sized accesses
  * only).  vec_pixels: the leading pixels of every row that move by such accesses -- 16 / sample_bytes per lane and step in the
  * group passes, 8 in the field passes, and for the v210 passes 6 x the blocks that move in pairs; the rest of the row (all of it
  * when vec_pixels is 0) moves sample by sample, word by word or block by block.  width, rows: of the group's planes (v210: of the
@@ -321,6 +322,18 @@ JINC_API int jinc_debug_narrow_v210(const void *const in[3], int in_kind, void *
  * JINC_SAMPLE_DEFAULT fp32, JINC_SAMPLE_FLOAT16 / JINC_SAMPLE_BFLOAT16 the 16-bit patterns rounded to nearest even. */
 JINC_API int jinc_debug_widen_scaled(const void *in, int src_bits, int shift, float scale, float offset, int out_kind, void *out, int n,
                                      int device);
+/* ... the widening passes of jinc_filter_process_device_widened_packed10(_scaled) / _widened_v210(_scaled) themselves, the
+ * counterparts of jinc_debug_narrow_fields / _narrow_v210: widen_fields_kernel on ONE row of `n` caller-given words, out[c] receives
+ * n samples fl32(fl32(float((word >> field_offset[c]) & 1023) * scale[c]) + offset[c]) of out_kind (JINC_SAMPLE_DEFAULT fp32,
+ * JINC_SAMPLE_FLOAT16 / JINC_SAMPLE_BFLOAT16 the 16-bit patterns rounded to nearest even) -- scale / offset: three floats each,
+ * finite, scale not zero; a NULL array means 1.0 / 0.0 and both NULL the unscaled form (float(field), exact; no bfloat16 there:
+ * bad argument); and widen_v210_kernel on ONE row of jinc_v210_row_bytes(width) bytes of blocks (width even): out[0] receives `width`
+ * luma samples, out[1] and out[2] width / 2 Cb and Cr samples.  Whole lanes of 8 pixels / pairs of blocks through the vector paths,
+ * the rest word by word / sample by sample. */
+JINC_API int jinc_debug_widen_fields(const uint32_t *words, int n, const int field_offset[3], const float *scale, const float *offset,
+                                     int out_kind, void *const out[3], int device);
+JINC_API int jinc_debug_widen_v210(const void *blocks, int width, const float *scale, const float *offset, int out_kind,
+                                   void *const out[3], int device);
 
 /* Test hook: 1 when the device's buffer range check covers the scalar offset of buffer loads (the premise of the
  * direct kernel's bounded segment fetches; probed once per device, the direct kernel is not used where it fails), 0 when
