@@ -16,6 +16,7 @@ The directory name contains a hyphen, so load it with ``importlib`` (see ``__gra
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import enum
 import os
 import subprocess
@@ -103,7 +104,9 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_process_device_narrowed_packed10", "jinc_filter_process_device_narrowed_v210",
            "jinc_debug_narrow_fields", "jinc_debug_narrow_v210",
            "jinc_filter_process_device_widened_packed10_scaled", "jinc_filter_process_device_widened_v210_scaled",
-           "jinc_debug_widen_fields", "jinc_debug_widen_v210"]
+           "jinc_debug_widen_fields", "jinc_debug_widen_v210",
+           "jinc_filter_create_out", "jinc_batch_create_out",
+           "jinc_filter_process_device_shifted_packed10", "jinc_filter_process_device_v210_packed10"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -127,6 +130,9 @@ def lib():
         L.jinc_filter_create_ex.restype = C.c_int
         L.jinc_filter_create_ex.argtypes = [C.POINTER(VideoInfo), C.POINTER(Args), C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                             C.c_char_p, C.c_size_t]
+        L.jinc_filter_create_out.restype = C.c_int
+        L.jinc_filter_create_out.argtypes = [C.POINTER(VideoInfo), C.POINTER(Args), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                             C.c_char_p, C.c_size_t]
         L.jinc_filter_free.restype = None
         L.jinc_filter_free.argtypes = [C.c_void_p]
         L.jinc_filter_output_info.argtypes = [C.c_void_p, C.POINTER(VideoInfo)]
@@ -222,6 +228,8 @@ def lib():
                                         C.c_char_p, C.c_size_t]
         L.jinc_batch_create_ex.argtypes = [C.POINTER(VideoInfo), C.POINTER(Args), C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+        L.jinc_batch_create_out.argtypes = [C.POINTER(VideoInfo), C.POINTER(Args), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         L.jinc_batch_devices.argtypes = [C.c_void_p]
         L.jinc_batch_device_of_frame.argtypes = [C.c_void_p, C.c_int]
         L.jinc_batch_process.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _I4, C.c_void_p, _I4]
@@ -787,6 +795,13 @@ class Clip:
         return self.source(n)
 
 
+def _out_format(fmt: "Format", out_sub) -> "Format":
+    """The format of a filter's output planes: `fmt` with the chroma sub-sampling of out_sub=(w, h) (None or -1s: fmt itself)."""
+    if out_sub is None or tuple(out_sub) == (-1, -1) or tuple(out_sub) == (fmt.sub_w, fmt.sub_h):
+        return fmt
+    return dataclasses.replace(fmt, name=f"{fmt.name}>sub{out_sub[0]}{out_sub[1]}", sub_w=int(out_sub[0]), sub_h=int(out_sub[1]))
+
+
 def _build_args(fmt, width, height, target_width, target_height, frame0_chroma_location, planar, cpu_flags, alias_taps, kw):
     """jinc_video_info + jinc_args of a JincResize() call (keyword names = the script arguments)."""
     vi = fmt.video_info(width, height)
@@ -835,15 +850,21 @@ class Batch:
     and `streams` frames in flight per device, no exchange between devices)."""
 
     def __init__(self, fmt: Format, width: int, height: int, target_width: int, target_height: int, *, ndevices: int = 0,
-                 streams: int = 2, register_host_buffers: bool = False, **kw):
+                 streams: int = 2, register_host_buffers: bool = False, out_sub: Optional[Tuple[int, int]] = None, **kw):
+        """out_sub=(w, h): the output's chroma sub-sampling (jinc_batch_create_out); None: the input's (jinc_batch_create_ex)."""
         self.fmt = fmt
         vi, a, self._keep = _build_args(fmt, width, height, target_width, target_height, -1, True, (True, True, True), None, kw)
         self._h = C.c_void_p()
         err = C.create_string_buffer(512)
-        rc = lib().jinc_batch_create_ex(C.byref(vi), C.byref(a), fmt.sample_type, int(ndevices), int(streams), int(register_host_buffers),
-                                        C.byref(self._h), err, len(err))
+        if out_sub is None:
+            rc = lib().jinc_batch_create_ex(C.byref(vi), C.byref(a), fmt.sample_type, int(ndevices), int(streams), int(register_host_buffers),
+                                            C.byref(self._h), err, len(err))
+        else:
+            rc = lib().jinc_batch_create_out(C.byref(vi), C.byref(a), fmt.sample_type, int(out_sub[0]), int(out_sub[1]), int(ndevices),
+                                             int(streams), int(register_host_buffers), C.byref(self._h), err, len(err))
         if rc != 0:
             raise JincError(rc, err.value.decode())
+        self.out_fmt = _out_format(fmt, out_sub)
         self.dst_w, self.dst_h = int(target_width), int(target_height)
 
     @property
@@ -873,7 +894,7 @@ class Batch:
         return int(lib().jinc_batch_device_of_frame(self._h, int(n)))
 
     def out_dims(self) -> List[Tuple[int, int]]:
-        return self.fmt.plane_dims(self.dst_w, self.dst_h)
+        return self.out_fmt.plane_dims(self.dst_w, self.dst_h)
 
     def process(self, frames: Sequence[Sequence[np.ndarray]], outs: Optional[Sequence[Sequence[np.ndarray]]] = None):
         """frames[n] = the planes of frame n (all with the same pitches); returns outs[n] = its output planes."""
@@ -913,17 +934,25 @@ class Filter:
 
     def __init__(self, fmt: Format, width: int, height: int, target_width: int, target_height: int, *,
                  device: int = 0, frame0_chroma_location: int = -1, planar: bool = True,
-                 cpu_flags: Tuple[bool, bool, bool] = (True, True, True), alias_taps: Optional[int] = None, **kw):
+                 cpu_flags: Tuple[bool, bool, bool] = (True, True, True), alias_taps: Optional[int] = None,
+                 out_sub: Optional[Tuple[int, int]] = None, **kw):
+        """out_sub=(w, h): the output's chroma sub-sampling (jinc_filter_create_out: 4:2:0 in, 4:4:4 out and the like); None: the
+        input's (jinc_filter_create_ex).  `out_fmt` is the format of the planes the filter writes."""
         self.fmt = fmt
         vi, a, self._keep = _build_args(fmt, width, height, target_width, target_height, frame0_chroma_location, planar,
                                         cpu_flags, alias_taps, kw)
         self._h = C.c_void_p()
         err = C.create_string_buffer(512)
-        rc = lib().jinc_filter_create_ex(C.byref(vi), C.byref(a), fmt.sample_type, int(device), C.byref(self._h), err, len(err))
+        if out_sub is None:
+            rc = lib().jinc_filter_create_ex(C.byref(vi), C.byref(a), fmt.sample_type, int(device), C.byref(self._h), err, len(err))
+        else:
+            rc = lib().jinc_filter_create_out(C.byref(vi), C.byref(a), fmt.sample_type, int(out_sub[0]), int(out_sub[1]), int(device),
+                                              C.byref(self._h), err, len(err))
         if rc != 0:
             raise JincError(rc, err.value.decode())
         out = VideoInfo()
         lib().jinc_filter_output_info(self._h, C.byref(out))
+        self.out_fmt = _out_format(fmt, (out.sub_w, out.sub_h) if out_sub is not None else None)
         self.src_w, self.src_h = width, height
         self.dst_w, self.dst_h = out.width, out.height
         self.device = device
@@ -950,7 +979,7 @@ class Filter:
         self._check(lib().jinc_filter_set_chroma_location_mode(self._h, int(mode)))
 
     def out_dims(self) -> List[Tuple[int, int]]:
-        return self.fmt.plane_dims(self.dst_w, self.dst_h)
+        return self.out_fmt.plane_dims(self.dst_w, self.dst_h)
 
     def set_kernel_mode(self, mode: int) -> None:
         self._check(lib().jinc_filter_set_kernel_mode(self._h, mode))
@@ -1303,6 +1332,33 @@ class Filter:
             self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_S4, src_strides), C.c_void_p(dst_ptr),
             int(dst_pitch), arr(C.c_float * 3, dst_scales, 3), arr(C.c_float * 3, dst_offsets_add, 3), C.c_size_t(int(dst_stride or 0)),
             int(nframes), C.c_void_p(stream)))
+
+    def process_device_shifted_packed10(self, src_ptrs, src_pitches, src_steps, src_shifts, src_strides, dst_ptr: int, dst_pitch: int,
+                                        dst_offsets, dst_fill: int, dst_stride: int, nframes: int, stream: int = 0) -> None:
+        """P010-style source planes (process_device_shifted's source side) into ONE buffer of 10:10:10:2 words (process_device_packed10's
+        destination side) on a 10-bit integer filter whose output is 4:4:4 (jinc_filter_process_device_shifted_packed10)."""
+        n = self.fmt.planes
+
+        def arr(kind, values, count=n):
+            if values is None:
+                return None
+            a = kind()
+            for i in range(min(count, len(values))):
+                a[i] = values[i]
+            return a
+        self._check(lib().jinc_filter_process_device_shifted_packed10(
+            self._h, arr(_P4, src_ptrs), arr(_I4, src_pitches), arr(_I4, src_steps), arr(_I4, src_shifts), arr(_S4, src_strides),
+            C.c_void_p(dst_ptr), int(dst_pitch), arr(C.c_int * 3, dst_offsets, 3), C.c_uint(dst_fill & 0xFFFFFFFF), C.c_size_t(int(dst_stride or 0)),
+            int(nframes), C.c_void_p(stream)))
+
+    def process_device_v210_packed10(self, src_ptr: int, src_pitch: int, src_stride: int, dst_ptr: int, dst_pitch: int, dst_offsets,
+                                     dst_fill: int, dst_stride: int, nframes: int, stream: int = 0) -> None:
+        """v210 blocks into ONE buffer of 10:10:10:2 words on a YUV422P10 filter whose output is 4:4:4
+        (jinc_filter_process_device_v210_packed10)."""
+        off = (C.c_int * 3)(*[int(o) for o in dst_offsets]) if dst_offsets is not None else None
+        self._check(lib().jinc_filter_process_device_v210_packed10(
+            self._h, C.c_void_p(src_ptr), int(src_pitch), C.c_size_t(int(src_stride or 0)), C.c_void_p(dst_ptr), int(dst_pitch), off,
+            C.c_uint(dst_fill & 0xFFFFFFFF), C.c_size_t(int(dst_stride or 0)), int(nframes), C.c_void_p(stream)))
 
     last_strided = staticmethod(last_strided)
     last_groups = staticmethod(last_groups)

@@ -203,6 +203,11 @@ int jinc_batch_create(const jinc_video_info* vi, const jinc_args* args, int ndev
 
 int jinc_batch_create_ex(const jinc_video_info* vi, const jinc_args* args, int sample_type, int ndevices, int streams_per_device,
                          int register_host_buffers, jinc_batch** out, char* err, size_t err_len) {
+    return jinc_batch_create_out(vi, args, sample_type, -1, -1, ndevices, streams_per_device, register_host_buffers, out, err, err_len);
+}
+
+int jinc_batch_create_out(const jinc_video_info* vi, const jinc_args* args, int sample_type, int out_sub_w, int out_sub_h, int ndevices,
+                          int streams_per_device, int register_host_buffers, jinc_batch** out, char* err, size_t err_len) {
     if (out) *out = nullptr;
     if (err && err_len) err[0] = '\0';
     if (!vi || !args || !out) return batch_fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
@@ -219,7 +224,7 @@ int jinc_batch_create_ex(const jinc_video_info* vi, const jinc_args* args, int s
     b->vi_in = *vi;
     for (int d = 0; d < ndevices; ++d) {
         jinc_filter* f = nullptr;
-        int rc = jinc_filter_create_ex(vi, args, sample_type, d, &f, err, err_len);
+        int rc = jinc_filter_create_out(vi, args, sample_type, out_sub_w, out_sub_h, d, &f, err, err_len);
         if (rc == JINC_OK) rc = jinc_filter_set_pipeline(f, streams_per_device, b->register_host == 3 ? 3 : 0);  // host memory is pinned here, not per instance
         if (rc != JINC_OK) {
             if (f) {

@@ -213,8 +213,15 @@ struct Choice {
     // few dozen workgroups of long serial phase loops even after the phase split below; the gather kernel's many small
     // blocks finish sooner: one frame per call 4/3x 45 -> 68 Gpix/s, 4/3x with tap 4 37 -> 46, 960 x 540 at 1.5x 16.5 -> 28
     // (two frames: 33 -> 44), 5/4x and 1.5x at 1080p equal; 1.5x with tap 4 loses 11 % (45 -> 40).
+    // The call size a plane's own decisions see.  A filter whose output has another chroma sub-sampling than its input
+    // (jinc_filter_create_out) promises that each plane is launched as a Y-only filter of the plane's geometry would launch it at
+    // the same frame count, so there a plane's limits read the plane's own samples; every other filter keeps the whole call's, as
+    // measured (the three planes of a 4:2:0 frame share the call's launch overhead).
+    double samples_for(const DeviceTable& t) const {
+        return f.converts_chroma() ? static_cast<double>(t.plan.dst_w) * t.plan.dst_h * nframes : call_samples;
+    }
     bool quasi_declined(const DeviceTable& t) const {  // (... in favour of the gather kernel, not of the direct kernel)
-        return f.kernel_mode == 0 && call_samples < Rules::kQuasiMinSamples && t.use_quasi && !t.use_periodic;
+        return f.kernel_mode == 0 && samples_for(t) < Rules::kQuasiMinSamples && t.use_quasi && !t.use_periodic;
     }
     bool wants_quasi(const DeviceTable& t) const {
         if (quasi_declined(t)) return false;
@@ -246,8 +253,8 @@ struct Choice {
             // round3/runs_vs_auto.txt: 1.5x at 4 / 16 frames per call 148 -> 173 / 277 -> 283 Gpix/s, at 64 the frame-lane kernel
             // is ahead (437 against 407); DVD -> 1080p (72 phases) at 1 / 4 / 16 frames 16.7 -> 19.5 / 62 -> 74 / 126 -> 141, at 64
             // 274 against 194; 3x (source step 1) loses from 4 frames on (467 -> 350 at 16)
-            if (t.runs.sx < 2 || t.runs.sy < 2 || call_samples < Rules::kQuasiMinSamples) return false;
-            if (call_samples > (t.runs.px * t.runs.py > 16 ? Rules::kRunsSmallFsMaxSamplesManyPhases : Rules::kRunsSmallFsMaxSamples)) return false;
+            if (t.runs.sx < 2 || t.runs.sy < 2 || samples_for(t) < Rules::kQuasiMinSamples) return false;
+            if (samples_for(t) > (t.runs.px * t.runs.py > 16 ? Rules::kRunsSmallFsMaxSamplesManyPhases : Rules::kRunsSmallFsMaxSamples)) return false;
         }
         // tiny calls: the gather kernel's single launch is over before border + interior launches of this form are
         // (640 x 360 -> 960 x 540 with tap 4, one frame, 42e6 taps: 21.5 against 15.6 Gpix/s; four frames: 48 against 54;
@@ -390,20 +397,24 @@ struct Choice {
     // call their launches cost more than they save (round3/border_strips_ab.txt, one frame per call: C2 122 -> 183 Gpix/s, C1 15.7 ->
     // 25.4, 1080p -> 4K 4:2:0 49 -> 74, 4K -> 1080p 27.7 -> 45, C3 24 -> 31; four frames: C2 346 -> 412, C1 59 -> 93; level from 3e9 ..
     // 7e9 taps on; tap 16 at 9e9 taps: -30 %).  f.border_strips: -1 this rule, 1 / 2 / 3 / 4 / 0 forced (tests, A/B; 3 = ewa_strip_kernel where configured, 4 = 3 with the columns in the interior kernel's edge tiles where configured).
-    bool wants_border_strips() const {
+    // `mine`: the table of the plane that asks.  A converting filter (samples_for) decides for each plane as for a single-plane call
+    // of that plane: its own taps, and the single-plane rule below.
+    bool wants_border_strips(const DeviceTable& mine) const {
         if (f.border_strips >= 0) return f.border_strips != 0;
+        const bool own = f.converts_chroma();
         double taps = 0.0;
-        for (int i = 0; i < f.planecount; ++i) {
+        for (int i = 0; i < f.planecount && !own; ++i) {
             const DeviceTable& t = f.tables[f.table_of_plane(i)];
             taps += static_cast<double>(t.plan.dst_w) * t.plan.dst_h * t.plan.fs * t.plan.fs;
         }
+        if (own) taps = static_cast<double>(mine.plan.dst_w) * mine.plan.dst_h * mine.plan.fs * mine.plan.fs;
         if (taps * nframes >= Rules::kStripBorderMinTaps) return true;
         // Single-plane calls whose border columns the interior kernel computes in its edge tiles (round 5): what is left of the strip
         // border is two small launches (rows, corners) against the gather launch over the whole frame -- ahead from half the size
         // (round5/small_call_border_ab.log: C2 at 6 / 8 / 12 frames per call +3 / +13 / +11 %, C1 at 64 / 96 +3.6 / +8.6 %; C2 at 4 and
         // C1 at 32 level / behind; calls with chroma planes -- three times the launches -- stay behind up to the limit above).
-        if (f.planecount == 1 && f.border_strips < 0) {
-            const DeviceTable& t = f.tables[f.table_of_plane(0)];
+        if ((f.planecount == 1 || own) && f.border_strips < 0) {
+            const DeviceTable& t = own ? mine : f.tables[f.table_of_plane(0)];
             const bool edge_form = t.use_edge_cols && t.strips_ok && (f.kernel_mode == 0 || f.kernel_mode == 13) && trimmed(t) && quad_chosen(t) &&
                                    (periodic_fs(t) == 6 || (periodic_fs(t) == 8 && quad2x8_chosen(t, rule_sb))) &&
                                    knobs::flag(JINC_KNOB_EDGE_COLS, true) && knobs::geti(JINC_KNOB_ROWPAIR_SMALL, 0) != 1;
@@ -584,7 +595,7 @@ void launch_plane(jinc_filter& f, const Choice& c, int i, const void* const src[
     bool edge_fused = false;
     if (direct || periodic || quasi) {
         // border frame: rows on kernel_direct.hip + columns on the gather kernel, or the gather kernel for all of it
-        const bool strips = c.wants_border_strips() && t.strips_ok && c.direct_ok(t, i);
+        const bool strips = c.wants_border_strips(t) && t.strips_ok && c.direct_ok(t, i);
         edge_fused = strips && periodic && t.use_edge_cols && (f.border_strips < 0 || f.border_strips == 4) && (f.kernel_mode == 0 || f.kernel_mode == 13) && c.trimmed(t) &&
                      c.quad_chosen(t) && (c.periodic_fs(t) == 6 || (c.periodic_fs(t) == 8 && c.quad2x8_chosen(t, c.rule_sb))) &&
                      knobs::flag(JINC_KNOB_EDGE_COLS, true) && knobs::geti(JINC_KNOB_ROWPAIR_SMALL, 0) != 1;  // (that knob sends the launch to the row-pair kernel)
@@ -1119,8 +1130,13 @@ jinc::FieldArgs field_args(const Side& s, const void* base, int pitch, const siz
     return a;
 }
 
-void check_packed10_side(const void* base, int pitch, const size_t* fs, int width, int nframes) {
+// (s: the side's planes -- a word holds one sample of each, so the three stand-ins have one size: filter.cpp has refused a side
+// whose chroma is sub-sampled with a message of the call's own; field_args reads the first plane's size for all three)
+void check_packed10_side(const void* base, int pitch, const size_t* fs, const Side& s, int nframes) {
+    const int width = s.w[0];
     if (!base) throw ArgError("JincResize: null plane pointer.");
+    if (s.w[1] != s.w[0] || s.w[2] != s.w[0] || s.h[1] != s.h[0] || s.h[2] != s.h[0])
+        throw ArgError("JincResize: packed 10-bit words need three planes of one size on their side of the filter.");
     if (reinterpret_cast<uintptr_t>(base) % 4) throw ArgError("JincResize: packed 10-bit words are not aligned to 4 bytes.");
     if (pitch <= 0 || pitch % 4) throw ArgError("JincResize: pitch of packed 10-bit words is not a multiple of 4.");
     if (fs && nframes > 1 && fs[0] % 4) throw ArgError("JincResize: frame stride of packed 10-bit words is not a multiple of 4.");
@@ -1252,8 +1268,8 @@ void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pi
     }
     in.ngroups = src_fields ? 1 : 0;
     out.ngroups = dst_fields ? 1 : 0;
-    if (src_fields) check_packed10_side(src[0], src_pitch[0], src_fs, in.w[0], nframes);
-    if (dst_fields) check_packed10_side(dst[0], dst_pitch[0], dst_fs, out.w[0], nframes);
+    if (src_fields) check_packed10_side(src[0], src_pitch[0], src_fs, in, nframes);
+    if (dst_fields) check_packed10_side(dst[0], dst_pitch[0], dst_fs, out, nframes);
     run_on_stand_ins(
         f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
         [&](char* scratch, int k0, int slice, int n) {
@@ -1469,7 +1485,7 @@ void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, co
     t_last_groups.count = 0;
     Side in, out;
     widened_words_sides(f, dst, dst_pitch, dst_step, dst_fs, nframes, in, out);
-    check_packed10_side(src, src_pitch, &src_fs, in.w[0], nframes);  // (filter.cpp has refused these already, with messages of this call's own)
+    check_packed10_side(src, src_pitch, &src_fs, in, nframes);  // (filter.cpp has refused these already, with messages of this call's own)
     // (every source plane has a stand-in: run_on_stand_ins reads none of these)
     const void* const src_planes[4] = {src, src, src, nullptr};
     const int src_pitches[4] = {src_pitch, src_pitch, src_pitch, 0};
@@ -1674,7 +1690,7 @@ void enqueue_narrowed_packed10(jinc_filter& f, const void* const src[4], const i
     t_last_groups.count = 0;
     Side in, out;
     narrowed_words_sides(f, src, src_pitch, src_step, src_fs, nframes, in, out);
-    check_packed10_side(dst, dst_pitch, &dst_fs, out.w[0], nframes);  // (filter.cpp has refused these already, with messages of this call's own)
+    check_packed10_side(dst, dst_pitch, &dst_fs, out, nframes);  // (filter.cpp has refused these already, with messages of this call's own)
     // (every destination plane has a stand-in: run_on_stand_ins reads none of these)
     void* const dst_planes[4] = {dst, dst, dst, nullptr};
     const int dst_pitches[4] = {dst_pitch, dst_pitch, dst_pitch, 0};
@@ -1714,6 +1730,67 @@ void enqueue_narrowed_v210(jinc_filter& f, const void* const src[4], const int s
             for (int c = 0; c < 3; ++c) a.value_scale[c] = dst_scale ? dst_scale[c] : 1.f, a.value_offset[c] = dst_offset ? dst_offset[c] : 0.f;
             record_v210(f, kNarrowV210, a, k0, scaled);
             hip_check(static_cast<hipError_t>(jinc::launch_narrow_v210(a, f.sample_kind(), n, stream, scaled)), "narrow v210 launch");
+            return 1;
+        });
+}
+
+// ---- jinc_filter_process_device_shifted_packed10 / _v210_packed10: P010-style planes or v210 blocks in, Y410 / RGB10A2 words out ----
+// The source side of enqueue_strided (steps and shifts; planes of step 1 and shift 0 go to the kernels where they lie) or of
+// enqueue_v210 (ONE buffer of blocks), the destination side of enqueue_packed10 (ONE buffer of words, one group of the three result
+// stand-ins, pack_fields_kernel): no new pass, run_on_stand_ins composes the two.  For filters whose OUTPUT is 4:4:4
+// (jinc_filter_create_out): a decoder's P010 or a capture card's v210 leaves as Y410 in one call.  The filter, the offsets, steps
+// and shifts have been checked by filter.cpp.
+void enqueue_into_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
+                           bool src_is_v210, const size_t* src_fs, void* dst, int dst_pitch, const int* dst_fields, unsigned dst_fill,
+                           size_t dst_fs, int nframes, hipStream_t stream) {
+    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
+    t_last_groups.count = 0;
+    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
+    Side in, out;
+    for (int i = 0; i < f.planecount; ++i) {
+        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
+        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
+        out.group_of[i] = out.channel_of[i] = 0;
+        in.group_of[i] = in.channel_of[i] = src_is_v210 ? 0 : -1;
+    }
+    out.ngroups = 1;
+    if (src_is_v210) {
+        in.ngroups = 1;
+        check_v210_side(src[0], src_pitch[0], src_fs, in, nframes);
+    } else {
+        in.ngroups = groups_of_side(src, src_pitch, src_step, src_shift, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
+        check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
+    }
+    check_packed10_side(dst, dst_pitch, &dst_fs, out, nframes);
+    void* const dst_planes[4] = {dst, dst, dst, nullptr};
+    const int dst_pitches[4] = {dst_pitch, dst_pitch, dst_pitch, 0};
+    const size_t dst_strides[4] = {dst_fs, dst_fs, dst_fs, 0};
+    run_on_stand_ins(
+        f, in, out, src, src_pitch, src_fs, dst_planes, dst_pitches, dst_strides, nframes, stream,
+        [&](char* scratch, int k0, int slice, int n) {
+            if (src_is_v210) {
+                const jinc::V210Args a = v210_args(in, src[0], src_pitch[0], src_fs, scratch, k0, slice, nframes);
+                record_v210(f, kUnpackV210, a, k0);
+                hip_check(static_cast<hipError_t>(jinc::launch_unpack_v210(a, n, stream)), "v210 unpack launch");
+                return 1;
+            }
+            InterleaveArgs split[5];
+            const int recorded = t_last_groups.count;
+            fill_args(f, in, src, src_pitch, src_step, src_shift, src_fs, scratch, k0, slice, nframes, false, split);
+            int launches = 0;
+            for (int step = 1; step <= 4; ++step)  // (step 1: shifted dense planes)
+                if (split[step].ngroups) {
+                    bool shifted = false;
+                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream, &shifted)), "split launch");
+                    record_shifted(recorded, kSplit, step, shifted, k0);
+                    ++launches;
+                }
+            return launches;
+        },
+        [&](char* scratch, int k0, int slice, int n) {
+            const jinc::FieldArgs a = field_args(out, dst, dst_pitch, dst_strides, dst_fields, dst_fill, scratch, k0, slice, nframes);
+            record_fields(f, kPackFields, a, k0);
+            hip_check(static_cast<hipError_t>(jinc::launch_pack_fields(a, n, stream)), "pack launch");
             return 1;
         });
 }

@@ -90,6 +90,17 @@ std::string refuse_narrowed_words(const jinc_filter* f, const char* what, const 
     return std::string();
 }
 
+// The shape rules of the stand-in calls are per side: a side of packed 10:10:10:2 words needs that side of the filter without
+// sub-sampling, a side of v210 blocks needs it 4:2:2.  Filters whose two sides share their sub-sampling (jinc_filter_create /
+// _create_ex) are refused by the calls' own texts; these are what a filter of jinc_filter_create_out with ANOTHER output
+// sub-sampling is told: `what` names the words or blocks, `side` is "source" or "destination".
+std::string refuse_side(const jinc_filter* f, const char* what, const char* side, const char* needs) {
+    const bool source = side[0] == 's';
+    const jinc_video_info& vi = source ? f->vi_in : f->vi_out;
+    return std::string("JincResize: ") + what + " on the " + side + " side need a filter whose " + (source ? "input" : "output") + " is " + needs +
+           "; this filter's " + (source ? "input" : "output") + " has sub_w " + std::to_string(vi.sub_w) + " and sub_h " + std::to_string(vi.sub_h) + ".";
+}
+
 // What the two scaled calls refuse of their own: a scale or offset of a used plane that is NaN or infinite, a scale that is zero.
 // `side` is "source" (widened) or "destination" (narrowed).  Empty: nothing to refuse.
 std::string refuse_scale_offset(const char* side, const float* scale, const float* offset, int planes) {
@@ -129,6 +140,11 @@ int jinc_filter_create(const jinc_video_info* vi, const jinc_args* args, int dev
 
 int jinc_filter_create_ex(const jinc_video_info* vi, const jinc_args* args, int sample_type, int device, jinc_filter** out, char* err,
                           size_t err_len) {
+    return jinc_filter_create_out(vi, args, sample_type, -1, -1, device, out, err, err_len);
+}
+
+int jinc_filter_create_out(const jinc_video_info* vi, const jinc_args* args, int sample_type, int out_sub_w, int out_sub_h, int device,
+                           jinc_filter** out, char* err, size_t err_len) {
     if (out) *out = nullptr;
     if (err && err_len) err[0] = '\0';
     if (!vi || !args || !out) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
@@ -143,7 +159,7 @@ int jinc_filter_create_ex(const jinc_video_info* vi, const jinc_args* args, int 
             throw ArgError("JincResize: bfloat16 clips must have 16 bits per component and 2-byte samples.");
         f->half = sample_type == JINC_SAMPLE_FLOAT16;
         f->bf16 = sample_type == JINC_SAMPLE_BFLOAT16;
-        configure(*f, *vi, *args);
+        configure(*f, *vi, *args, out_sub_w, out_sub_h);
         if (device >= 0) init_device(*f, device);
     });
     if (rc == JINC_ERR_HIP && device >= 0 && jinc_device_count() == 0) rc = JINC_ERR_NO_DEVICE;
@@ -327,9 +343,14 @@ int jinc_filter_process_device_packed10(jinc_filter* f, const void* const src[4]
     // the filter and the offsets first (they need no device), then the checks of jinc_filter_process_device_shifted in its order
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (src_field_offset || dst_field_offset) {
-        if (f->planecount != 3 || f->subsampled || f->float_samples() || f->vi_in.component_size != 2 || f->vi_in.bits_per_component != 10)
+        const bool sides_ok = (!src_field_offset || jinc_filter::side_is_444(f->vi_in)) && (!dst_field_offset || jinc_filter::side_is_444(f->vi_out));
+        if (f->planecount != 3 || (!f->converts_chroma() && !sides_ok) || f->float_samples() || f->vi_in.component_size != 2 || f->vi_in.bits_per_component != 10)
             return fail(JINC_ERR_INVALID_ARG, "JincResize: packed 10:10:10:2 words need a filter with three 10-bit components in 16-bit samples and no "
                                               "sub-sampling (YUV444P10, RGBP10).");
+        if (src_field_offset && !jinc_filter::side_is_444(f->vi_in))
+            return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "packed 10:10:10:2 words", "source", "not sub-sampled (4:4:4)"));
+        if (dst_field_offset && !jinc_filter::side_is_444(f->vi_out))
+            return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "packed 10:10:10:2 words", "destination", "not sub-sampled (4:4:4)"));
         for (const int* o : {src_field_offset, dst_field_offset}) {
             for (int i = 0; o && i < 3; ++i)
                 if (o[i] < 0 || o[i] > 22) return fail(JINC_ERR_INVALID_ARG, "JincResize: a field offset of a packed 10:10:10:2 word must be in 0..22.");
@@ -357,10 +378,15 @@ int jinc_filter_process_device_v210(jinc_filter* f, const void* const src[4], co
     // the filter first (it needs no device), then the checks of jinc_filter_process_device_shifted in its order
     if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (src_is_v210 || dst_is_v210) {
-        if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0 || f->float_samples() || f->vi_in.component_size != 2 ||
+        const bool sides_ok = (!src_is_v210 || jinc_filter::side_is_422(f->vi_in)) && (!dst_is_v210 || jinc_filter::side_is_422(f->vi_out));
+        if (f->planecount != 3 || (!f->converts_chroma() && !sides_ok) || f->float_samples() || f->vi_in.component_size != 2 ||
             f->vi_in.bits_per_component != 10)
             return fail(JINC_ERR_INVALID_ARG, "JincResize: v210 blocks need a filter with three 10-bit components in 16-bit samples and 4:2:2 "
                                               "sub-sampling (YUV422P10).");
+        if (src_is_v210 && !jinc_filter::side_is_422(f->vi_in))
+            return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "v210 blocks", "source", "4:2:2 (sub_w 1, sub_h 0)"));
+        if (dst_is_v210 && !jinc_filter::side_is_422(f->vi_out))
+            return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "v210 blocks", "destination", "4:2:2 (sub_w 1, sub_h 0)"));
     }
     if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
@@ -371,6 +397,70 @@ int jinc_filter_process_device_v210(jinc_filter* f, const void* const src[4], co
         hip_check(hipSetDevice(f->device), "hipSetDevice");
         enqueue_v210(*f, src, src_pitch, src_is_v210 != 0, src_frame_stride, dst, dst_pitch, dst_is_v210 != 0, dst_frame_stride, nframes,
                      static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+namespace {
+// jinc_filter_process_device_shifted_packed10 / _v210_packed10: the filter and the offsets first (they need no device).
+// `says`: a message, empty when there is nothing to refuse.
+void refuse_into_packed10(const jinc_filter* f, bool src_is_v210, const int* dst_field_offset, std::string& says) {
+    says.clear();
+    if (f->planecount != 3 || f->float_samples() || f->vi_in.component_size != 2 || f->vi_in.bits_per_component != 10)
+        { says = "JincResize: a packed 10:10:10:2 destination needs a filter with three 10-bit components in 16-bit samples."; return; }
+    if (src_is_v210 && !jinc_filter::side_is_422(f->vi_in)) { says = refuse_side(f, "v210 blocks", "source", "4:2:2 (sub_w 1, sub_h 0)"); return; }
+    if (!jinc_filter::side_is_444(f->vi_out)) { says = refuse_side(f, "packed 10:10:10:2 words", "destination", "not sub-sampled (4:4:4)"); return; }
+    for (int i = 0; dst_field_offset && i < 3; ++i)
+        if (dst_field_offset[i] < 0 || dst_field_offset[i] > 22) { says = "JincResize: a field offset of a packed 10:10:10:2 word must be in 0..22."; return; }
+    for (int i = 0; dst_field_offset && i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (dst_field_offset[i] - dst_field_offset[j] < 10 && dst_field_offset[j] - dst_field_offset[i] < 10)
+                { says = "JincResize: two fields of a packed 10:10:10:2 word overlap."; return; }
+}
+}  // namespace
+
+int jinc_filter_process_device_shifted_packed10(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
+                                                const int src_sample_shift[4], const size_t src_frame_stride[4], void* dst, int dst_pitch,
+                                                const int dst_field_offset[3], unsigned dst_fill, size_t dst_frame_stride, int nframes,
+                                                void* hip_stream) {
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    std::string refusal;
+    refuse_into_packed10(f, false, dst_field_offset, refusal);
+    if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
+    for (int i = 0; src_sample_step && i < 3; ++i)
+        if (src_sample_step[i] < 1 || src_sample_step[i] > 4) return fail(JINC_ERR_INVALID_ARG, "JincResize: sample step must be in 1..4.");
+    for (int i = 0; src_sample_shift && i < 3; ++i) {
+        if (src_sample_shift[i] < 0) return fail(JINC_ERR_INVALID_ARG, "JincResize: sample shift must not be negative.");
+        if (src_sample_shift[i] > 6)
+            return fail(JINC_ERR_INVALID_ARG, "JincResize: sample shift is larger than the padding of the sample's container (6 bits).");
+    }
+    if (!src || !src_pitch || !dst || !dst_field_offset) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && !src_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_into_packed10(*f, src, src_pitch, src_sample_step, src_sample_shift, false, src_frame_stride, dst, dst_pitch, dst_field_offset,
+                              dst_fill, dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int jinc_filter_process_device_v210_packed10(jinc_filter* f, const void* src, int src_pitch, size_t src_frame_stride, void* dst, int dst_pitch,
+                                             const int dst_field_offset[3], unsigned dst_fill, size_t dst_frame_stride, int nframes,
+                                             void* hip_stream) {
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    std::string refusal;
+    refuse_into_packed10(f, true, dst_field_offset, refusal);
+    if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
+    if (!src || !dst || !dst_field_offset) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        const void* const src_planes[4] = {src, src, src, nullptr};
+        const int src_pitches[4] = {src_pitch, src_pitch, src_pitch, 0};
+        const size_t src_strides[4] = {src_frame_stride, src_frame_stride, src_frame_stride, 0};
+        enqueue_into_packed10(*f, src_planes, src_pitches, nullptr, nullptr, true, src_strides, dst, dst_pitch, dst_field_offset, dst_fill,
+                              dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
     });
 }
 
@@ -554,7 +644,9 @@ int process_device_widened_packed10(jinc_filter* f, const void* src, int src_pit
     if (!scaled && f->bf16)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words do not go into a bfloat16 filter: 10-bit fields are not exact in "
                                           "bfloat16 (at most 8 bits); widen them into an fp32 or binary16 filter.");
-    if (f->planecount != 3 || f->subsampled)
+    if (f->planecount == 3 && f->converts_chroma() && !jinc_filter::side_is_444(f->vi_in))
+        return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "widened packed 10:10:10:2 words", "source", "not sub-sampled (4:4:4)"));
+    if (f->planecount != 3 || !jinc_filter::side_is_444(f->vi_in))
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words need a float filter with three components and no sub-sampling "
                                           "(YUV444PS, YUV444PH, RGBPS, RGBPH); this filter has " + std::to_string(f->planecount) + " component(s), sub_w " +
                                               std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
@@ -616,7 +708,9 @@ int process_device_widened_v210(jinc_filter* f, const void* src, int src_pitch, 
     if (!scaled && f->bf16)
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened v210 blocks do not go into a bfloat16 filter: 10-bit samples are not exact in bfloat16 "
                                           "(at most 8 bits); widen them into an fp32 or binary16 filter.");
-    if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0)
+    if (f->planecount == 3 && f->converts_chroma() && !jinc_filter::side_is_422(f->vi_in))
+        return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "widened v210 blocks", "source", "4:2:2 (sub_w 1, sub_h 0)"));
+    if (f->planecount != 3 || !jinc_filter::side_is_422(f->vi_in))
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened v210 blocks need a float filter with three components and 4:2:2 sub-sampling "
                                           "(YUV422PS, YUV422PH: sub_w 1, sub_h 0); this filter has " + std::to_string(f->planecount) + " component(s), sub_w " +
                                               std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
@@ -663,7 +757,9 @@ int jinc_filter_process_device_narrowed_packed10(jinc_filter* f, const void* con
     if (!f->float_samples())
         return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed packed 10:10:10:2 words need an fp32, binary16 or bfloat16 filter; this filter has " +
                                               std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_packed10).");
-    if (f->planecount != 3 || f->subsampled)
+    if (f->planecount == 3 && f->converts_chroma() && !jinc_filter::side_is_444(f->vi_out))
+        return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "narrowed packed 10:10:10:2 words", "destination", "not sub-sampled (4:4:4)"));
+    if (f->planecount != 3 || !jinc_filter::side_is_444(f->vi_out))
         return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed packed 10:10:10:2 words need a float filter with three components and no sub-sampling "
                                           "(YUV444PS, YUV444PH, RGBPS, RGBPH and their bfloat16 twins); this filter has " + std::to_string(f->planecount) +
                                               " component(s), sub_w " + std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
@@ -702,7 +798,9 @@ int jinc_filter_process_device_narrowed_v210(jinc_filter* f, const void* const s
     if (!f->float_samples())
         return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed v210 blocks need an fp32, binary16 or bfloat16 filter; this filter has " +
                                               std::to_string(f->vi_in.bits_per_component) + "-bit integer samples (use jinc_filter_process_device_v210).");
-    if (f->planecount != 3 || !f->subsampled || f->vi_in.sub_w != 1 || f->vi_in.sub_h != 0)
+    if (f->planecount == 3 && f->converts_chroma() && !jinc_filter::side_is_422(f->vi_out))
+        return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "narrowed v210 blocks", "destination", "4:2:2 (sub_w 1, sub_h 0)"));
+    if (f->planecount != 3 || !jinc_filter::side_is_422(f->vi_out))
         return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed v210 blocks need a float filter with three components and 4:2:2 sub-sampling "
                                           "(YUV422PS, YUV422PH and their bfloat16 twin: sub_w 1, sub_h 0); this filter has " + std::to_string(f->planecount) +
                                               " component(s), sub_w " + std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");

@@ -19,7 +19,8 @@ std::string lower(std::string s) {
 }  // namespace
 
 // ---- Create_JincResize argument handling (ref :700-789), then geometry (ref :791-866) ------------
-void configure(jinc_filter& f, const jinc_video_info& vi, const jinc_args& a) {
+// out_sub_w / out_sub_h (jinc_filter_create_out): the OUTPUT's chroma sub-sampling, -1 / -1 = the input's (the reference's filter).
+void configure(jinc_filter& f, const jinc_video_info& vi, const jinc_args& a, int out_sub_w, int out_sub_h) {
     auto has = [&](unsigned bit) { return (a.defined & bit) != 0; };
 
     if (!vi.is_planar) throw ArgError("JincResize: clip must be in planar format.");
@@ -50,7 +51,9 @@ void configure(jinc_filter& f, const jinc_video_info& vi, const jinc_args& a) {
         }
     }
     const bool is_420 = is_yuv_subsampled(vi, 1, 1);
-    if (cplace == "topleft" && !is_420)
+    // (the siting describes whichever side is sub-sampled: a 4:2:0 OUTPUT of a YUV clip takes topleft as a 4:2:0 input does)
+    const bool out_is_420 = !vi.is_rgb && vi.num_components >= 3 && out_sub_w == 1 && out_sub_h == 1;
+    if (cplace == "topleft" && !is_420 && !out_is_420)
         throw ArgError("JincResize: topleft must be used only for 4:2:0 chroma subsampling.");
 
     const int opt = has(JINC_ARG_OPT) ? a.opt : -1;
@@ -86,11 +89,35 @@ void configure(jinc_filter& f, const jinc_video_info& vi, const jinc_args& a) {
                                      : std::max(target_width * target_height, src_width * src_height);
     if (initial_capacity <= 0) throw ArgError("JincResize: initial_capacity must be greater than 0.");
 
+    // ---- the output's chroma sub-sampling (beyond the reference): behind its checks, in front of any work ----
+    const bool has_chroma = !vi.is_rgb && vi.num_components >= 3;
+    const bool out_given = out_sub_w != -1 || out_sub_h != -1;
+    const bool out_is_input = out_sub_w == vi.sub_w && out_sub_h == vi.sub_h;
+    if (out_given) {
+        if (!has_chroma) throw ArgError("JincResize: an output chroma sub-sampling needs a YUV clip with chroma planes (not RGB, not Y).");
+        if (!out_is_input) {
+            if (out_sub_w < -1 || out_sub_w > 1 || out_sub_h < -1 || out_sub_h > 1)
+                throw ArgError("JincResize: out_sub_w and out_sub_h must be -1, 0 or 1.");
+            if (out_sub_w == -1 || out_sub_h == -1) throw ArgError("JincResize: out_sub_w and out_sub_h must both be -1 or both be given.");
+            if (out_sub_w == 0 && out_sub_h == 1) throw ArgError("JincResize: 4:4:0 output (out_sub_w 0, out_sub_h 1) is not supported.");
+            if (!(vi.sub_w == 0 && vi.sub_h == 0) && !(vi.sub_w == 1 && vi.sub_h == 0) && !(vi.sub_w == 1 && vi.sub_h == 1))
+                throw ArgError("JincResize: 4:1:1 and 4:4:0 clips keep their chroma sub-sampling (give -1 or the clip's own values).");
+        }
+        if (target_width % (1 << out_sub_w))
+            throw ArgError("JincResize: target_width must be a multiple of the output's horizontal chroma sub-sampling factor.");
+        if (target_height % (1 << out_sub_h))
+            throw ArgError("JincResize: target_height must be a multiple of the output's vertical chroma sub-sampling factor.");
+    }
+    const int in_sub_w = vi.sub_w, in_sub_h = vi.sub_h;
+    if (!out_given) out_sub_w = in_sub_w, out_sub_h = in_sub_h;
+
     // ---- ref :791-866 ----
     f.vi_in = vi;
     f.vi_out = vi;
     f.vi_out.width = target_width;
     f.vi_out.height = target_height;
+    f.vi_out.sub_w = out_sub_w;
+    f.vi_out.sub_h = out_sub_h;
     f.cplace = cplace;
     f.peak = (vi.bits_per_component <= 16 && !f.half && !f.bf16) ? static_cast<float>((1 << vi.bits_per_component) - 1) : 0.f;  // (half, bfloat16: no clamp)
     f.planecount = vi.num_components;
@@ -110,24 +137,32 @@ void configure(jinc_filter& f, const jinc_video_info& vi, const jinc_args& a) {
     g.crop_w = crop_width;
     g.crop_h = crop_height;
 
-    const bool is_444 = !vi.is_rgb && vi.sub_w == 0 && vi.sub_h == 0;
+    // A chroma plan of its own wherever either side's chroma grid is not the luma grid (plane_dims shifts by each side's own values).
+    const bool is_444 = !vi.is_rgb && in_sub_w == 0 && in_sub_h == 0 && out_sub_w == 0 && out_sub_h == 0;
     f.subsampled = f.planecount > 1 && !(is_444 || vi.is_rgb);
     f.plans.push_back(jinc::build_plane_plan(f.lut, g));
     if (f.subsampled) {
-        const double div_w = 1 << vi.sub_w;
-        const double div_h = 1 << vi.sub_h;
+        const double div_w = 1 << in_sub_w;
+        const double div_h = 1 << in_sub_h;
+        // Offset of a co-sited axis in luma samples: a co-sited grid of factor d maps its
+        // coordinate c to luma d c - (d - 1) / 2, so output grid (d_o) o luma map (r u + crop) o input grid (d_i) leaves
+        // 0.5 ((d_i - 1) - r (d_o - 1)).  Equal factors keep the reference's line as it stands, 0.5 (1 - r) -- which is the same
+        // value for d = 2 and the reference's own for 4:1:1 (d = 4, ref :838-841).
+        auto co_sited = [](double d_i, double d_o, double r) {
+            return d_i == d_o ? 0.5 * (1.0 - r) : 0.5 * ((d_i - 1.0) - r * (d_o - 1.0));
+        };
         const double crop_left_uv =
             (cplace == "mpeg2" || cplace == "topleft")
-                ? (0.5 * (1.0 - static_cast<double>(src_width) / target_width) + crop_left) / div_w
+                ? (co_sited(div_w, 1 << out_sub_w, static_cast<double>(src_width) / target_width) + crop_left) / div_w
                 : crop_left / div_w;
         const double crop_top_uv =
-            (cplace == "topleft") ? (0.5 * (1.0 - static_cast<double>(src_height) / target_height) + crop_top) / div_h
+            (cplace == "topleft") ? (co_sited(div_h, 1 << out_sub_h, static_cast<double>(src_height) / target_height) + crop_top) / div_h
                                   : crop_top / div_h;
         jinc::TableGeometry gc = g;
-        gc.src_w = src_width >> vi.sub_w;
-        gc.src_h = src_height >> vi.sub_h;
-        gc.dst_w = target_width >> vi.sub_w;
-        gc.dst_h = target_height >> vi.sub_h;
+        gc.src_w = src_width >> in_sub_w;
+        gc.src_h = src_height >> in_sub_h;
+        gc.dst_w = target_width >> out_sub_w;
+        gc.dst_h = target_height >> out_sub_h;
         gc.crop_left = crop_left_uv;
         gc.crop_top = crop_top_uv;
         gc.crop_w = crop_width / div_w;
@@ -140,7 +175,8 @@ void configure(jinc_filter& f, const jinc_video_info& vi, const jinc_args& a) {
     // chroma geometry above and nothing else), so its GetFrame always takes the `else` of :623-624 and writes 2.
     // chroma_location is what the reference binary writes; chroma_location_by_siting is what its source means to
     // write, kept behind jinc_filter_set_chroma_location_mode.
-    if (is_420 || is_yuv_subsampled(vi, 1, 0) || is_yuv_subsampled(vi, 2, 0)) {
+    // (the property describes the frames this filter WRITES: it follows vi_out)
+    if (is_yuv_subsampled(f.vi_out, 1, 1) || is_yuv_subsampled(f.vi_out, 1, 0) || is_yuv_subsampled(f.vi_out, 2, 0)) {
         f.chroma_location = 2;
         f.chroma_location_by_siting = cplace == "mpeg2" ? 0 : (cplace == "mpeg1" ? 1 : 2);
     } else {

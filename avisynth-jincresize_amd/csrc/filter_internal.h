@@ -208,7 +208,11 @@ struct jinc_filter {
     bool float_samples() const { return half || bf16 || vi_in.component_size == 4; }
     int sample_kind() const { return half ? jinc::kSampleHalf : (bf16 ? jinc::kSampleBFloat16 : 0); }  // PlaneIO::sample_kind
     int planecount = 0;
-    bool subsampled = false;
+    bool subsampled = false;  // the chroma planes have a plan of their own: vi_in or vi_out is sub-sampled (each side by its own sub_w / sub_h)
+    // One side of a filter by its chroma grid (the stand-in calls' shape rules: a packed side needs 4:4:4, a v210 side 4:2:2).
+    static bool side_is_444(const jinc_video_info& vi) { return vi.is_rgb || (vi.sub_w == 0 && vi.sub_h == 0); }
+    static bool side_is_422(const jinc_video_info& vi) { return !vi.is_rgb && vi.sub_w == 1 && vi.sub_h == 0; }
+    bool converts_chroma() const { return vi_in.sub_w != vi_out.sub_w || vi_in.sub_h != vi_out.sub_h; }  // jinc_filter_create_out with another sub-sampling
     jinc::JincLut lut;
     std::vector<jinc::PlanePlan> plans;  // [0] luma / all planes, [1] chroma of subsampled formats
     int kernel_mode = 0;
@@ -310,8 +314,9 @@ namespace host {
 
 // filter.cpp: message of the last failure on the calling thread
 int fail(int code, const std::string& msg);
-// filter_args.cpp: Create_JincResize's argument handling (ref :700-789) and geometry (ref :791-866); throws ArgError
-void configure(jinc_filter& f, const jinc_video_info& vi, const jinc_args& a);
+// filter_args.cpp: Create_JincResize's argument handling (ref :700-789) and geometry (ref :791-866); throws ArgError.
+// out_sub_w / out_sub_h: the output's chroma sub-sampling (jinc_filter_create_out), -1 / -1: the input's.
+void configure(jinc_filter& f, const jinc_video_info& vi, const jinc_args& a, int out_sub_w = -1, int out_sub_h = -1);
 // device_plan.cpp
 void init_device(jinc_filter& f, int device);
 int buffer_range_check_covers_soffset(int device);
@@ -337,6 +342,11 @@ void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pi
 // pitch[0] and frame stride [0] are read.
 void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], bool src_is_v210, const size_t* src_fs,
                   void* const dst[4], const int dst_pitch[4], bool dst_is_v210, const size_t* dst_fs, int nframes, hipStream_t stream);
+// ... a strided / shifted source (enqueue_strided's source side) or ONE buffer of v210 blocks (src_is_v210: src[0], src_pitch[0] and
+// frame stride [0] are read) into ONE buffer of 10:10:10:2 words (enqueue_packed10's destination side).  Checked by filter.cpp.
+void enqueue_into_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
+                           bool src_is_v210, const size_t* src_fs, void* dst, int dst_pitch, const int* dst_fields, unsigned dst_fill,
+                           size_t dst_fs, int nframes, hipStream_t stream);
 size_t v210_row_bytes(int width);  // 16 * ceil(width / 6); 0 for width < 1
 // ... enqueue on an fp32 / binary16 filter for INTEGER source samples of src_bytes (1 or 2) holding src_bits bits above `shift`:
 // every source plane is widened into a dense stand-in of the filter's sample type; the destination side is enqueue_strided's.

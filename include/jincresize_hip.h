@@ -162,10 +162,60 @@ JINC_API int jinc_filter_create(const jinc_video_info *vi, const jinc_args *args
 JINC_API int jinc_filter_create_ex(const jinc_video_info *vi, const jinc_args *args, int sample_type, int device,
                                    jinc_filter **out, char *err, size_t err_len);
 
+/* jinc_filter_create_ex with the OUTPUT's chroma sub-sampling (beyond the reference, whose output always has the input's): a
+ * decoder's 4:2:0 / 4:2:2 frames leave with chroma on the luma grid (networks, Y410 / RGB10A2 swap chains, every YCbCr -> RGB step
+ * want that), 4:4:4 planes leave as 4:2:0 / 4:2:2.  out_sub_w / out_sub_h are log2 factors like jinc_video_info.sub_w / sub_h:
+ *   -1, -1            the input's: the call IS jinc_filter_create_ex -- same plans, same bits, same messages;
+ *   the input's own   the same filter (the target must then be a multiple of the factors, see below);
+ *   (0,0) (1,0) (1,1) 4:4:4, 4:2:2, 4:2:0 output from a 4:4:4, 4:2:2 or 4:2:0 YUV(A) clip of any sample type: all nine pairs.
+ * jinc_filter_output_info reports the output's values; every surface (get_frame, submit / wait, process_device and its variants,
+ * jinc_batch_process) takes source planes of the input's extents and writes destination planes of the output's.
+ * Definition.  Plane 0 (and alpha) is what a Y-only filter with the same arguments computes.  Planes 1 and 2 are, bit for bit, what
+ * a Y-only filter computes for a clip of the input's chroma size (width >> sub_w, height >> sub_h), target (target_width >>
+ * out_sub_w, target_height >> out_sub_h), the same quant_x / quant_y / tap / blur, and per axis, with d_i = 1 << sub (input),
+ * d_o = 1 << out_sub, r = clip size / target size (as doubles) and crop / crop_size the resolved src_left / src_width (src_top /
+ * src_height):
+ *   src_left (src_top)     = (k + crop) / d_i,  k = 0.5 * ((d_i - 1) - r * (d_o - 1)) on a co-sited axis, else crop / d_i
+ *   src_width (src_height) = crop_size / d_i
+ * An axis is co-sited horizontally for cplace mpeg2 and topleft, vertically for topleft; for d_i = d_o = 2 this is the
+ * reference's (0.5 * (1 - r) + crop) / 2.  cplace / _ChromaLocation describe the siting of whichever side is sub-sampled (of both
+ * when both are); "topleft" is taken when the input OR the output is 4:2:0.  jinc_filter_chroma_location follows the output: 2
+ * (or the by-siting value) for a sub-sampled output, -1 for a 4:4:4 one.
+ * JINC_ERR_INVALID_ARG, behind the reference's own checks and before any device work, each with a message of its own: out_sub
+ * other than -1 / -1 on an RGB or Y-only clip; a value outside -1, 0, 1 or only one of the two -1; (0,1) (4:4:0 output); a 4:1:1
+ * or 4:4:0 clip with an output that differs from it; target_width / target_height that is no multiple of 1 << out_sub_w /
+ * 1 << out_sub_h.
+ * The stand-in calls' shape rules hold per side: packed 10:10:10:2 words need that SIDE of the filter 4:4:4, v210 blocks need it
+ * 4:2:2, and the planes of a channel group share their extent on their side -- so NV12 / P010 go to planar 4:4:4 float planes
+ * through _widened[_scaled], P010 and v210 to Y410 through _shifted_packed10 / _v210_packed10 (below), 4:4:4 float planes to NV12 /
+ * P010 / v210 through _narrowed[_scaled] / _narrowed_v210. */
+JINC_API int jinc_filter_create_out(const jinc_video_info *vi, const jinc_args *args, int sample_type, int out_sub_w, int out_sub_h,
+                                    int device, jinc_filter **out, char *err, size_t err_len);
+
+/* A decoder's P010 (or any planes of jinc_filter_process_device_shifted's source side: a sample step 1..4 and a shift 0..6 per plane,
+ * either array may be NULL) into ONE buffer of 10:10:10:2 words (the destination side of jinc_filter_process_device_packed10: three
+ * bit offsets in plane order, 0..22 and not overlapping, dst_fill outside the fields; base, pitch and frame stride multiples of 4,
+ * pitch >= 4 * width) -- for an integer filter with three 10-bit components in 16-bit samples whose OUTPUT is 4:4:4
+ * (jinc_filter_create_out(..., 0, 0, ...) on YUV420P10 / YUV422P10, or YUV444P10 / RGBP10 themselves).  The same two passes as
+ * those calls -- the split of the source side, the pack of the destination side -- around the unchanged resampling launches, so
+ * the words hold, bit for bit, what jinc_filter_process_device writes into dense planes of the same values.  Frame strides of the
+ * source are required for nframes > 1. */
+JINC_API int jinc_filter_process_device_shifted_packed10(jinc_filter *f, const void *const src[4], const int src_pitch[4],
+                                                         const int src_sample_step[4], const int src_sample_shift[4],
+                                                         const size_t src_frame_stride[4], void *dst, int dst_pitch,
+                                                         const int dst_field_offset[3], unsigned dst_fill, size_t dst_frame_stride,
+                                                         int nframes, void *hip_stream);
+/* ... and v210 blocks (the source side of jinc_filter_process_device_v210: ONE buffer, rows of jinc_v210_row_bytes(width) bytes)
+ * into such words: the filter's INPUT is 4:2:2, its output 4:4:4 (jinc_filter_create_out(..., 0, 0, ...) on YUV422P10). */
+JINC_API int jinc_filter_process_device_v210_packed10(jinc_filter *f, const void *src, int src_pitch, size_t src_frame_stride, void *dst,
+                                                      int dst_pitch, const int dst_field_offset[3], unsigned dst_fill,
+                                                      size_t dst_frame_stride, int nframes, void *hip_stream);
+
 /* free_JincResize (ref :632-647). NULL is allowed. */
 JINC_API void jinc_filter_free(jinc_filter *f);
 
-/* The output clip's AVS_VideoInfo: the input's with width/height replaced (ref :791-792). */
+/* The output clip's AVS_VideoInfo: the input's with width/height replaced (ref :791-792) -- and sub_w / sub_h, for a filter of
+ * jinc_filter_create_out. */
 JINC_API int jinc_filter_output_info(const jinc_filter *f, jinc_video_info *out_vi);
 
 /* Value JincResize_GetFrame writes to the _ChromaLocation frame property (ref :617-625): **2 for every 4:2:0 / 4:2:2 /
@@ -713,6 +763,10 @@ JINC_API int jinc_batch_create(const jinc_video_info *vi, const jinc_args *args,
 /* jinc_batch_create with a sample type (JINC_SAMPLE_DEFAULT / JINC_SAMPLE_FLOAT16 / JINC_SAMPLE_BFLOAT16, as jinc_filter_create_ex). */
 JINC_API int jinc_batch_create_ex(const jinc_video_info *vi, const jinc_args *args, int sample_type, int ndevices,
                                   int streams_per_device, int register_host_buffers, jinc_batch **out, char *err, size_t err_len);
+/* jinc_batch_create_ex with the output's chroma sub-sampling (-1, -1: the input's), as jinc_filter_create_out. */
+JINC_API int jinc_batch_create_out(const jinc_video_info *vi, const jinc_args *args, int sample_type, int out_sub_w, int out_sub_h,
+                                   int ndevices, int streams_per_device, int register_host_buffers, jinc_batch **out, char *err,
+                                   size_t err_len);
 JINC_API int jinc_batch_devices(const jinc_batch *b);
 JINC_API int jinc_batch_set_affinity(jinc_batch *b, int on);
 JINC_API int jinc_batch_device_cpus(const jinc_batch *b, int device_index, int *cpus, int max_cpus);
