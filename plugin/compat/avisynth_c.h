@@ -3,8 +3,10 @@
  *
  * The AviSynth+ SDK header is not part of this repository or its build image.  This file is written from the API's
  * public names and call shapes so that the plugin can be compiled here -- into plugin/lib/libjincresize.so by
- * __graft_entry__.build(), and together with the mock host of tests/mock_avs/ for the plugin tests.  It is never used
- * to compile any file of /root/reference.  When building against a real AviSynth+ installation, put the SDK's include
+ * __graft_entry__.build(), and together with the mock host of tests/mock_avs/ for the plugin tests.  The test
+ * infrastructure also compiles the reference implementation against it (through a wrapper header of its own, into a test
+ * binary, never into the product): reference and mock host then share this one declaration, which pins arithmetic and
+ * argument handling, not binary compatibility with a real AviSynth+.  When building against a real AviSynth+ installation, put the SDK's include
  * directory FIRST on the include path so that its avisynth_c.h replaces this one; nothing in the plugin depends on this
  * file's details.
  *

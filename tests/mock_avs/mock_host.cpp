@@ -177,6 +177,14 @@ int avs_is_rgb(const AVS_VideoInfo* vi) { return pt_rgb(vi); }
 int avs_bits_per_component(const AVS_VideoInfo* vi) { return pt_bits(vi); }
 int avs_component_size(const AVS_VideoInfo* vi) { return pt_component_size(vi); }
 int avs_num_components(const AVS_VideoInfo* vi) { return pt_num_components(vi); }
+// Colour-family predicates (the plugin of this project does not use them; the reference built by oracle/build_ref.py does).
+static inline int pt_yuv_sub(const AVS_VideoInfo* vi, int sub_w, int sub_h) {
+    return pt_planar(vi) && !pt_rgb(vi) && pt_num_components(vi) >= 3 && pt_sub_w(vi) == sub_w && pt_sub_h(vi) == sub_h;
+}
+int avs_is_420(const AVS_VideoInfo* vi) { return pt_yuv_sub(vi, 1, 1); }
+int avs_is_422(const AVS_VideoInfo* vi) { return pt_yuv_sub(vi, 1, 0); }
+int avs_is_444(const AVS_VideoInfo* vi) { return pt_yuv_sub(vi, 0, 0); }
+int avs_is_yv411(const AVS_VideoInfo* vi) { return pt_yuv_sub(vi, 2, 0); }
 int avs_get_plane_width_subsampling(const AVS_VideoInfo* vi, int plane) {
     return (plane == AVS_PLANAR_U || plane == AVS_PLANAR_V) ? pt_sub_w(vi) : 0;
 }

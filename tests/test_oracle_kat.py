@@ -90,6 +90,22 @@ def test_output_kat_recorded_by_the_round5_judge(O, k):
     assert O.crc32_planes(out, dims) == k["crc32"]
 
 
+@pytest.mark.parametrize("k", [k for k in KAT["outputs_script_floats"] if not k.get("full_size")], ids=lambda k: k["name"])
+def test_output_kat_of_scripted_float_arguments(O, k):
+    """the reference reads every script float through avs_as_float, i.e. as a 32-bit value.  The oracle fed the
+    float32-rounded arguments gives the reference's answer to the scripted call; fed the doubles it gives the other crc on file
+    (the answer only a caller of the C ABI can get).  The full-size row (C4) is checked on the GPU, tests/test_reference_sweep.py."""
+    from conftest import oracle_kwargs
+    fmt = O.FORMATS[k["format"]]
+    src = O.lcg_frame(fmt, *k["src"], seed=k["seed"])
+    as_f32 = {a: (float(np.float32(v)) if isinstance(v, float) else v) for a, v in k["args"].items()}
+    for args, crc in ((as_f32, k["crc32"]), (k["args"], k["crc32_same_call_doubles"])):
+        flt = O.OracleFilter(fmt, k["src"][0], k["src"][1], k["dst"][0], k["dst"][1], **oracle_kwargs(args))
+        dims = flt.out_dims()
+        assert sum(w * h for w, h in dims) * fmt.sample_bytes == k["bytes"]
+        assert O.crc32_planes(flt.get_frame(src, threads=4), dims) == crc
+
+
 def test_threads_do_not_change_results(O):
     fmt = O.FORMATS["YUV420P16"]
     flt = O.OracleFilter(fmt, 96, 64, 200, 130, tap=4)
