@@ -1,15 +1,13 @@
 // dispatch.cpp -- the kernel launches of one frame call: per plane, which interior kernel and which border kernels run,
 // on which stream (the body of the process_frame call, ref /root/reference/src/JincResize.cpp:615, on device planes).
 // Layout: Rules (the measured cross-over constants) -> Choice (the rules applied to one call: no launches) -> launch_plane (the
-// launches of one plane under a Choice) -> enqueue_run (batch split, fork / join of the side stream, the plane loop); at the end
-// enqueue_strided: planes with a sample step, split -> enqueue -> merge.
+// launches of one plane under a Choice) -> enqueue_run (batch split, fork / join of the side stream, the plane loop).
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
 
 #include "filter_internal.h"
 #include "knobs.h"
-#include "v210_rows.h"
 
 namespace jinc {
 namespace host {
@@ -101,6 +99,8 @@ struct Rules {
     static constexpr long long kQuasiSplitTarget = 1024, kQuasiSplitTargetFs9 = 400;
 };
 
+}  // namespace
+
 // Everything the launches below assume about the caller's planes, checked BEFORE anything is queued: an error on plane 2
 // must not leave plane 0's border kernels running on the side stream with no join recorded.
 void validate_planes(const jinc_filter& f, const void* const src[4], const int src_pitch[4], const size_t src_fs[4],
@@ -121,6 +121,8 @@ void validate_planes(const jinc_filter& f, const void* const src[4], const int s
             throw ArgError("JincResize: destination plane larger than 4 GiB is not supported (32-bit store offsets).");
     }
 }
+
+namespace {
 
 // Two planes of ONE frame that share a table (the chroma planes of a YUV frame) as a two-frame batch of one plane: what the second
 // plane's pointers are from the first's.
@@ -865,935 +867,6 @@ void enqueue_run(jinc_filter& f, const void* const src[4], const int src_pitch[4
     }
 }
 }  // namespace
-
-// ---- jinc_filter_process_device_strided: device frames whose samples do not lie side by side (NV12 / P016, packed RGB(A)) ----
-// The resampling kernels keep their dense planes: a strided plane is SPLIT into a dense plane of the filter's own, the call runs
-// through enqueue as any other, and dense results are MERGED into the strided destination (kernel_interleave.hip).  Planes with
-// step 1 inside such a call go to the kernels where they lie.
-// jinc_filter_process_device_shifted (P010 / P012 / Y210: the sample in the high bits of its 16-bit word) adds a shift per plane
-// and side.  The same two passes apply it, so a plane with a non-zero shift takes a dense stand-in on that side at step 1 too: a
-// channel group of one plane with one sample per pixel.  The arithmetic kernels see low-aligned values, as ever.
-
-namespace {
-thread_local StridedReport t_last_strided;
-thread_local GroupsReport t_last_groups;  // cleared wherever t_last_strided is: what a call that runs no pass leaves
-
-// GroupRecord::direction
-enum : int { kWiden = 0, kNarrow = 1, kSplit = 2, kMerge = 3, kUnpackFields = 4, kPackFields = 5, kWidenFields = 6, kUnpackV210 = 7, kPackV210 = 8, kWidenV210 = 9, kNarrowFields = 10, kNarrowV210 = 11 };
-
-// One entry of jinc_debug_last_groups: a pass of a slice by the numbers its launch gets.  Only the call's first slice is kept: the
-// later ones differ in their frames alone.  The split lambda of a slice runs in front of its merge lambda and each fills its
-// arguments group by group, so the entries stand source side first, each side in the order of its groups' first planes.
-void record_pass(const jinc_filter& f, int direction, int step, int members, size_t sample_bytes, bool scaled, uint32_t unit,
-                 uint32_t vec_pixels, uint32_t width, uint32_t rows, int first_frame) {
-    if (first_frame != 0 || t_last_groups.count >= GroupsReport::kCapacity) return;
-    GroupRecord& r = t_last_groups.g[t_last_groups.count++];
-    r.direction = direction, r.step = step, r.members = members, r.sample_bytes = static_cast<int>(sample_bytes);
-    r.sample_type = f.half ? JINC_SAMPLE_FLOAT16 : f.bf16 ? JINC_SAMPLE_BFLOAT16 : JINC_SAMPLE_DEFAULT;
-    r.scaled = scaled ? 1 : 0;
-    r.unit = unit, r.vec_pixels = vec_pixels, r.width = width, r.rows = rows;
-    r.shifted = 0;
-}
-// Group e as its widening / narrowing / split / merge launch gets it.
-template <class Group>
-void record_group(const jinc_filter& f, int direction, const Group& e, int step, int members, size_t sample_bytes, bool scaled,
-                  int first_frame) {
-    record_pass(f, direction, step, members, sample_bytes, scaled, e.unit, e.vec_pixels, e.width, e.rows, first_frame);
-}
-// The split / merge entries from `from` on whose groups travelled in the launch of `step`: what launch_by_shape decided for it.
-void record_shifted(int from, int direction, int step, bool shifted, int first_frame) {
-    if (first_frame != 0) return;
-    for (int i = from; i < t_last_groups.count; ++i)
-        if (t_last_groups.g[i].direction == direction && t_last_groups.g[i].step == step) t_last_groups.g[i].shifted = shifted ? 1 : 0;
-}
-// The field and block passes: the three planes of the filter as one group (step and members 3), samples of the filter's size.
-void record_fields(const jinc_filter& f, int direction, const jinc::FieldArgs& a, int first_frame, bool scaled = false) {
-    record_pass(f, direction, 3, 3, static_cast<size_t>(f.vi_in.component_size), scaled, a.unit, a.vec_pixels, a.width, a.rows, first_frame);
-}
-void record_v210(const jinc_filter& f, int direction, const jinc::V210Args& a, int first_frame, bool scaled = false) {  // (vec_pixels: the pixels of the blocks that move in pairs)
-    record_pass(f, direction, 3, 3, static_cast<size_t>(f.vi_in.component_size), scaled, a.unit, 6u * jinc::v210::paired_blocks(a), a.width, a.rows, first_frame);
-}
-
-// Dense planes behind a call: 1 GiB unless the knob says otherwise.  Derived, not measured: a 1080p -> 4K 4:2:0 frame has
-// 2 x 960 x 540 source and 2 x 1920 x 1080 result chroma samples, with rows padded to 256 bytes 2 x (1024 x 540 + 2048 x 1080)
-// = 5.5 MB of dense planes per frame (5.2 MB unpadded), 0.66 - 0.71 GB for the 128 frames the full-group batch kernels want in one
-// call: the default keeps such a call in one slice.
-// A SHIFTED call keeps its luma here as well.  16-bit 1080p -> 4K with every plane shifted on both sides: 2 x (2048 x 540 +
-// 4096 x 1080) = 11.1 MB of chroma and 3840 x 1080 + 7680 x 2160 = 20.7 MB of luma, 31.8 MB per frame -- the default holds 33
-// frames, so a call of 128 runs as 33 + 33 + 33 + 29 and no slice fills a whole group of the batch kernels.  Callers that
-// send long shifted calls raise the knob (4.1 GB for 128 frames); the rule below is the same for every call.
-constexpr size_t kStridedScratchDefaultBytes = size_t(1) << 30;
-constexpr int kSliceFrames = 128;  // slices are multiples of this where the cap allows (kFrameLanePairFrames: whole groups of the batch kernels)
-
-struct Side {
-    int group_of[4], channel_of[4], ngroups = 0;
-    int w[4], h[4];
-    size_t dense_pitch[4] = {0, 0, 0, 0}, dense_fs[4] = {0, 0, 0, 0};  // of the strided planes (0: the plane is dense where it lies)
-    size_t offset[4] = {0, 0, 0, 0};                                    // of a strided plane's dense frames in the scratch, per frame of a slice
-};
-
-int step_of(const int* step, int i) { return step ? step[i] : 1; }
-int shift_of(const int* shift, int i) { return shift ? shift[i] : 0; }
-
-void check_strided_planes(const jinc_filter& f, const void* const base[4], const int pitch[4], const int* step, const size_t* fs,
-                          const Side& s, int nframes) {
-    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
-    for (int i = 0; i < f.planecount; ++i) {
-        if (s.group_of[i] < 0) continue;  // (planes that go to the kernels where they lie: validate_planes)
-        if (!base[i]) throw ArgError("JincResize: null plane pointer.");
-        if (pitch[i] <= 0 || pitch[i] % sb) throw ArgError("JincResize: plane pitch is not a multiple of the sample size.");
-        if (reinterpret_cast<uintptr_t>(base[i]) % sb) throw ArgError("JincResize: plane pointer is not aligned to the sample size.");
-        if (fs && nframes > 1 && fs[i] % sb) throw ArgError("JincResize: frame stride is not a multiple of the sample size.");
-        if (static_cast<size_t>(pitch[i]) < (static_cast<size_t>(s.w[i] - 1) * step_of(step, i) + 1) * sb)
-            throw ArgError("JincResize: plane pitch is smaller than the row size at this sample step.");
-    }
-}
-
-// The groups of one side as launch arguments, one InterleaveArgs per step (a call's groups normally share one).
-void fill_args(const jinc_filter& f, const Side& s, const void* const base[4], const int pitch[4], const int* step, const int* shift,
-               const size_t* fs, char* scratch, int first_frame, int slice_frames, int nframes, bool merge, InterleaveArgs by_step[5]) {
-    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
-    for (int g = 0; g < s.ngroups; ++g) {
-        InterleaveGroup e;
-        int n = 0, members = 0, first = -1;
-        uintptr_t lo = 0;
-        for (int i = 0; i < f.planecount; ++i) {
-            if (s.group_of[i] != g) continue;
-            if (first < 0) first = i;
-            const uintptr_t b = reinterpret_cast<uintptr_t>(base[i]);
-            lo = members ? std::min(lo, b) : b;
-            ++members;
-            e.plane[s.channel_of[i]] = scratch + s.offset[i] * static_cast<size_t>(slice_frames);
-            e.shift[s.channel_of[i]] = static_cast<uint8_t>(shift_of(shift, i));
-        }
-        n = step_of(step, first);
-        const size_t frame_stride = (fs && nframes > 1) ? fs[first] : 0;
-        e.packed = reinterpret_cast<char*>(lo) + static_cast<size_t>(first_frame) * frame_stride;
-        e.packed_frame_stride = frame_stride;
-        e.plane_frame_stride = s.dense_fs[first];
-        e.packed_pitch = static_cast<uint32_t>(pitch[first]);
-        e.plane_pitch = static_cast<uint32_t>(s.dense_pitch[first]);
-        e.width = static_cast<uint32_t>(s.w[first]);
-        e.rows = static_cast<uint32_t>(s.h[first]);
-        const uintptr_t a = lo | static_cast<uintptr_t>(pitch[first]) | static_cast<uintptr_t>(frame_stride);
-        e.unit = a % 16 == 0 ? 16u : a % 4 == 0 ? 4u : 0u;
-        const bool complete = members == n;
-        const uint32_t lane_pixels = static_cast<uint32_t>(16 / sb);
-        // (kernels.h: the merge of an incomplete group stores sample by sample; the split of one leaves the row's last pixel to the tail)
-        const uint32_t vec_from = complete ? e.width : merge ? 0u : e.width - 1;
-        e.vec_pixels = e.unit ? vec_from / lane_pixels * lane_pixels : 0u;
-        record_group(f, merge ? kMerge : kSplit, e, n, members, sb, false, first_frame);
-        InterleaveArgs& a_n = by_step[n];
-        a_n.g[a_n.ngroups++] = e;
-    }
-}
-
-// strided_groups, and with `shift` also every plane of step 1 with a non-zero shift as a group of its own
-int groups_of_side(const void* const base[4], const int pitch[4], const int* step, const int* shift, const size_t* frame_stride,
-                   const int width[4], const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
-    int ngroups = 0, first[4] = {0, 0, 0, 0};
-    uintptr_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
-    const uintptr_t sb = static_cast<uintptr_t>(component_size);
-    auto fs_of = [&](int i) { return frame_stride ? frame_stride[i] : size_t(0); };
-    for (int i = 0; i < nplanes; ++i) {
-        group_of[i] = channel_of[i] = -1;
-        const int n = step_of(step, i);
-        if (n <= 1 && shift_of(shift, i) == 0) continue;
-        const uintptr_t b = reinterpret_cast<uintptr_t>(base[i]);
-        for (int g = 0; g < ngroups && group_of[i] < 0 && n > 1; ++g) {
-            const int j = first[g];
-            if (step_of(step, j) != n || pitch[j] != pitch[i] || fs_of(j) != fs_of(i) || width[j] != width[i] || height[j] != height[i]) continue;
-            const uintptr_t nlo = std::min(lo[g], b), nhi = std::max(hi[g], b);
-            if (nhi - nlo >= static_cast<uintptr_t>(n) * sb || (b - nlo) % sb || (lo[g] - nlo) % sb) continue;  // not one pixel
-            bool distinct = true;
-            for (int k = 0; k < i; ++k) distinct &= !(group_of[k] == g && base[k] == base[i]);
-            if (!distinct) continue;
-            group_of[i] = g, lo[g] = nlo, hi[g] = nhi;
-        }
-        if (group_of[i] < 0) group_of[i] = ngroups, first[ngroups] = i, lo[ngroups] = hi[ngroups] = b, ++ngroups;
-    }
-    for (int i = 0; i < nplanes; ++i)
-        if (group_of[i] >= 0) channel_of[i] = static_cast<int>((reinterpret_cast<uintptr_t>(base[i]) - lo[group_of[i]]) / sb);
-    return ngroups;
-}
-
-// The part every call with stand-ins shares (strided / shifted planes, 10:10:10:2 words): `in` / `out` say which planes of a side
-// take a dense stand-in (group_of >= 0; of those planes base, pitch and frame stride are not read here).  split(scratch, first
-// frame, frames per slice, frames now) queues the passes that fill the source stand-ins of one slice, merge(...) those that empty
-// the result stand-ins; both return their number of launches.
-template <class Split, class Merge>
-void run_on_stand_ins(jinc_filter& f, Side& in, Side& out, const void* const src[4], const int src_pitch[4], const size_t* src_fs,
-                      void* const dst[4], const int dst_pitch[4], const size_t* dst_fs, int nframes, hipStream_t stream, Split split,
-                      Merge merge) {
-    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
-
-    // Dense planes of the strided ones: pitch and frame stride multiples of 256 bytes, like the look-ahead pipeline's group buffers.
-    size_t per_frame = 0;
-    for (Side* s : {&in, &out})
-        for (int i = 0; i < f.planecount; ++i) {
-            if (s->group_of[i] < 0) continue;
-            s->dense_pitch[i] = align_up(static_cast<size_t>(s->w[i]) * sb, 256);
-            s->dense_fs[i] = s->dense_pitch[i] * static_cast<size_t>(s->h[i]);
-            s->offset[i] = per_frame;
-            per_frame += s->dense_fs[i];
-        }
-    const double cap_knob = knobs::get(JINC_KNOB_STRIDED_SCRATCH_BYTES, static_cast<double>(kStridedScratchDefaultBytes));
-    const size_t cap = cap_knob < 1.0 ? size_t(1) : static_cast<size_t>(cap_knob);
-    int slice = static_cast<int>(std::min<size_t>(static_cast<size_t>(nframes), std::max<size_t>(cap / per_frame, 1)));
-    if (slice < nframes && slice >= kSliceFrames) slice = slice / kSliceFrames * kSliceFrames;
-
-    // The planes as the kernels will get them: dense ones where they lie, strided ones as their dense stand-ins.
-    const void* s_run[4] = {nullptr, nullptr, nullptr, nullptr};
-    void* d_run[4] = {nullptr, nullptr, nullptr, nullptr};
-    int sp_run[4] = {0, 0, 0, 0}, dp_run[4] = {0, 0, 0, 0};
-    size_t sfs_run[4] = {0, 0, 0, 0}, dfs_run[4] = {0, 0, 0, 0};
-    for (int i = 0; i < f.planecount; ++i) {
-        const bool si = in.group_of[i] >= 0, di = out.group_of[i] >= 0;
-        s_run[i] = si ? static_cast<const void*>(nullptr) : src[i];
-        d_run[i] = di ? static_cast<void*>(nullptr) : dst[i];
-        sp_run[i] = si ? static_cast<int>(in.dense_pitch[i]) : src_pitch[i];
-        dp_run[i] = di ? static_cast<int>(out.dense_pitch[i]) : dst_pitch[i];
-        sfs_run[i] = si ? in.dense_fs[i] : (src_fs && nframes > 1 ? src_fs[i] : 0);
-        dfs_run[i] = di ? out.dense_fs[i] : (dst_fs && nframes > 1 ? dst_fs[i] : 0);
-    }
-    const size_t need = per_frame * static_cast<size_t>(slice);
-    if (need > f.strided_scratch_bytes) {
-        if (f.strided_scratch) {
-            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize(strided scratch)");  // launches of earlier calls may still use the old planes
-            (void)hipFree(f.strided_scratch);
-        }
-        f.strided_scratch = nullptr, f.strided_scratch_bytes = 0, f.strided_pending = false;
-        hip_check(hipMalloc(&f.strided_scratch, need), "hipMalloc(strided scratch)");
-        f.strided_scratch_bytes = need;
-    }
-    char* scratch = static_cast<char*>(f.strided_scratch);
-    for (int i = 0; i < f.planecount; ++i) {
-        if (in.group_of[i] >= 0) s_run[i] = scratch + in.offset[i] * static_cast<size_t>(slice);
-        if (out.group_of[i] >= 0) d_run[i] = scratch + out.offset[i] * static_cast<size_t>(slice);
-    }
-    validate_planes(f, s_run, sp_run, sfs_run, d_run, dp_run, dfs_run, nframes);  // (before anything is queued)
-
-    // The dense planes are shared by successive calls: a call on ANOTHER stream than the previous strided call's waits for that
-    // call's last merge (same stream: stream order does it).  A ring of events, one per call in turn, like the fork / join events:
-    // no event is recorded again while a stream may still be waiting on it.
-    const unsigned turn = f.strided_turn % jinc_filter::kForkEvents;
-    if (f.strided_pending && stream != f.strided_last_stream)
-        hip_check(hipStreamWaitEvent(stream, f.ev_strided[(f.strided_turn + jinc_filter::kForkEvents - 1) % jinc_filter::kForkEvents], 0), "hipStreamWaitEvent(strided)");
-    if (!f.ev_strided[turn]) hip_check(hipEventCreateWithFlags(&f.ev_strided[turn], hipEventDisableTiming), "hipEventCreate(strided)");
-
-    StridedReport report{0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};
-    for (int k0 = 0; k0 < nframes; k0 += slice) {
-        const int n = std::min(slice, nframes - k0);
-        const void* s_now[4];
-        void* d_now[4];
-        for (int i = 0; i < 4; ++i) {
-            s_now[i] = (i < f.planecount && in.group_of[i] < 0) ? static_cast<const char*>(src[i]) + static_cast<size_t>(k0) * sfs_run[i] : s_run[i];
-            d_now[i] = (i < f.planecount && out.group_of[i] < 0) ? static_cast<char*>(dst[i]) + static_cast<size_t>(k0) * dfs_run[i] : d_run[i];
-        }
-        // Order on the caller's stream: split -> enqueue -> merge.  enqueue's side-stream kernels start behind ev_fork, which it records
-        // on `stream` AFTER the split queued here, and `stream` goes on only behind ev_join, recorded on the side stream after its last
-        // kernel: the merge queued below follows both streams' kernels.
-        report.split_launches += split(scratch, k0, slice, n);
-        enqueue(f, s_now, sp_run, sfs_run, d_now, dp_run, dfs_run, n, stream);
-        report.merge_launches += merge(scratch, k0, slice, n);
-        ++report.slices;
-    }
-    hip_check(hipEventRecord(f.ev_strided[turn], stream), "hipEventRecord(strided)");
-    ++f.strided_turn;
-    f.strided_pending = true;
-    f.strided_last_stream = stream;
-    t_last_strided = report;
-}
-
-// One side of a packed10 call as a launch argument.  fields: the three bit offsets (checked: filter.cpp).
-jinc::FieldArgs field_args(const Side& s, const void* base, int pitch, const size_t* fs, const int* fields, unsigned fill, char* scratch,
-                           int first_frame, int slice_frames, int nframes) {
-    jinc::FieldArgs a;
-    const size_t frame_stride = (fs && nframes > 1) ? fs[0] : 0;
-    a.packed = const_cast<char*>(static_cast<const char*>(base)) + static_cast<size_t>(first_frame) * frame_stride;
-    a.packed_frame_stride = frame_stride;
-    a.packed_pitch = static_cast<uint32_t>(pitch);
-    a.plane_pitch = static_cast<uint32_t>(s.dense_pitch[0]);
-    a.plane_frame_stride = s.dense_fs[0];
-    a.width = static_cast<uint32_t>(s.w[0]);
-    a.rows = static_cast<uint32_t>(s.h[0]);
-    const uintptr_t al = reinterpret_cast<uintptr_t>(base) | static_cast<uintptr_t>(pitch) | static_cast<uintptr_t>(frame_stride);
-    a.unit = al % 16 == 0 ? 16u : 4u;
-    a.vec_pixels = a.width / 8 * 8;
-    uint32_t mask = 0;
-    for (int c = 0; c < 3; ++c) {
-        a.plane[c] = scratch + s.offset[c] * static_cast<size_t>(slice_frames);
-        a.offset[c] = static_cast<uint32_t>(fields[c]);
-        mask |= 1023u << fields[c];
-    }
-    a.fill = fill & ~mask;
-    return a;
-}
-
-// (s: the side's planes -- a word holds one sample of each, so the three stand-ins have one size: filter.cpp has refused a side
-// whose chroma is sub-sampled with a message of the call's own; field_args reads the first plane's size for all three)
-void check_packed10_side(const void* base, int pitch, const size_t* fs, const Side& s, int nframes) {
-    const int width = s.w[0];
-    if (!base) throw ArgError("JincResize: null plane pointer.");
-    if (s.w[1] != s.w[0] || s.w[2] != s.w[0] || s.h[1] != s.h[0] || s.h[2] != s.h[0])
-        throw ArgError("JincResize: packed 10-bit words need three planes of one size on their side of the filter.");
-    if (reinterpret_cast<uintptr_t>(base) % 4) throw ArgError("JincResize: packed 10-bit words are not aligned to 4 bytes.");
-    if (pitch <= 0 || pitch % 4) throw ArgError("JincResize: pitch of packed 10-bit words is not a multiple of 4.");
-    if (fs && nframes > 1 && fs[0] % 4) throw ArgError("JincResize: frame stride of packed 10-bit words is not a multiple of 4.");
-    if (static_cast<size_t>(pitch) < 4 * static_cast<size_t>(width)) throw ArgError("JincResize: pitch of packed 10-bit words is smaller than 4 * width.");
-}
-
-// One side of a v210 call as a launch argument: plane 0 is the luma stand-in, planes 1 and 2 the chroma stand-ins (one size).
-jinc::V210Args v210_args(const Side& s, const void* base, int pitch, const size_t* fs, char* scratch, int first_frame, int slice_frames,
-                         int nframes) {
-    jinc::V210Args a;
-    const size_t frame_stride = (fs && nframes > 1) ? fs[0] : 0;
-    a.blocks = const_cast<char*>(static_cast<const char*>(base)) + static_cast<size_t>(first_frame) * frame_stride;
-    a.block_frame_stride = frame_stride;
-    a.block_pitch = static_cast<uint32_t>(pitch);
-    a.luma_pitch = static_cast<uint32_t>(s.dense_pitch[0]);
-    a.chroma_pitch = static_cast<uint32_t>(s.dense_pitch[1]);
-    a.luma_frame_stride = s.dense_fs[0];
-    a.chroma_frame_stride = s.dense_fs[1];
-    a.width = static_cast<uint32_t>(s.w[0]);
-    a.rows = static_cast<uint32_t>(s.h[0]);
-    a.whole_blocks = a.width / 6;
-    const uintptr_t al = reinterpret_cast<uintptr_t>(base) | static_cast<uintptr_t>(pitch) | static_cast<uintptr_t>(frame_stride);
-    a.unit = al % 16 == 0 ? 16u : 4u;
-    for (int c = 0; c < 3; ++c) a.plane[c] = scratch + s.offset[c] * static_cast<size_t>(slice_frames);
-    return a;
-}
-
-void check_v210_side(const void* base, int pitch, const size_t* fs, const Side& s, int nframes) {
-    if (!base) throw ArgError("JincResize: null plane pointer.");
-    if (s.w[0] != 2 * s.w[1] || s.w[1] != s.w[2] || s.h[0] != s.h[1] || s.h[1] != s.h[2])
-        throw ArgError("JincResize: v210 blocks need an even width and chroma planes of half that width.");
-    if (reinterpret_cast<uintptr_t>(base) % 4) throw ArgError("JincResize: v210 blocks are not aligned to 4 bytes.");
-    if (pitch <= 0 || pitch % 4) throw ArgError("JincResize: pitch of v210 blocks is not a multiple of 4.");
-    if (fs && nframes > 1 && fs[0] % 4) throw ArgError("JincResize: frame stride of v210 blocks is not a multiple of 4.");
-    if (static_cast<size_t>(pitch) < v210_row_bytes(s.w[0]))
-        throw ArgError("JincResize: pitch of v210 blocks is smaller than the row's blocks (16 * ceil(width / 6) bytes).");
-}
-
-}  // namespace
-
-size_t v210_row_bytes(int width) { return width < 1 ? 0 : 16 * ((static_cast<size_t>(width) + 5) / 6); }
-
-int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
-                   const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]) {
-    return groups_of_side(base, pitch, step, nullptr, frame_stride, width, height, component_size, nplanes, group_of, channel_of);
-}
-
-const StridedReport& last_strided_report() { return t_last_strided; }
-const GroupsReport& last_groups_report() { return t_last_groups; }
-
-void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
-                     const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift,
-                     const size_t* dst_fs, int nframes, hipStream_t stream) {
-    t_last_groups.count = 0;
-    bool dense = true;
-    for (int i = 0; i < f.planecount; ++i)
-        dense &= step_of(src_step, i) == 1 && step_of(dst_step, i) == 1 && shift_of(src_shift, i) == 0 && shift_of(dst_shift, i) == 0;
-    if (dense) {  // the call IS jinc_filter_process_device
-        enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
-        t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};
-        return;
-    }
-    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
-    Side in, out;
-    for (int i = 0; i < f.planecount; ++i) {
-        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
-        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
-    }
-    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
-    in.ngroups = groups_of_side(src, src_pitch, src_step, src_shift, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
-    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, dst_shift, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(sb), f.planecount, out.group_of, out.channel_of);
-    check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
-    check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
-    run_on_stand_ins(
-        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) {
-            InterleaveArgs split[5];
-            const int recorded = t_last_groups.count;
-            fill_args(f, in, src, src_pitch, src_step, src_shift, src_fs, scratch, k0, slice, nframes, false, split);
-            int launches = 0;
-            for (int step = 1; step <= 4; ++step)  // (step 1: shifted dense planes)
-                if (split[step].ngroups) {
-                    bool shifted = false;
-                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream, &shifted)), "split launch");
-                    record_shifted(recorded, kSplit, step, shifted, k0);
-                    ++launches;
-                }
-            return launches;
-        },
-        [&](char* scratch, int k0, int slice, int n) {
-            InterleaveArgs merge[5];
-            const int recorded = t_last_groups.count;
-            fill_args(f, out, dst_c, dst_pitch, dst_step, dst_shift, dst_fs, scratch, k0, slice, nframes, true, merge);
-            int launches = 0;
-            for (int step = 1; step <= 4; ++step)
-                if (merge[step].ngroups) {
-                    bool shifted = false;
-                    hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], static_cast<int>(sb), step, n, stream, &shifted)), "merge launch");
-                    record_shifted(recorded, kMerge, step, shifted, k0);
-                    ++launches;
-                }
-            return launches;
-        });
-}
-
-// ---- jinc_filter_process_device_packed10: Y410, R10G10B10A2 and kin -- three 10-bit samples in one 32-bit word per pixel ----
-// A packed side is ONE group of the filter's three planes: unpack_fields_kernel fills their dense stand-ins from the words,
-// pack_fields_kernel builds the words from the result stand-ins (kernel_interleave.hip).  Everything else -- the stand-ins'
-// 256-byte pitches, the slicing under strided_scratch_bytes, the order on the caller's stream, the event ring -- is
-// run_on_stand_ins, as for the strided and shifted calls.  Dense planes per frame: 3 x 2 bytes x the side's pixels (rows padded to
-// 256 bytes).  1080p -> 4K, both sides packed: 3 x (3840 x 1080 + 7680 x 2160) = 62 208 000 bytes, so the 1 GiB default holds
-// floor(1 073 741 824 / 62 208 000) = 17 frames -- below kSliceFrames, so no rounding: a call of 128 runs as 7 x 17 + 9.  Packed
-// source only: 12 441 600 bytes, 86 frames; packed destination only: 49 766 400 bytes, 21 frames.
-void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_fields, const size_t* src_fs,
-                      void* const dst[4], const int dst_pitch[4], const int* dst_fields, unsigned dst_fill, const size_t* dst_fs,
-                      int nframes, hipStream_t stream) {
-    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
-    t_last_groups.count = 0;
-    if (!src_fields && !dst_fields) {  // the call IS jinc_filter_process_device
-        enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
-        return;
-    }
-    Side in, out;
-    for (int i = 0; i < f.planecount; ++i) {
-        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
-        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
-        in.group_of[i] = in.channel_of[i] = src_fields ? 0 : -1;
-        out.group_of[i] = out.channel_of[i] = dst_fields ? 0 : -1;
-    }
-    in.ngroups = src_fields ? 1 : 0;
-    out.ngroups = dst_fields ? 1 : 0;
-    if (src_fields) check_packed10_side(src[0], src_pitch[0], src_fs, in, nframes);
-    if (dst_fields) check_packed10_side(dst[0], dst_pitch[0], dst_fs, out, nframes);
-    run_on_stand_ins(
-        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) {
-            if (!src_fields) return 0;
-            const jinc::FieldArgs a = field_args(in, src[0], src_pitch[0], src_fs, src_fields, 0u, scratch, k0, slice, nframes);
-            record_fields(f, kUnpackFields, a, k0);
-            hip_check(static_cast<hipError_t>(jinc::launch_unpack_fields(a, n, stream)), "unpack launch");
-            return 1;
-        },
-        [&](char* scratch, int k0, int slice, int n) {
-            if (!dst_fields) return 0;
-            const jinc::FieldArgs a = field_args(out, dst[0], dst_pitch[0], dst_fs, dst_fields, dst_fill, scratch, k0, slice, nframes);
-            record_fields(f, kPackFields, a, k0);
-            hip_check(static_cast<hipError_t>(jinc::launch_pack_fields(a, n, stream)), "pack launch");
-            return 1;
-        });
-}
-
-// ---- jinc_filter_process_device_v210: 10-bit 4:2:2 in 16-byte blocks of six pixels (capture and playout cards, ProRes / DNxHR tools) ----
-// A v210 side is ONE group of the filter's three planes (YUV422P10): unpack_v210_kernel fills their dense stand-ins from the blocks,
-// pack_v210_kernel builds the blocks from the result stand-ins (kernel_interleave.hip, v210_rows.h).  Everything else is
-// run_on_stand_ins, as for the strided, shifted and packed10 calls.  Dense planes per frame: the luma stand-in is `width` samples
-// wide, both chroma stand-ins width / 2 -- 2 planes' worth of 2-byte samples, 4 bytes x the side's pixels (rows padded to 256
-// bytes).  1080p -> 4K: 3840, 7680 and 3840 bytes a row are multiples of 256 already, the source's chroma rows of 960 x 2 = 1920
-// bytes are padded to 2048, so the source side takes (3840 + 2 x 2048) x 1080 = 8 570 880 bytes, the destination side
-// (7680 + 2 x 3840) x 2160 = 33 177 600; both 41 748 480, and the 1 GiB default holds floor(1 073 741 824 / 41 748 480) = 25
-// frames -- below kSliceFrames, so no rounding: a call of 128 runs as 5 x 25 + 3.  v210 source only: 125 frames, a call of 128 runs
-// as 125 + 3; v210 destination only: 32 frames.
-void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], bool src_is_v210, const size_t* src_fs,
-                  void* const dst[4], const int dst_pitch[4], bool dst_is_v210, const size_t* dst_fs, int nframes, hipStream_t stream) {
-    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
-    t_last_groups.count = 0;
-    if (!src_is_v210 && !dst_is_v210) {  // the call IS jinc_filter_process_device
-        enqueue(f, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream);
-        return;
-    }
-    Side in, out;
-    for (int i = 0; i < f.planecount; ++i) {
-        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
-        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
-        in.group_of[i] = in.channel_of[i] = src_is_v210 ? 0 : -1;
-        out.group_of[i] = out.channel_of[i] = dst_is_v210 ? 0 : -1;
-    }
-    in.ngroups = src_is_v210 ? 1 : 0;
-    out.ngroups = dst_is_v210 ? 1 : 0;
-    if (src_is_v210) check_v210_side(src[0], src_pitch[0], src_fs, in, nframes);
-    if (dst_is_v210) check_v210_side(dst[0], dst_pitch[0], dst_fs, out, nframes);
-    run_on_stand_ins(
-        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) {
-            if (!src_is_v210) return 0;
-            const jinc::V210Args a = v210_args(in, src[0], src_pitch[0], src_fs, scratch, k0, slice, nframes);
-            record_v210(f, kUnpackV210, a, k0);
-            hip_check(static_cast<hipError_t>(jinc::launch_unpack_v210(a, n, stream)), "v210 unpack launch");
-            return 1;
-        },
-        [&](char* scratch, int k0, int slice, int n) {
-            if (!dst_is_v210) return 0;
-            const jinc::V210Args a = v210_args(out, dst[0], dst_pitch[0], dst_fs, scratch, k0, slice, nframes);
-            record_v210(f, kPackV210, a, k0);
-            hip_check(static_cast<hipError_t>(jinc::launch_pack_v210(a, n, stream)), "v210 pack launch");
-            return 1;
-        });
-}
-
-// ---- jinc_filter_process_device_widened: integer device frames into an fp32 / binary16 / bfloat16 filter (NV12, P010, Y210, BGRA8, planar) ----
-// The split that joins a decoder's surface to the float filters: EVERY source plane, dense ones included, takes a dense stand-in of
-// the filter's sample type, filled by widen_samples_kernel (kernel_widen.hip) with float((raw >> shift) & mask) -- exact.  From
-// there the call is enqueue on float planes, so the result is jinc_filter_process_device's on planes of those values by
-// construction: same plan, same kernels, same finite scan (which finds nothing).  The destination side is enqueue_strided's:
-// planes with step 1 are written where they lie, the others merged from result stand-ins.  Everything else is run_on_stand_ins.
-// Dense planes per frame, 1080p -> 4K into planar planes: fp32 rows of 1920 x 4 = 7680 and 960 x 4 = 3840 bytes are multiples of
-// 256 already, so NV12 / P010 take 7680 x 1080 + 2 x 3840 x 540 = 12 441 600 bytes and the 1 GiB default holds
-// floor(1 073 741 824 / 12 441 600) = 86 frames -- below kSliceFrames, so no rounding: a call of 128 runs as 86 + 42.  binary16:
-// 3840 x 1080 + 2 x 1920 x 540 = 6 220 800 bytes, 172 frames, rounded down to 128: a call of 128 in one slice.
-namespace {
-// The groups of a widened source as launch arguments, one WidenArgs per step (fill_args for source samples of their own size).
-void fill_widen_args(const jinc_filter& f, const Side& s, const void* const base[4], const int pitch[4], const int* step, const int* shift,
-                     const float* scale, const float* offset, const size_t* fs, size_t src_bytes, uint32_t mask, char* scratch,
-                     int first_frame, int slice_frames, int nframes, WidenArgs by_step[5]) {
-    for (int g = 0; g < s.ngroups; ++g) {
-        WidenGroup e;
-        int members = 0, first = -1;
-        uintptr_t lo = 0;
-        for (int i = 0; i < f.planecount; ++i) {
-            if (s.group_of[i] != g) continue;
-            if (first < 0) first = i;
-            const uintptr_t b = reinterpret_cast<uintptr_t>(base[i]);
-            lo = members ? std::min(lo, b) : b;
-            ++members;
-            e.plane[s.channel_of[i]] = scratch + s.offset[i] * static_cast<size_t>(slice_frames);
-            e.shift[s.channel_of[i]] = static_cast<uint8_t>(shift_of(shift, i));
-            e.scale[s.channel_of[i]] = scale ? scale[i] : 1.f;  // (plane i's pair travels with its channel of the group)
-            e.offset[s.channel_of[i]] = offset ? offset[i] : 0.f;
-        }
-        const int n = step_of(step, first);
-        const size_t frame_stride = (fs && nframes > 1) ? fs[first] : 0;
-        e.packed = reinterpret_cast<const char*>(lo) + static_cast<size_t>(first_frame) * frame_stride;
-        e.packed_frame_stride = frame_stride;
-        e.plane_frame_stride = s.dense_fs[first];
-        e.packed_pitch = static_cast<uint32_t>(pitch[first]);
-        e.plane_pitch = static_cast<uint32_t>(s.dense_pitch[first]);
-        e.width = static_cast<uint32_t>(s.w[first]);
-        e.rows = static_cast<uint32_t>(s.h[first]);
-        const uintptr_t a = lo | static_cast<uintptr_t>(pitch[first]) | static_cast<uintptr_t>(frame_stride);
-        e.unit = a % 16 == 0 ? 16u : a % 4 == 0 ? 4u : 0u;
-        const uint32_t lane_pixels = static_cast<uint32_t>(16 / src_bytes);
-        // (a group with a channel missing leaves the row's last pixel to the tail: its missing samples may lie behind the caller's buffer)
-        const uint32_t vec_from = members == n ? e.width : e.width - 1;
-        e.vec_pixels = e.unit ? vec_from / lane_pixels * lane_pixels : 0u;
-        record_group(f, kWiden, e, n, members, src_bytes, scale || offset, first_frame);
-        WidenArgs& a_n = by_step[n];
-        a_n.mask = mask;
-        a_n.g[a_n.ngroups++] = e;
-    }
-}
-// The merge of a widened call's destination side (enqueue_strided's, without shifts): planes with a step other than 1 out of their
-// result stand-ins.  Returns the number of launches.
-int merge_widened(const jinc_filter& f, const Side& out, const void* const dst_c[4], const int dst_pitch[4], const int* dst_step,
-                  const size_t* dst_fs, char* scratch, int k0, int slice, int n, int nframes, hipStream_t stream) {
-    InterleaveArgs merge[5];
-    const int recorded = t_last_groups.count;
-    fill_args(f, out, dst_c, dst_pitch, dst_step, nullptr, dst_fs, scratch, k0, slice, nframes, true, merge);
-    int launches = 0;
-    for (int step = 1; step <= 4; ++step)
-        if (merge[step].ngroups) {
-            bool shifted = false;
-            hip_check(static_cast<hipError_t>(jinc::launch_merge_samples(merge[step], f.vi_in.component_size, step, n, stream, &shifted)), "merge launch");
-            record_shifted(recorded, kMerge, step, shifted, k0);
-            ++launches;
-        }
-    return launches;
-}
-}  // namespace
-
-// src_scale / src_offset (jinc_filter_process_device_widened_scaled; both nullptr: the unscaled call): the same stand-ins, the same
-// launches, the same report -- the widening kernel's scaled form stores fl32(fl32(float(value) * scale) + offset) in their place.
-void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
-                     int src_bits, const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step,
-                     const size_t* dst_fs, int nframes, hipStream_t stream, const float* src_scale, const float* src_offset) {
-    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
-    t_last_groups.count = 0;
-    const size_t sb = static_cast<size_t>(f.vi_in.component_size), src_bytes = src_bits > 8 ? 2 : 1;
-    Side in, out;
-    for (int i = 0; i < f.planecount; ++i) {
-        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
-        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
-    }
-    // Every source plane is a member of a group (groups_of_side gives a plane of step 1 a group of its own when it has a shift: here
-    // every plane counts as having one); planes of one pixel share a group by the strided call's rule, in source samples.
-    static const int kEveryPlane[4] = {1, 1, 1, 1};
-    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
-    in.ngroups = groups_of_side(src, src_pitch, src_step, kEveryPlane, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(src_bytes), f.planecount, in.group_of, in.channel_of);
-    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, nullptr, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(sb), f.planecount, out.group_of, out.channel_of);
-    for (int i = 0; i < f.planecount; ++i) {  // (base alignment and the row's size: filter.cpp, in front of the device check)
-        if (!src[i]) throw ArgError("JincResize: null plane pointer.");
-        if (src_pitch[i] <= 0 || src_pitch[i] % src_bytes) throw ArgError("JincResize: source pitch is not a multiple of the source sample size.");
-        if (src_fs && nframes > 1 && src_fs[i] % src_bytes) throw ArgError("JincResize: source frame stride is not a multiple of the source sample size.");
-    }
-    check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
-    const uint32_t mask = (1u << src_bits) - 1u;
-    const bool scaled = src_scale || src_offset;
-    run_on_stand_ins(
-        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) {
-            WidenArgs widen[5];
-            fill_widen_args(f, in, src, src_pitch, src_step, src_shift, src_scale, src_offset, src_fs, src_bytes, mask, scratch, k0, slice, nframes, widen);
-            int launches = 0;
-            for (int step = 1; step <= 4; ++step)
-                if (widen[step].ngroups) {
-                    hip_check(static_cast<hipError_t>(jinc::launch_widen_samples(widen[step], static_cast<int>(src_bytes), step, static_cast<int>(sb), f.sample_kind(), n, stream, scaled)), "widen launch");
-                    ++launches;
-                }
-            return launches;
-        },
-        [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });
-}
-
-// ---- jinc_filter_process_device_widened_packed10 / _v210 (and their _scaled forms): Y410 / RGB10A2 words and v210 blocks into an fp32 / binary16 (scaled: bfloat16 too) filter ----
-// The source is ONE group of the filter's three planes, as the packed side of enqueue_packed10 or the v210 side of enqueue_v210, and
-// every source plane takes a stand-in of the FILTER's type: widen_fields_kernel / widen_v210_kernel (kernel_widen.hip) fill them
-// with float(field) -- ten bits, exact in fp32 and in binary16.  The destination side and its merge are enqueue_widened's, and
-// everything else is run_on_stand_ins, so these calls alternate with strided and widened ones on one filter.  The report counts the
-// widening launch as a split launch.
-// Dense planes per frame of a 1080p source (rows padded to 256 bytes), planar destination: Y410 into fp32 3 x 7680 x 1080 =
-// 24 883 200 bytes, floor(1 073 741 824 / 24 883 200) = 43 frames under the 1 GiB default; into binary16 3 x 3840 x 1080 =
-// 12 441 600 bytes, 86 frames.  v210 into fp32 (7680 + 2 x 3840) x 1080 = 16 588 800 bytes, 64 frames; into binary16 the chroma
-// rows of 960 x 2 = 1920 bytes are padded to 2048: (3840 + 2 x 2048) x 1080 = 8 570 880 bytes, 125 frames.  All below kSliceFrames,
-// so no rounding: a call of 128 runs as 43 + 43 + 42, 86 + 42, 64 + 64 and 125 + 3.
-namespace {
-// The sides of such a call: the source one group of three stand-ins, the destination enqueue_strided's.
-void widened_words_sides(const jinc_filter& f, void* const dst[4], const int dst_pitch[4], const int* dst_step, const size_t* dst_fs,
-                         int nframes, Side& in, Side& out) {
-    for (int i = 0; i < f.planecount; ++i) {
-        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
-        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
-        in.group_of[i] = in.channel_of[i] = 0;
-    }
-    in.ngroups = 1;
-    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
-    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, nullptr, nframes > 1 ? dst_fs : nullptr, out.w, out.h, f.vi_in.component_size, f.planecount, out.group_of, out.channel_of);
-    check_strided_planes(f, dst_c, dst_pitch, dst_step, dst_fs, out, nframes);
-}
-}  // namespace
-
-// src_scale / src_offset (jinc_filter_process_device_widened_packed10_scaled / _widened_v210_scaled; three floats in plane order, both
-// nullptr: the unscaled calls): the same stand-ins, the same launches, the same report -- the kernels' scaled forms store
-// fl32(fl32(float(field) * scale) + offset), rounded to nearest even into 16-bit planes, so bfloat16 filters come this way too.
-void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, const int* src_fields, size_t src_fs, void* const dst[4],
-                              const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream,
-                              const float* src_scale, const float* src_offset) {
-    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
-    t_last_groups.count = 0;
-    Side in, out;
-    widened_words_sides(f, dst, dst_pitch, dst_step, dst_fs, nframes, in, out);
-    check_packed10_side(src, src_pitch, &src_fs, in, nframes);  // (filter.cpp has refused these already, with messages of this call's own)
-    // (every source plane has a stand-in: run_on_stand_ins reads none of these)
-    const void* const src_planes[4] = {src, src, src, nullptr};
-    const int src_pitches[4] = {src_pitch, src_pitch, src_pitch, 0};
-    const size_t src_strides[4] = {src_fs, src_fs, src_fs, 0};
-    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
-    const bool scaled = src_scale || src_offset;
-    run_on_stand_ins(
-        f, in, out, src_planes, src_pitches, src_strides, dst, dst_pitch, dst_fs, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) {
-            jinc::WidenFieldArgs a;
-            static_cast<jinc::FieldArgs&>(a) = field_args(in, src, src_pitch, src_strides, src_fields, 0u, scratch, k0, slice, nframes);
-            for (int c = 0; c < 3; ++c) a.value_scale[c] = src_scale ? src_scale[c] : 1.f, a.value_offset[c] = src_offset ? src_offset[c] : 0.f;
-            record_fields(f, kWidenFields, a, k0, scaled);
-            hip_check(static_cast<hipError_t>(jinc::launch_widen_fields(a, f.sample_kind(), n, stream, scaled)), "widen fields launch");
-            return 1;
-        },
-        [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });
-}
-
-void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t src_fs, void* const dst[4], const int dst_pitch[4],
-                          const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream, const float* src_scale,
-                          const float* src_offset) {
-    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
-    t_last_groups.count = 0;
-    Side in, out;
-    widened_words_sides(f, dst, dst_pitch, dst_step, dst_fs, nframes, in, out);
-    check_v210_side(src, src_pitch, &src_fs, in, nframes);  // (filter.cpp has refused these already, with messages of this call's own)
-    const void* const src_planes[4] = {src, src, src, nullptr};
-    const int src_pitches[4] = {src_pitch, src_pitch, src_pitch, 0};
-    const size_t src_strides[4] = {src_fs, src_fs, src_fs, 0};
-    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
-    const bool scaled = src_scale || src_offset;
-    run_on_stand_ins(
-        f, in, out, src_planes, src_pitches, src_strides, dst, dst_pitch, dst_fs, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) {
-            jinc::WidenV210Args a;
-            static_cast<jinc::V210Args&>(a) = v210_args(in, src, src_pitch, src_strides, scratch, k0, slice, nframes);
-            for (int c = 0; c < 3; ++c) a.value_scale[c] = src_scale ? src_scale[c] : 1.f, a.value_offset[c] = src_offset ? src_offset[c] : 0.f;
-            record_v210(f, kWidenV210, a, k0, scaled);
-            hip_check(static_cast<hipError_t>(jinc::launch_widen_v210(a, f.sample_kind(), n, stream, scaled)), "widen v210 launch");
-            return 1;
-        },
-        [&](char* scratch, int k0, int slice, int n) { return merge_widened(f, out, dst_c, dst_pitch, dst_step, dst_fs, scratch, k0, slice, n, nframes, stream); });
-}
-
-// ---- jinc_filter_process_device_narrowed: the results of an fp32 / binary16 / bfloat16 filter into INTEGER device frames ----
-// The mirror image of enqueue_widened: the unchanged enqueue on stand-ins of the filter's own type and ONE new pass behind it.
-// EVERY destination plane takes a dense stand-in of the filter's type (for groups_of_side every plane counts as having a shift, in
-// destination sample bytes); narrow_samples_kernel (kernel_narrow.hip) stores lrintf(clamp(r, 0, peak)) << shift from them, one launch
-// per step value present -- NV12: 2 (Y at step 1, UV at step 2), planar: 1, BGRA8: 1 -- which the report counts as merge launches.
-// A source plane takes a stand-in only where its step is not 1, through enqueue_strided's split.  Everything else is
-// run_on_stand_ins, so these calls alternate with strided, shifted, packed10, v210 and widened ones on one filter.
-// Dense planes per frame, 1080p -> 4K into NV12 from planar planes: fp32 rows of 3840 x 4 = 15 360 and 1920 x 4 = 7680 bytes are
-// multiples of 256 already, so a frame takes 15 360 x 2160 + 2 x 7680 x 1080 = 49 766 400 bytes and the 1 GiB default holds
-// floor(1 073 741 824 / 49 766 400) = 21 frames -- below kSliceFrames, so no rounding: a call of 128 runs as 6 x 21 + 2.  binary16 /
-// bfloat16: 7680 x 2160 + 2 x 3840 x 1080 = 24 883 200 bytes, 43 frames: 43 + 43 + 42.
-namespace {
-// The groups of a narrowed destination as launch arguments, one NarrowArgs per step (fill_args for destination samples of their own size).
-void fill_narrow_args(const jinc_filter& f, const Side& s, void* const base[4], const int pitch[4], const int* step, const int* shift,
-                      const float* scale, const float* offset, const size_t* fs, size_t dst_bytes, float peak, const char* scratch,
-                      int first_frame, int slice_frames, int nframes, NarrowArgs by_step[5]) {
-    for (int g = 0; g < s.ngroups; ++g) {
-        NarrowGroup e;
-        int members = 0, first = -1;
-        uintptr_t lo = 0;
-        for (int i = 0; i < f.planecount; ++i) {
-            if (s.group_of[i] != g) continue;
-            if (first < 0) first = i;
-            const uintptr_t b = reinterpret_cast<uintptr_t>(base[i]);
-            lo = members ? std::min(lo, b) : b;
-            ++members;
-            e.plane[s.channel_of[i]] = scratch + s.offset[i] * static_cast<size_t>(slice_frames);
-            e.shift[s.channel_of[i]] = static_cast<uint8_t>(shift_of(shift, i));
-            e.scale[s.channel_of[i]] = scale ? scale[i] : 1.f;  // (plane i's pair travels with its channel of the group)
-            e.offset[s.channel_of[i]] = offset ? offset[i] : 0.f;
-        }
-        const int n = step_of(step, first);
-        const size_t frame_stride = (fs && nframes > 1) ? fs[first] : 0;
-        e.packed = reinterpret_cast<char*>(lo) + static_cast<size_t>(first_frame) * frame_stride;
-        e.packed_frame_stride = frame_stride;
-        e.plane_frame_stride = s.dense_fs[first];
-        e.packed_pitch = static_cast<uint32_t>(pitch[first]);
-        e.plane_pitch = static_cast<uint32_t>(s.dense_pitch[first]);
-        e.width = static_cast<uint32_t>(s.w[first]);
-        e.rows = static_cast<uint32_t>(s.h[first]);
-        const uintptr_t a = lo | static_cast<uintptr_t>(pitch[first]) | static_cast<uintptr_t>(frame_stride);
-        e.unit = a % 16 == 0 ? 16u : a % 4 == 0 ? 4u : 0u;
-        const uint32_t lane_pixels = static_cast<uint32_t>(16 / dst_bytes);
-        // (a group with a channel missing stores sample by sample: only the given channels' samples may be stored to)
-        e.vec_pixels = (e.unit && members == n) ? e.width / lane_pixels * lane_pixels : 0u;
-        record_group(f, kNarrow, e, n, members, dst_bytes, scale || offset, first_frame);
-        NarrowArgs& a_n = by_step[n];
-        a_n.peak = peak;
-        a_n.g[a_n.ngroups++] = e;
-    }
-}
-}  // namespace
-
-// dst_scale / dst_offset (jinc_filter_process_device_narrowed_scaled; both nullptr: the unscaled call): the same stand-ins, the same
-// launches, the same report -- the narrowing kernel's scaled form takes fl32(fl32(r * scale) + offset) into the same conversion.
-void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
-                      void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift, int dst_bits,
-                      const size_t* dst_fs, int nframes, hipStream_t stream, const float* dst_scale, const float* dst_offset) {
-    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
-    t_last_groups.count = 0;
-    const size_t sb = static_cast<size_t>(f.vi_in.component_size), dst_bytes = dst_bits > 8 ? 2 : 1;
-    Side in, out;
-    for (int i = 0; i < f.planecount; ++i) {
-        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
-        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
-    }
-    // Every destination plane is a member of a group (groups_of_side gives a plane of step 1 a group of its own when it has a shift:
-    // here every plane counts as having one); planes of one pixel share a group by the strided call's rule, in destination samples.
-    static const int kEveryPlane[4] = {1, 1, 1, 1};
-    const void* dst_c[4] = {dst[0], dst[1], dst[2], dst[3]};
-    in.ngroups = groups_of_side(src, src_pitch, src_step, nullptr, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
-    out.ngroups = groups_of_side(dst_c, dst_pitch, dst_step, kEveryPlane, nframes > 1 ? dst_fs : nullptr, out.w, out.h, static_cast<int>(dst_bytes), f.planecount, out.group_of, out.channel_of);
-    check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
-    for (int i = 0; i < f.planecount; ++i) {  // (base alignment and the row's size: filter.cpp, in front of the device check)
-        if (!dst[i]) throw ArgError("JincResize: null plane pointer.");
-        if (dst_pitch[i] <= 0 || dst_pitch[i] % dst_bytes) throw ArgError("JincResize: destination pitch is not a multiple of the destination sample size.");
-        if (dst_fs && nframes > 1 && dst_fs[i] % dst_bytes) throw ArgError("JincResize: destination frame stride is not a multiple of the destination sample size.");
-    }
-    const float peak = static_cast<float>((1u << dst_bits) - 1u);
-    const bool scaled = dst_scale || dst_offset;
-    run_on_stand_ins(
-        f, in, out, src, src_pitch, src_fs, dst, dst_pitch, dst_fs, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) {
-            InterleaveArgs split[5];
-            const int recorded = t_last_groups.count;
-            fill_args(f, in, src, src_pitch, src_step, nullptr, src_fs, scratch, k0, slice, nframes, false, split);
-            int launches = 0;
-            for (int step = 2; step <= 4; ++step)
-                if (split[step].ngroups) {
-                    bool shifted = false;
-                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream, &shifted)), "split launch");
-                    record_shifted(recorded, kSplit, step, shifted, k0);
-                    ++launches;
-                }
-            return launches;
-        },
-        [&](char* scratch, int k0, int slice, int n) {
-            NarrowArgs narrow[5];
-            fill_narrow_args(f, out, dst, dst_pitch, dst_step, dst_shift, dst_scale, dst_offset, dst_fs, dst_bytes, peak, scratch, k0, slice, nframes, narrow);
-            int launches = 0;
-            for (int step = 1; step <= 4; ++step)
-                if (narrow[step].ngroups) {
-                    hip_check(static_cast<hipError_t>(jinc::launch_narrow_samples(narrow[step], f.sample_kind(), step, static_cast<int>(dst_bytes), n, stream, scaled)), "narrow launch");
-                    ++launches;
-                }
-            return launches;
-        });
-}
-
-// ---- jinc_filter_process_device_narrowed_packed10 / _v210: an fp32 / binary16 / bfloat16 filter's results into Y410 / RGB10A2 words and v210 blocks ----
-// The mirror image of enqueue_widened_packed10 / _v210: the destination is ONE group of the filter's three planes, as the packed side
-// of enqueue_packed10 or the v210 side of enqueue_v210, and every destination plane takes a dense stand-in of the FILTER's type;
-// narrow_fields_kernel / narrow_v210_kernel (kernel_narrow.hip) store lrintf(clamp(r, 0, 1023)) from them -- behind the scaled calls'
-// multiply and add where an array was given -- as whole words / blocks: ONE launch per slice, which the report counts as a merge
-// launch.  The source side and its split are enqueue_narrowed's, and everything else is run_on_stand_ins, so these calls alternate
-// with strided, shifted, packed10, v210, widened and narrowed ones on one filter.
-// Dense planes per frame of a 4K destination (rows padded to 256 bytes: 3840 x 4 = 15 360, 1920 x 4 = 3840 x 2 = 7680 and 1920 x 2 =
-// 3840 are multiples already), planar source: Y410 from fp32 3 x 15 360 x 2160 = 99 532 800 bytes, floor(1 073 741 824 /
-// 99 532 800) = 10 frames under the 1 GiB default; from binary16 / bfloat16 3 x 7680 x 2160 = 49 766 400 bytes, 21 frames.  v210 from
-// fp32 (15 360 + 2 x 7680) x 2160 = 66 355 200 bytes, 16 frames; from the 16-bit types (7680 + 2 x 3840) x 2160 = 33 177 600 bytes,
-// 32 frames.  All below kSliceFrames, so no rounding: a call of 128 runs as 12 x 10 + 8, 6 x 21 + 2, 8 x 16 and 4 x 32.
-namespace {
-// The sides of such a call: the source enqueue_narrowed's, the destination one group of three stand-ins.
-void narrowed_words_sides(const jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
-                          int nframes, Side& in, Side& out) {
-    for (int i = 0; i < f.planecount; ++i) {
-        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
-        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
-        out.group_of[i] = out.channel_of[i] = 0;
-    }
-    out.ngroups = 1;
-    in.ngroups = groups_of_side(src, src_pitch, src_step, nullptr, nframes > 1 ? src_fs : nullptr, in.w, in.h, f.vi_in.component_size, f.planecount, in.group_of, in.channel_of);
-    check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
-}
-// The split of such a call's source side (enqueue_narrowed's): planes with a step other than 1 into their stand-ins.
-int split_narrowed(const jinc_filter& f, const Side& in, const void* const src[4], const int src_pitch[4], const int* src_step,
-                   const size_t* src_fs, char* scratch, int k0, int slice, int n, int nframes, hipStream_t stream) {
-    InterleaveArgs split[5];
-    const int recorded = t_last_groups.count;
-    fill_args(f, in, src, src_pitch, src_step, nullptr, src_fs, scratch, k0, slice, nframes, false, split);
-    int launches = 0;
-    for (int step = 2; step <= 4; ++step)
-        if (split[step].ngroups) {
-            bool shifted = false;
-            hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], f.vi_in.component_size, step, n, stream, &shifted)), "split launch");
-            record_shifted(recorded, kSplit, step, shifted, k0);
-            ++launches;
-        }
-    return launches;
-}
-}  // namespace
-
-void enqueue_narrowed_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
-                               void* dst, int dst_pitch, const int* dst_fields, unsigned dst_fill, const float* dst_scale,
-                               const float* dst_offset, size_t dst_fs, int nframes, hipStream_t stream) {
-    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
-    t_last_groups.count = 0;
-    Side in, out;
-    narrowed_words_sides(f, src, src_pitch, src_step, src_fs, nframes, in, out);
-    check_packed10_side(dst, dst_pitch, &dst_fs, out, nframes);  // (filter.cpp has refused these already, with messages of this call's own)
-    // (every destination plane has a stand-in: run_on_stand_ins reads none of these)
-    void* const dst_planes[4] = {dst, dst, dst, nullptr};
-    const int dst_pitches[4] = {dst_pitch, dst_pitch, dst_pitch, 0};
-    const size_t dst_strides[4] = {dst_fs, dst_fs, dst_fs, 0};
-    const bool scaled = dst_scale || dst_offset;
-    run_on_stand_ins(
-        f, in, out, src, src_pitch, src_fs, dst_planes, dst_pitches, dst_strides, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) { return split_narrowed(f, in, src, src_pitch, src_step, src_fs, scratch, k0, slice, n, nframes, stream); },
-        [&](char* scratch, int k0, int slice, int n) {
-            jinc::NarrowFieldArgs a;
-            static_cast<jinc::FieldArgs&>(a) = field_args(out, dst, dst_pitch, dst_strides, dst_fields, dst_fill, scratch, k0, slice, nframes);
-            for (int c = 0; c < 3; ++c) a.value_scale[c] = dst_scale ? dst_scale[c] : 1.f, a.value_offset[c] = dst_offset ? dst_offset[c] : 0.f;
-            record_fields(f, kNarrowFields, a, k0, scaled);
-            hip_check(static_cast<hipError_t>(jinc::launch_narrow_fields(a, f.sample_kind(), n, stream, scaled)), "narrow fields launch");
-            return 1;
-        });
-}
-
-void enqueue_narrowed_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
-                           void* dst, int dst_pitch, const float* dst_scale, const float* dst_offset, size_t dst_fs, int nframes,
-                           hipStream_t stream) {
-    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
-    t_last_groups.count = 0;
-    Side in, out;
-    narrowed_words_sides(f, src, src_pitch, src_step, src_fs, nframes, in, out);
-    check_v210_side(dst, dst_pitch, &dst_fs, out, nframes);  // (filter.cpp has refused these already, with messages of this call's own)
-    void* const dst_planes[4] = {dst, dst, dst, nullptr};
-    const int dst_pitches[4] = {dst_pitch, dst_pitch, dst_pitch, 0};
-    const size_t dst_strides[4] = {dst_fs, dst_fs, dst_fs, 0};
-    const bool scaled = dst_scale || dst_offset;
-    run_on_stand_ins(
-        f, in, out, src, src_pitch, src_fs, dst_planes, dst_pitches, dst_strides, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) { return split_narrowed(f, in, src, src_pitch, src_step, src_fs, scratch, k0, slice, n, nframes, stream); },
-        [&](char* scratch, int k0, int slice, int n) {
-            jinc::NarrowV210Args a;
-            static_cast<jinc::V210Args&>(a) = v210_args(out, dst, dst_pitch, dst_strides, scratch, k0, slice, nframes);
-            for (int c = 0; c < 3; ++c) a.value_scale[c] = dst_scale ? dst_scale[c] : 1.f, a.value_offset[c] = dst_offset ? dst_offset[c] : 0.f;
-            record_v210(f, kNarrowV210, a, k0, scaled);
-            hip_check(static_cast<hipError_t>(jinc::launch_narrow_v210(a, f.sample_kind(), n, stream, scaled)), "narrow v210 launch");
-            return 1;
-        });
-}
-
-// ---- jinc_filter_process_device_shifted_packed10 / _v210_packed10: P010-style planes or v210 blocks in, Y410 / RGB10A2 words out ----
-// The source side of enqueue_strided (steps and shifts; planes of step 1 and shift 0 go to the kernels where they lie) or of
-// enqueue_v210 (ONE buffer of blocks), the destination side of enqueue_packed10 (ONE buffer of words, one group of the three result
-// stand-ins, pack_fields_kernel): no new pass, run_on_stand_ins composes the two.  For filters whose OUTPUT is 4:4:4
-// (jinc_filter_create_out): a decoder's P010 or a capture card's v210 leaves as Y410 in one call.  The filter, the offsets, steps
-// and shifts have been checked by filter.cpp.
-void enqueue_into_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
-                           bool src_is_v210, const size_t* src_fs, void* dst, int dst_pitch, const int* dst_fields, unsigned dst_fill,
-                           size_t dst_fs, int nframes, hipStream_t stream) {
-    t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
-    t_last_groups.count = 0;
-    const size_t sb = static_cast<size_t>(f.vi_in.component_size);
-    Side in, out;
-    for (int i = 0; i < f.planecount; ++i) {
-        f.plane_dims(f.vi_in, i, in.w[i], in.h[i]);
-        f.plane_dims(f.vi_out, i, out.w[i], out.h[i]);
-        out.group_of[i] = out.channel_of[i] = 0;
-        in.group_of[i] = in.channel_of[i] = src_is_v210 ? 0 : -1;
-    }
-    out.ngroups = 1;
-    if (src_is_v210) {
-        in.ngroups = 1;
-        check_v210_side(src[0], src_pitch[0], src_fs, in, nframes);
-    } else {
-        in.ngroups = groups_of_side(src, src_pitch, src_step, src_shift, nframes > 1 ? src_fs : nullptr, in.w, in.h, static_cast<int>(sb), f.planecount, in.group_of, in.channel_of);
-        check_strided_planes(f, src, src_pitch, src_step, src_fs, in, nframes);
-    }
-    check_packed10_side(dst, dst_pitch, &dst_fs, out, nframes);
-    void* const dst_planes[4] = {dst, dst, dst, nullptr};
-    const int dst_pitches[4] = {dst_pitch, dst_pitch, dst_pitch, 0};
-    const size_t dst_strides[4] = {dst_fs, dst_fs, dst_fs, 0};
-    run_on_stand_ins(
-        f, in, out, src, src_pitch, src_fs, dst_planes, dst_pitches, dst_strides, nframes, stream,
-        [&](char* scratch, int k0, int slice, int n) {
-            if (src_is_v210) {
-                const jinc::V210Args a = v210_args(in, src[0], src_pitch[0], src_fs, scratch, k0, slice, nframes);
-                record_v210(f, kUnpackV210, a, k0);
-                hip_check(static_cast<hipError_t>(jinc::launch_unpack_v210(a, n, stream)), "v210 unpack launch");
-                return 1;
-            }
-            InterleaveArgs split[5];
-            const int recorded = t_last_groups.count;
-            fill_args(f, in, src, src_pitch, src_step, src_shift, src_fs, scratch, k0, slice, nframes, false, split);
-            int launches = 0;
-            for (int step = 1; step <= 4; ++step)  // (step 1: shifted dense planes)
-                if (split[step].ngroups) {
-                    bool shifted = false;
-                    hip_check(static_cast<hipError_t>(jinc::launch_split_samples(split[step], static_cast<int>(sb), step, n, stream, &shifted)), "split launch");
-                    record_shifted(recorded, kSplit, step, shifted, k0);
-                    ++launches;
-                }
-            return launches;
-        },
-        [&](char* scratch, int k0, int slice, int n) {
-            const jinc::FieldArgs a = field_args(out, dst, dst_pitch, dst_strides, dst_fields, dst_fill, scratch, k0, slice, nframes);
-            record_fields(f, kPackFields, a, k0);
-            hip_check(static_cast<hipError_t>(jinc::launch_pack_fields(a, n, stream)), "pack launch");
-            return 1;
-        });
-}
 
 }  // namespace host
 }  // namespace jinc

@@ -52,41 +52,37 @@ const jinc::PlanePlan* table_or_null(const jinc_filter* f, int table) {
     return &f->plans[table];
 }
 
-// What the two widened calls for words and blocks refuse alike, behind the checks of the filter: the destination steps, then base,
-// pitch and frame stride of the one source buffer (`what`: "packed 10-bit words" / "v210 blocks"; row_bytes: what a row occupies).
-// Returns a message, empty when there is nothing to refuse.
-std::string refuse_widened_words(const jinc_filter* f, const char* what, const void* src, int src_pitch, size_t src_frame_stride,
-                                 size_t row_bytes, const char* row_text, const int* dst_sample_step, int nframes) {
-    for (int i = 0; dst_sample_step && i < f->planecount; ++i)
-        if (dst_sample_step[i] < 1 || dst_sample_step[i] > 4)
-            return "JincResize: destination sample step of a widened call for " + std::string(what) + " must be in 1..4 (got " +
-                   std::to_string(dst_sample_step[i]) + ").";
-    if (reinterpret_cast<uintptr_t>(src) % 4) return "JincResize: widened " + std::string(what) + " are not aligned to 4 bytes.";
-    if (src_pitch % 4) return "JincResize: pitch " + std::to_string(src_pitch) + " of widened " + what + " is not a multiple of 4.";
-    if (nframes > 1 && src_frame_stride % 4)
-        return "JincResize: frame stride " + std::to_string(src_frame_stride) + " of widened " + what + " is not a multiple of 4.";
-    if (src_pitch <= 0 || static_cast<size_t>(src_pitch) < row_bytes)
-        return "JincResize: pitch " + std::to_string(src_pitch) + " of widened " + what + " is smaller than the row's " + std::to_string(row_bytes) +
-               " bytes (" + row_text + ").";
+// What the widened and the narrowed calls for words and blocks refuse alike, behind the checks of the filter (and the offsets): the
+// steps of the OTHER side's planes, then base, pitch and frame stride of the one buffer.  `call` / `other`: "widened" / "destination",
+// "narrowed" / "source"; `what`: "packed 10-bit words" / "v210 blocks"; row_bytes: what a row occupies.  Returns a message, empty
+// when there is nothing to refuse.
+std::string refuse_words(const jinc_filter* f, const char* call, const char* other, const char* what, const void* buffer, int pitch,
+                         size_t frame_stride, size_t row_bytes, const char* row_text, const int* other_sample_step, int nframes) {
+    const std::string of_call = std::string(" of ") + call + " " + what;
+    for (int i = 0; other_sample_step && i < f->planecount; ++i)
+        if (other_sample_step[i] < 1 || other_sample_step[i] > 4)
+            return std::string("JincResize: ") + other + " sample step of a " + call + " call for " + what + " must be in 1..4 (got " +
+                   std::to_string(other_sample_step[i]) + ").";
+    if (reinterpret_cast<uintptr_t>(buffer) % 4) return std::string("JincResize: ") + call + " " + what + " are not aligned to 4 bytes.";
+    if (pitch % 4) return "JincResize: pitch " + std::to_string(pitch) + of_call + " is not a multiple of 4.";
+    if (nframes > 1 && frame_stride % 4) return "JincResize: frame stride " + std::to_string(frame_stride) + of_call + " is not a multiple of 4.";
+    if (pitch <= 0 || static_cast<size_t>(pitch) < row_bytes)
+        return "JincResize: pitch " + std::to_string(pitch) + of_call + " is smaller than the row's " + std::to_string(row_bytes) + " bytes (" + row_text + ").";
     return std::string();
 }
 
-// What the two narrowed calls for words and blocks refuse alike, behind the checks of the filter and the offsets: the source steps,
-// then base, pitch and frame stride of the one destination buffer (`what`: "packed 10-bit words" / "v210 blocks"; row_bytes: what a
-// row occupies).  Returns a message, empty when there is nothing to refuse.
-std::string refuse_narrowed_words(const jinc_filter* f, const char* what, const void* dst, int dst_pitch, size_t dst_frame_stride,
-                                  size_t row_bytes, const char* row_text, const int* src_sample_step, int nframes) {
-    for (int i = 0; src_sample_step && i < f->planecount; ++i)
-        if (src_sample_step[i] < 1 || src_sample_step[i] > 4)
-            return "JincResize: source sample step of a narrowed call for " + std::string(what) + " must be in 1..4 (got " +
-                   std::to_string(src_sample_step[i]) + ").";
-    if (reinterpret_cast<uintptr_t>(dst) % 4) return "JincResize: narrowed " + std::string(what) + " are not aligned to 4 bytes.";
-    if (dst_pitch % 4) return "JincResize: pitch " + std::to_string(dst_pitch) + " of narrowed " + what + " is not a multiple of 4.";
-    if (nframes > 1 && dst_frame_stride % 4)
-        return "JincResize: frame stride " + std::to_string(dst_frame_stride) + " of narrowed " + what + " is not a multiple of 4.";
-    if (dst_pitch <= 0 || static_cast<size_t>(dst_pitch) < row_bytes)
-        return "JincResize: pitch " + std::to_string(dst_pitch) + " of narrowed " + what + " is smaller than the row's " + std::to_string(row_bytes) +
-               " bytes (" + row_text + ").";
+// The three bit offsets of a 10:10:10:2 word (NULL: nothing to refuse here): each in 0..22, no two fields overlapping.  `word`:
+// "packed" / "widened packed" / "narrowed packed"; with_values: the message ends in the offending offsets.
+std::string refuse_fields(const char* word, const int* o, bool with_values) {
+    for (int i = 0; o && i < 3; ++i)
+        if (o[i] < 0 || o[i] > 22)
+            return std::string("JincResize: a field offset of a ") + word + " 10:10:10:2 word must be in 0..22" +
+                   (with_values ? " (got " + std::to_string(o[i]) + ")" : std::string()) + ".";
+    for (int i = 0; o && i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (o[i] - o[j] < 10 && o[j] - o[i] < 10)
+                return std::string("JincResize: two fields of a ") + word + " 10:10:10:2 word overlap" +
+                       (with_values ? " (offsets " + std::to_string(o[i]) + " and " + std::to_string(o[j]) + ")" : std::string()) + ".";
     return std::string();
 }
 
@@ -113,6 +109,39 @@ std::string refuse_scale_offset(const char* side, const float* scale, const floa
         if (offset && std::isinf(offset[i])) return "JincResize: the offset of " + of_plane + " is infinite.";
     }
     return std::string();
+}
+
+// One side of a stand-in call from the caller's arrays (any of them NULL: an empty side; the call is refused before it is read) ...
+SideSpec side_of_arrays(const jinc_filter* f, SideSpec::Form form, const void* const base[4], const int pitch[4], const size_t* frame_stride,
+                        const int* step = nullptr, const int* shift = nullptr) {
+    SideSpec s;
+    s.form = form, s.step = step, s.shift = shift;
+    for (int i = 0; base && pitch && i < f->planecount; ++i)
+        s.base[i] = base[i], s.pitch[i] = pitch[i], s.frame_stride[i] = frame_stride ? frame_stride[i] : 0;
+    return s;
+}
+// ... and from ONE buffer of words or blocks.
+SideSpec side_of_buffer(SideSpec::Form form, const void* buffer, int pitch, size_t frame_stride) {
+    SideSpec s;
+    s.form = form, s.base[0] = buffer, s.pitch[0] = pitch, s.frame_stride[0] = frame_stride;
+    return s;
+}
+SideSpec converting(SideSpec s, int bits, const float* scale, const float* offset) {
+    s.converts = true, s.bits = bits, s.scale = scale, s.offset = offset;
+    return s;
+}
+
+// What every stand-in call ends with, behind its own refusals: null argument, no device, nframes and frame strides, in this order,
+// then the call.  arrays_given: no array the call reads is NULL; strides_given: nor the frame strides of a side that has an array of them.
+int run_sides(jinc_filter* f, bool arrays_given, bool strides_given, const SideSpec& src, const SideSpec& dst, int nframes, void* hip_stream) {
+    if (!arrays_given) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
+    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
+    if (nframes > 1 && !strides_given) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
+    return guarded([&] {
+        hip_check(hipSetDevice(f->device), "hipSetDevice");
+        enqueue_sides(*f, src, dst, nframes, static_cast<hipStream_t>(hip_stream));  // (NULL stream: the HIP null stream)
+    });
 }
 }  // namespace
 
@@ -325,15 +354,9 @@ int jinc_filter_process_device_shifted(jinc_filter* f, const void* const src[4],
                 return fail(JINC_ERR_INVALID_ARG, "JincResize: sample shift is larger than the padding of the sample's container (" +
                                                       std::to_string(spare) + " bits).");
         }
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
-        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_strided(*f, src, src_pitch, src_sample_step, src_sample_shift, src_frame_stride, dst, dst_pitch, dst_sample_step,
-                        dst_sample_shift, dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
-    });
+    return run_sides(f, true, src_frame_stride && dst_frame_stride,
+                     side_of_arrays(f, SideSpec::Planes, src, src_pitch, src_frame_stride, src_sample_step, src_sample_shift),
+                     side_of_arrays(f, SideSpec::Planes, dst, dst_pitch, dst_frame_stride, dst_sample_step, dst_sample_shift), nframes, hip_stream);
 }
 
 int jinc_filter_process_device_packed10(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_field_offset[3],
@@ -352,24 +375,14 @@ int jinc_filter_process_device_packed10(jinc_filter* f, const void* const src[4]
         if (dst_field_offset && !jinc_filter::side_is_444(f->vi_out))
             return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "packed 10:10:10:2 words", "destination", "not sub-sampled (4:4:4)"));
         for (const int* o : {src_field_offset, dst_field_offset}) {
-            for (int i = 0; o && i < 3; ++i)
-                if (o[i] < 0 || o[i] > 22) return fail(JINC_ERR_INVALID_ARG, "JincResize: a field offset of a packed 10:10:10:2 word must be in 0..22.");
-            for (int i = 0; o && i < 3; ++i)
-                for (int j = i + 1; j < 3; ++j)
-                    if (o[i] - o[j] < 10 && o[j] - o[i] < 10)
-                        return fail(JINC_ERR_INVALID_ARG, "JincResize: two fields of a packed 10:10:10:2 word overlap.");
+            const std::string refusal = refuse_fields("packed", o, false);
+            if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
         }
     }
-    if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
-        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_packed10(*f, src, src_pitch, src_field_offset, src_frame_stride, dst, dst_pitch, dst_field_offset, dst_fill, dst_frame_stride,
-                         nframes, static_cast<hipStream_t>(hip_stream));
-    });
+    SideSpec in = side_of_arrays(f, src_field_offset ? SideSpec::Words10 : SideSpec::Planes, src, src_pitch, src_frame_stride);
+    SideSpec out = side_of_arrays(f, dst_field_offset ? SideSpec::Words10 : SideSpec::Planes, dst, dst_pitch, dst_frame_stride);
+    in.fields = src_field_offset, out.fields = dst_field_offset, out.fill = dst_fill;
+    return run_sides(f, src && dst && src_pitch && dst_pitch, src_frame_stride && dst_frame_stride, in, out, nframes, hip_stream);
 }
 
 int jinc_filter_process_device_v210(jinc_filter* f, const void* const src[4], const int src_pitch[4], int src_is_v210,
@@ -388,33 +401,20 @@ int jinc_filter_process_device_v210(jinc_filter* f, const void* const src[4], co
         if (dst_is_v210 && !jinc_filter::side_is_422(f->vi_out))
             return fail(JINC_ERR_INVALID_ARG, refuse_side(f, "v210 blocks", "destination", "4:2:2 (sub_w 1, sub_h 0)"));
     }
-    if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
-        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_v210(*f, src, src_pitch, src_is_v210 != 0, src_frame_stride, dst, dst_pitch, dst_is_v210 != 0, dst_frame_stride, nframes,
-                     static_cast<hipStream_t>(hip_stream));
-    });
+    return run_sides(f, src && dst && src_pitch && dst_pitch, src_frame_stride && dst_frame_stride,
+                     side_of_arrays(f, src_is_v210 ? SideSpec::V210 : SideSpec::Planes, src, src_pitch, src_frame_stride),
+                     side_of_arrays(f, dst_is_v210 ? SideSpec::V210 : SideSpec::Planes, dst, dst_pitch, dst_frame_stride), nframes, hip_stream);
 }
 
 namespace {
 // jinc_filter_process_device_shifted_packed10 / _v210_packed10: the filter and the offsets first (they need no device).
 // `says`: a message, empty when there is nothing to refuse.
 void refuse_into_packed10(const jinc_filter* f, bool src_is_v210, const int* dst_field_offset, std::string& says) {
-    says.clear();
     if (f->planecount != 3 || f->float_samples() || f->vi_in.component_size != 2 || f->vi_in.bits_per_component != 10)
         { says = "JincResize: a packed 10:10:10:2 destination needs a filter with three 10-bit components in 16-bit samples."; return; }
     if (src_is_v210 && !jinc_filter::side_is_422(f->vi_in)) { says = refuse_side(f, "v210 blocks", "source", "4:2:2 (sub_w 1, sub_h 0)"); return; }
     if (!jinc_filter::side_is_444(f->vi_out)) { says = refuse_side(f, "packed 10:10:10:2 words", "destination", "not sub-sampled (4:4:4)"); return; }
-    for (int i = 0; dst_field_offset && i < 3; ++i)
-        if (dst_field_offset[i] < 0 || dst_field_offset[i] > 22) { says = "JincResize: a field offset of a packed 10:10:10:2 word must be in 0..22."; return; }
-    for (int i = 0; dst_field_offset && i < 3; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (dst_field_offset[i] - dst_field_offset[j] < 10 && dst_field_offset[j] - dst_field_offset[i] < 10)
-                { says = "JincResize: two fields of a packed 10:10:10:2 word overlap."; return; }
+    says = refuse_fields("packed", dst_field_offset, false);
 }
 }  // namespace
 
@@ -433,15 +433,10 @@ int jinc_filter_process_device_shifted_packed10(jinc_filter* f, const void* cons
         if (src_sample_shift[i] > 6)
             return fail(JINC_ERR_INVALID_ARG, "JincResize: sample shift is larger than the padding of the sample's container (6 bits).");
     }
-    if (!src || !src_pitch || !dst || !dst_field_offset) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && !src_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_into_packed10(*f, src, src_pitch, src_sample_step, src_sample_shift, false, src_frame_stride, dst, dst_pitch, dst_field_offset,
-                              dst_fill, dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
-    });
+    SideSpec out = side_of_buffer(SideSpec::Words10, dst, dst_pitch, dst_frame_stride);
+    out.fields = dst_field_offset, out.fill = dst_fill;
+    return run_sides(f, src && src_pitch && dst && dst_field_offset, src_frame_stride != nullptr,
+                     side_of_arrays(f, SideSpec::Planes, src, src_pitch, src_frame_stride, src_sample_step, src_sample_shift), out, nframes, hip_stream);
 }
 
 int jinc_filter_process_device_v210_packed10(jinc_filter* f, const void* src, int src_pitch, size_t src_frame_stride, void* dst, int dst_pitch,
@@ -451,17 +446,9 @@ int jinc_filter_process_device_v210_packed10(jinc_filter* f, const void* src, in
     std::string refusal;
     refuse_into_packed10(f, true, dst_field_offset, refusal);
     if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
-    if (!src || !dst || !dst_field_offset) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        const void* const src_planes[4] = {src, src, src, nullptr};
-        const int src_pitches[4] = {src_pitch, src_pitch, src_pitch, 0};
-        const size_t src_strides[4] = {src_frame_stride, src_frame_stride, src_frame_stride, 0};
-        enqueue_into_packed10(*f, src_planes, src_pitches, nullptr, nullptr, true, src_strides, dst, dst_pitch, dst_field_offset, dst_fill,
-                              dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
-    });
+    SideSpec out = side_of_buffer(SideSpec::Words10, dst, dst_pitch, dst_frame_stride);
+    out.fields = dst_field_offset, out.fill = dst_fill;
+    return run_sides(f, src && dst && dst_field_offset, true, side_of_buffer(SideSpec::V210, src, src_pitch, src_frame_stride), out, nframes, hip_stream);
 }
 
 size_t jinc_v210_row_bytes(int width) { return v210_row_bytes(width); }
@@ -512,16 +499,9 @@ int process_device_widened(jinc_filter* f, const void* const src[4], const int s
     }
     const std::string refusal = refuse_scale_offset("source", src_scale, src_offset, f->planecount);
     if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
-    if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
-        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_widened(*f, src, src_pitch, src_sample_step, src_sample_shift, src_bits, src_frame_stride, dst, dst_pitch, dst_sample_step,
-                        dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream), src_scale, src_offset);
-    });
+    return run_sides(f, src && dst && src_pitch && dst_pitch, src_frame_stride && dst_frame_stride,
+                     converting(side_of_arrays(f, SideSpec::Planes, src, src_pitch, src_frame_stride, src_sample_step, src_sample_shift), src_bits, src_scale, src_offset),
+                     side_of_arrays(f, SideSpec::Planes, dst, dst_pitch, dst_frame_stride, dst_sample_step), nframes, hip_stream);
 }
 }  // namespace
 
@@ -581,16 +561,10 @@ int process_device_narrowed(jinc_filter* f, const void* const src[4], const int 
     }
     const std::string refusal = refuse_scale_offset("destination", dst_scale, dst_offset, f->planecount);
     if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
-    if (!src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && (!src_frame_stride || !dst_frame_stride))
-        return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_narrowed(*f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_sample_shift, dst_bits,
-                         dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream), dst_scale, dst_offset);
-    });
+    return run_sides(f, src && dst && src_pitch && dst_pitch, src_frame_stride && dst_frame_stride,
+                     side_of_arrays(f, SideSpec::Planes, src, src_pitch, src_frame_stride, src_sample_step),
+                     converting(side_of_arrays(f, SideSpec::Planes, dst, dst_pitch, dst_frame_stride, dst_sample_step, dst_sample_shift), dst_bits, dst_scale, dst_offset),
+                     nframes, hip_stream);
 }
 }  // namespace
 
@@ -650,30 +624,18 @@ int process_device_widened_packed10(jinc_filter* f, const void* src, int src_pit
         return fail(JINC_ERR_INVALID_ARG, "JincResize: widened packed 10:10:10:2 words need a float filter with three components and no sub-sampling "
                                           "(YUV444PS, YUV444PH, RGBPS, RGBPH); this filter has " + std::to_string(f->planecount) + " component(s), sub_w " +
                                               std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
-    for (int i = 0; src_field_offset && i < 3; ++i)
-        if (src_field_offset[i] < 0 || src_field_offset[i] > 22)
-            return fail(JINC_ERR_INVALID_ARG, "JincResize: a field offset of a widened packed 10:10:10:2 word must be in 0..22 (got " +
-                                                  std::to_string(src_field_offset[i]) + ").");
-    for (int i = 0; src_field_offset && i < 3; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (src_field_offset[i] - src_field_offset[j] < 10 && src_field_offset[j] - src_field_offset[i] < 10)
-                return fail(JINC_ERR_INVALID_ARG, "JincResize: two fields of a widened packed 10:10:10:2 word overlap (offsets " +
-                                                      std::to_string(src_field_offset[i]) + " and " + std::to_string(src_field_offset[j]) + ").");
+    std::string refusal = refuse_fields("widened packed", src_field_offset, true);
     int w = 0, h = 0;
     f->plane_dims(f->vi_in, 0, w, h);
-    std::string refusal = refuse_widened_words(f, "packed 10-bit words", src, src_pitch, src_frame_stride, 4 * static_cast<size_t>(w),
-                                               "4 * width", dst_sample_step, nframes);
+    if (refusal.empty())
+        refusal = refuse_words(f, "widened", "destination", "packed 10-bit words", src, src_pitch, src_frame_stride, 4 * static_cast<size_t>(w),
+                               "4 * width", dst_sample_step, nframes);
     if (refusal.empty()) refusal = refuse_scale_offset("packed 10-bit source", src_scale, src_offset, 3);
     if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
-    if (!src || !src_field_offset || !dst || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && !dst_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_widened_packed10(*f, src, src_pitch, src_field_offset, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_frame_stride,
-                                 nframes, static_cast<hipStream_t>(hip_stream), src_scale, src_offset);
-    });
+    SideSpec in = converting(side_of_buffer(SideSpec::Words10, src, src_pitch, src_frame_stride), 10, src_scale, src_offset);
+    in.fields = src_field_offset;
+    return run_sides(f, src && src_field_offset && dst && dst_pitch, dst_frame_stride != nullptr, in,
+                     side_of_arrays(f, SideSpec::Planes, dst, dst_pitch, dst_frame_stride, dst_sample_step), nframes, hip_stream);
 }
 }  // namespace
 
@@ -716,19 +678,13 @@ int process_device_widened_v210(jinc_filter* f, const void* src, int src_pitch, 
                                               std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
     int w = 0, h = 0;
     f->plane_dims(f->vi_in, 0, w, h);
-    std::string refusal = refuse_widened_words(f, "v210 blocks", src, src_pitch, src_frame_stride, v210_row_bytes(w), "16 * ceil(width / 6)",
-                                               dst_sample_step, nframes);
+    std::string refusal = refuse_words(f, "widened", "destination", "v210 blocks", src, src_pitch, src_frame_stride, v210_row_bytes(w),
+                                       "16 * ceil(width / 6)", dst_sample_step, nframes);
     if (refusal.empty()) refusal = refuse_scale_offset("v210 source", src_scale, src_offset, 3);
     if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
-    if (!src || !dst || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && !dst_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_widened_v210(*f, src, src_pitch, src_frame_stride, dst, dst_pitch, dst_sample_step, dst_frame_stride, nframes,
-                             static_cast<hipStream_t>(hip_stream), src_scale, src_offset);
-    });
+    return run_sides(f, src && dst && dst_pitch, dst_frame_stride != nullptr,
+                     converting(side_of_buffer(SideSpec::V210, src, src_pitch, src_frame_stride), 10, src_scale, src_offset),
+                     side_of_arrays(f, SideSpec::Planes, dst, dst_pitch, dst_frame_stride, dst_sample_step), nframes, hip_stream);
 }
 }  // namespace
 
@@ -763,30 +719,18 @@ int jinc_filter_process_device_narrowed_packed10(jinc_filter* f, const void* con
         return fail(JINC_ERR_INVALID_ARG, "JincResize: narrowed packed 10:10:10:2 words need a float filter with three components and no sub-sampling "
                                           "(YUV444PS, YUV444PH, RGBPS, RGBPH and their bfloat16 twins); this filter has " + std::to_string(f->planecount) +
                                               " component(s), sub_w " + std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
-    for (int i = 0; dst_field_offset && i < 3; ++i)
-        if (dst_field_offset[i] < 0 || dst_field_offset[i] > 22)
-            return fail(JINC_ERR_INVALID_ARG, "JincResize: a field offset of a narrowed packed 10:10:10:2 word must be in 0..22 (got " +
-                                                  std::to_string(dst_field_offset[i]) + ").");
-    for (int i = 0; dst_field_offset && i < 3; ++i)
-        for (int j = i + 1; j < 3; ++j)
-            if (dst_field_offset[i] - dst_field_offset[j] < 10 && dst_field_offset[j] - dst_field_offset[i] < 10)
-                return fail(JINC_ERR_INVALID_ARG, "JincResize: two fields of a narrowed packed 10:10:10:2 word overlap (offsets " +
-                                                      std::to_string(dst_field_offset[i]) + " and " + std::to_string(dst_field_offset[j]) + ").");
+    std::string refusal = refuse_fields("narrowed packed", dst_field_offset, true);
     int w = 0, h = 0;
     f->plane_dims(f->vi_out, 0, w, h);
-    std::string refusal = refuse_narrowed_words(f, "packed 10-bit words", dst, dst_pitch, dst_frame_stride, 4 * static_cast<size_t>(w), "4 * width",
-                                                src_sample_step, nframes);
+    if (refusal.empty())
+        refusal = refuse_words(f, "narrowed", "source", "packed 10-bit words", dst, dst_pitch, dst_frame_stride, 4 * static_cast<size_t>(w), "4 * width",
+                               src_sample_step, nframes);
     if (refusal.empty()) refusal = refuse_scale_offset("packed 10-bit destination", dst_scale, dst_offset, 3);
     if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
-    if (!src || !src_pitch || !dst || !dst_field_offset) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && !src_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_narrowed_packed10(*f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_field_offset, dst_fill, dst_scale,
-                                  dst_offset, dst_frame_stride, nframes, static_cast<hipStream_t>(hip_stream));
-    });
+    SideSpec out = converting(side_of_buffer(SideSpec::Words10, dst, dst_pitch, dst_frame_stride), 10, dst_scale, dst_offset);
+    out.fields = dst_field_offset, out.fill = dst_fill;
+    return run_sides(f, src && src_pitch && dst && dst_field_offset, src_frame_stride != nullptr,
+                     side_of_arrays(f, SideSpec::Planes, src, src_pitch, src_frame_stride, src_sample_step), out, nframes, hip_stream);
 }
 
 int jinc_filter_process_device_narrowed_v210(jinc_filter* f, const void* const src[4], const int src_pitch[4], const int src_sample_step[4],
@@ -806,19 +750,13 @@ int jinc_filter_process_device_narrowed_v210(jinc_filter* f, const void* const s
                                               " component(s), sub_w " + std::to_string(f->vi_in.sub_w) + " and sub_h " + std::to_string(f->vi_in.sub_h) + ".");
     int w = 0, h = 0;
     f->plane_dims(f->vi_out, 0, w, h);
-    std::string refusal = refuse_narrowed_words(f, "v210 blocks", dst, dst_pitch, dst_frame_stride, v210_row_bytes(w), "16 * ceil(width / 6)",
-                                                src_sample_step, nframes);
+    std::string refusal = refuse_words(f, "narrowed", "source", "v210 blocks", dst, dst_pitch, dst_frame_stride, v210_row_bytes(w),
+                                       "16 * ceil(width / 6)", src_sample_step, nframes);
     if (refusal.empty()) refusal = refuse_scale_offset("v210 destination", dst_scale, dst_offset, 3);
     if (!refusal.empty()) return fail(JINC_ERR_INVALID_ARG, refusal);
-    if (!src || !src_pitch || !dst) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
-    if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
-    if (nframes < 1 || nframes > 65535) return fail(JINC_ERR_INVALID_ARG, "JincResize: nframes must be in 1..65535.");
-    if (nframes > 1 && !src_frame_stride) return fail(JINC_ERR_INVALID_ARG, "JincResize: frame strides are required for nframes > 1.");
-    return guarded([&] {
-        hip_check(hipSetDevice(f->device), "hipSetDevice");
-        enqueue_narrowed_v210(*f, src, src_pitch, src_sample_step, src_frame_stride, dst, dst_pitch, dst_scale, dst_offset, dst_frame_stride,
-                              nframes, static_cast<hipStream_t>(hip_stream));
-    });
+    return run_sides(f, src && src_pitch && dst, src_frame_stride != nullptr,
+                     side_of_arrays(f, SideSpec::Planes, src, src_pitch, src_frame_stride, src_sample_step),
+                     converting(side_of_buffer(SideSpec::V210, dst, dst_pitch, dst_frame_stride), 10, dst_scale, dst_offset), nframes, hip_stream);
 }
 
 int jinc_packed10_layout(const char* name, int field_offset[3], unsigned* opaque_fill) {

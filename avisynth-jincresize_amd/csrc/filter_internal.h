@@ -1,7 +1,8 @@
 // filter_internal.h -- types and internal interfaces shared by the host translation units of libjincresize_hip.so:
 //   filter_args.cpp   Create_JincResize's argument handling and geometry derivation (configure)
 //   device_plan.cpp   device-resident plans: upload, launch planning for every kernel family (init_device)
-//   dispatch.cpp      per-call kernel selection and launches (enqueue; enqueue_strided: planes with a sample step; enqueue_packed10: 10:10:10:2 words; enqueue_v210: v210 blocks; enqueue_widened: integer samples into float / half filters; enqueue_widened_packed10 / _v210: 10:10:10:2 words and v210 blocks into them; enqueue_narrowed: their results into integer samples; enqueue_narrowed_packed10 / _v210: their results into 10:10:10:2 words and v210 blocks)
+//   dispatch.cpp      per-call kernel selection and launches (enqueue)
+//   stand_ins.cpp     enqueue for frames that do not lie as dense planes (enqueue_sides: sample steps and shifts, 10:10:10:2 words, v210 blocks, integer samples into / out of float filters)
 //   pipeline.cpp      frames in flight: device staging slots, pinned host ranges, H2D -> kernels -> D2H
 //   filter.cpp        the C ABI of include/jincresize_hip.h
 // Nothing here crosses the C ABI.
@@ -262,7 +263,7 @@ struct jinc_filter {
     static constexpr int kForkEvents = 16;
     hipEvent_t ev_fork[kForkEvents] = {}, ev_join[kForkEvents] = {};
     unsigned fork_turn = 0;
-    // jinc_filter_process_device_strided / _shifted / _packed10 / _v210 (dispatch.cpp run_on_stand_ins): the dense planes strided, shifted or packed ones are split into / merged from -- one allocation,
+    // jinc_filter_process_device_strided and the calls behind it (stand_ins.cpp run_on_stand_ins): the dense planes strided, shifted or packed ones are split into / merged from -- one allocation,
     // made on first use, grown when a call needs more -- and, because successive calls share them, an event behind each call's last
     // merge (a ring, as above) for the next call to wait on when it comes on another stream.
     void* strided_scratch = nullptr;
@@ -326,71 +327,31 @@ uint32_t direct_src_bytes(const void* base, uint64_t plane_bytes);
 void enqueue(jinc_filter& f, const void* const src[4], const int src_pitch[4], const size_t src_fs[4], void* const dst[4],
              const int dst_pitch[4], const size_t dst_fs[4], int nframes, hipStream_t stream);
 const char* last_interior_kernel_in_process();
-// ... enqueue for planes with a sample step and / or a sample shift (NULL step array: all ones; NULL shift array: all zeros; every
-// step 1 and every shift 0: enqueue itself).  The shifts have been checked against the format (filter.cpp).
-void enqueue_strided(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
-                     const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift,
-                     const size_t* dst_fs, int nframes, hipStream_t stream);
-// ... enqueue for sides that are ONE buffer of 10:10:10:2 words (fields: the three bit offsets in plane order, checked against the
-// filter by filter.cpp; NULL: that side is dense planes; both NULL: enqueue itself).  Of a packed side only base[0], pitch[0] and
-// frame stride [0] are read.  dst_fill: the bits of every stored word outside the fields.
-void enqueue_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_fields, const size_t* src_fs,
-                      void* const dst[4], const int dst_pitch[4], const int* dst_fields, unsigned dst_fill, const size_t* dst_fs,
-                      int nframes, hipStream_t stream);
-// ... enqueue for sides that are ONE buffer of v210 blocks (10-bit 4:2:2, six pixels in 16 bytes; the filter has been checked by
-// filter.cpp: YUV422P10).  A side whose flag is false is dense planes; both false: enqueue itself.  Of a v210 side only base[0],
-// pitch[0] and frame stride [0] are read.
-void enqueue_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], bool src_is_v210, const size_t* src_fs,
-                  void* const dst[4], const int dst_pitch[4], bool dst_is_v210, const size_t* dst_fs, int nframes, hipStream_t stream);
-// ... a strided / shifted source (enqueue_strided's source side) or ONE buffer of v210 blocks (src_is_v210: src[0], src_pitch[0] and
-// frame stride [0] are read) into ONE buffer of 10:10:10:2 words (enqueue_packed10's destination side).  Checked by filter.cpp.
-void enqueue_into_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
-                           bool src_is_v210, const size_t* src_fs, void* dst, int dst_pitch, const int* dst_fields, unsigned dst_fill,
-                           size_t dst_fs, int nframes, hipStream_t stream);
+void validate_planes(const jinc_filter& f, const void* const src[4], const int src_pitch[4], const size_t src_fs[4], void* const dst[4],
+                     const int dst_pitch[4], const size_t dst_fs[4], int nframes);  // what enqueue checks before it queues anything; throws ArgError
+// stand_ins.cpp: enqueue for device frames that do not lie as the filter's dense planes.  One side of such a call, as the caller gave
+// it and as filter.cpp has checked it against the filter (a destination's bases are written through):
+struct SideSpec {
+    enum Form {
+        Planes,   // planes with a sample step and / or a sample shift (NULL step array: all ones; NULL shift array: all zeros)
+        Words10,  // ONE buffer of 10:10:10:2 words: of base, pitch and frame_stride only [0] is read
+        V210      // ONE buffer of v210 blocks (10-bit 4:2:2, six pixels in 16 bytes): likewise
+    } form = Planes;
+    bool converts = false;  // INTEGER samples widened into (source) / narrowed from (destination) an fp32 / binary16 / bfloat16 filter
+    const void* base[4] = {nullptr, nullptr, nullptr, nullptr};
+    int pitch[4] = {0, 0, 0, 0};
+    size_t frame_stride[4] = {0, 0, 0, 0};  // as given (zeros for a NULL array); read for nframes > 1 only
+    const int* step = nullptr;              // Planes
+    const int* shift = nullptr;             // Planes: the padding below a sample in its word
+    int bits = 0;                           // Planes && converts: bits of an integer sample (8: bytes; 9 .. 16: 16-bit words)
+    const int* fields = nullptr;            // Words10: the three bit offsets in plane order
+    unsigned fill = 0;                      // Words10 destination: the bits of every stored word outside the fields
+    const float* scale = nullptr;           // converts: a scale and an offset per plane (the forms' arithmetic: stand_ins.cpp); either
+    const float* offset = nullptr;          // may be nullptr, both nullptr: the unscaled call -- same stand-ins, same launches, same report
+};
+// Both sides dense planes of the filter's own samples (Planes, every step 1, every shift 0): enqueue itself.
+void enqueue_sides(jinc_filter& f, const SideSpec& src, const SideSpec& dst, int nframes, hipStream_t stream);
 size_t v210_row_bytes(int width);  // 16 * ceil(width / 6); 0 for width < 1
-// ... enqueue on an fp32 / binary16 filter for INTEGER source samples of src_bytes (1 or 2) holding src_bits bits above `shift`:
-// every source plane is widened into a dense stand-in of the filter's sample type; the destination side is enqueue_strided's.
-// Filter, src_bits, steps, shifts, source bases and source pitches have been checked by filter.cpp.
-// src_scale / src_offset (four floats in plane order, either may be nullptr; both nullptr: the unscaled call): the stand-ins hold
-// fl32(fl32(float(value) * scale) + offset) rounded to the filter's type -- same stand-ins, same launches, same report.
-void enqueue_widened(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const int* src_shift,
-                     int src_bits, const size_t* src_fs, void* const dst[4], const int dst_pitch[4], const int* dst_step,
-                     const size_t* dst_fs, int nframes, hipStream_t stream, const float* src_scale = nullptr,
-                     const float* src_offset = nullptr);
-// ... enqueue on an fp32 / binary16 filter whose SOURCE is one buffer of 10:10:10:2 words (fields: the three bit offsets in plane
-// order) or of v210 blocks: the three source planes are widened into dense stand-ins of the filter's sample type
-// (widen_fields_kernel / widen_v210_kernel); the destination side is enqueue_strided's.  Filter, offsets, destination steps and the
-// source's base, pitch and frame stride have been checked by filter.cpp.
-// src_scale / src_offset (three floats in plane order -- v210: Y, Cb, Cr -- either may be nullptr; both nullptr: the unscaled call):
-// the stand-ins hold fl32(fl32(float(field) * scale) + offset) rounded to the filter's type, bfloat16 included -- same stand-ins,
-// same launches, same report (jinc_filter_process_device_widened_packed10_scaled / _widened_v210_scaled).
-void enqueue_widened_packed10(jinc_filter& f, const void* src, int src_pitch, const int* src_fields, size_t src_fs, void* const dst[4],
-                              const int dst_pitch[4], const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream,
-                              const float* src_scale = nullptr, const float* src_offset = nullptr);
-void enqueue_widened_v210(jinc_filter& f, const void* src, int src_pitch, size_t src_fs, void* const dst[4], const int dst_pitch[4],
-                          const int* dst_step, const size_t* dst_fs, int nframes, hipStream_t stream, const float* src_scale = nullptr,
-                          const float* src_offset = nullptr);
-// ... enqueue on an fp32 / binary16 / bfloat16 filter whose results go into INTEGER samples of dst_bits bits (8: bytes; 9 .. 16:
-// 16-bit words) at `shift` in their container: every destination plane takes a dense stand-in of the filter's sample type and
-// narrow_samples_kernel stores lrintf(clamp(r, 0, peak)) << shift from it; the source side is enqueue_strided's (no shifts).
-// Filter, dst_bits, steps, shifts, destination bases and destination pitches have been checked by filter.cpp.
-// dst_scale / dst_offset (as above): the stored sample is lrintf(clamp(fl32(fl32(r * scale) + offset), 0, peak)) << shift.
-void enqueue_narrowed(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
-                      void* const dst[4], const int dst_pitch[4], const int* dst_step, const int* dst_shift, int dst_bits,
-                      const size_t* dst_fs, int nframes, hipStream_t stream, const float* dst_scale = nullptr,
-                      const float* dst_offset = nullptr);
-// ... enqueue on an fp32 / binary16 / bfloat16 filter whose DESTINATION is one buffer of 10:10:10:2 words (fields: the three bit
-// offsets in plane order; fill: the bits outside them) or of v210 blocks: the three destination planes take dense stand-ins of the
-// filter's sample type and narrow_fields_kernel / narrow_v210_kernel store lrintf(clamp(r, 0, 1023)) -- behind the multiply and add
-// of dst_scale / dst_offset (three floats in plane order, either may be nullptr; both nullptr: the unscaled call) -- into the words
-// / blocks; the source side is enqueue_strided's (no shifts).  Filter, offsets, source steps, scales and the destination's base,
-// pitch and frame stride have been checked by filter.cpp.
-void enqueue_narrowed_packed10(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
-                               void* dst, int dst_pitch, const int* dst_fields, unsigned dst_fill, const float* dst_scale,
-                               const float* dst_offset, size_t dst_fs, int nframes, hipStream_t stream);
-void enqueue_narrowed_v210(jinc_filter& f, const void* const src[4], const int src_pitch[4], const int* src_step, const size_t* src_fs,
-                           void* dst, int dst_pitch, const float* dst_scale, const float* dst_offset, size_t dst_fs, int nframes,
-                           hipStream_t stream);
 // ... the channel groups of one side's planes (pure: test header jinc_debug_strided_groups); returns their number
 int strided_groups(const void* const base[4], const int pitch[4], const int* step, const size_t* frame_stride, const int width[4],
                    const int height[4], int component_size, int nplanes, int group_of[4], int channel_of[4]);
@@ -398,7 +359,7 @@ struct StridedReport {  // test header: jinc_debug_last_strided
     int split_launches = 0, merge_launches = 0, slices = 0;
     long long scratch_bytes = 0;
 };
-const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_strided / enqueue_packed10 / enqueue_v210 / enqueue_widened* / enqueue_narrowed*
+const StridedReport& last_strided_report();  // of the calling thread's most recent enqueue_sides
 // ... and the passes of that call's first slice as their launches got them (test header: jinc_debug_last_groups): the channel
 // groups of the widening / narrowing / split / merge launches and one entry per field or block pass, source side first, then the
 // destination side, each in the order of the groups' first planes (a side has at most one group per plane: 8 entries hold any
