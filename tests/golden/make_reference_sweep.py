@@ -149,7 +149,8 @@ def f32_bits(v):
     return struct.unpack("<I", struct.pack("<f", v))[0]
 
 
-def _case(name, fmt, src, dst, args=None, *, seed, opt=0, function="JincResize", nonfinite=None, gpu_only=False, family=None):
+def _case(name, fmt, src, dst, args=None, *, seed, opt=0, function="JincResize", nonfinite=None, nonfinite_kinds=None, gpu_only=False,
+          family=None):
     a = {k: (f32(v) if isinstance(v, float) else v) for k, v in (args or {}).items()}
     c = {"name": name, "format": fmt, "src": list(src), "dst": list(dst), "function": function, "args": a,
          "args_f32_bits": {k: f"{f32_bits(v):08x}" for k, v in a.items() if isinstance(v, float)},
@@ -158,6 +159,8 @@ def _case(name, fmt, src, dst, args=None, *, seed, opt=0, function="JincResize",
          "cpu_flags": (CPUF_SSE41 | CPUF_AVX2 | CPUF_AVX512F) if opt else 0}
     if nonfinite is not None:
         c["nonfinite_seed"] = nonfinite
+    if nonfinite_kinds is not None:
+        c["nonfinite_kinds"] = list(nonfinite_kinds)   # which of SPECIALS the frame carries (absent: all of them)
     if gpu_only:
         c["gpu_only"] = True      # recorded once at full size; the host tests neither regenerate nor recompute it
     if family:
@@ -328,6 +331,14 @@ def cases():
         out.append(_case(f"simd_opt{opt}_Y16_150x100_tap4", "Y16", (150, 100), (300, 200), dict(tap=4), seed=4242, opt=opt))
         out.append(_case(f"simd_opt{opt}_Y32_131x77", "Y32", (131, 77), (262, 154), {}, seed=4242, opt=opt))
         out.append(_case(f"simd_opt{opt}_YUV420PS_128x96_tap5", "YUV420PS", (128, 96), (200, 150), dict(tap=5, cplace="mpeg1"), seed=4242, opt=opt))
+    # NaN, -inf and denormals under the SIMD orders.  No +inf: the reference's vector loads read up to 15 samples to the right of
+    # the window and multiply them by the zero padding of the coefficient row, so a +inf there (0 x inf) makes the reference's own
+    # sample depend on memory outside the window; max_ps turns NaN and -inf into min_val before the multiply, wherever they lie.
+    for opt in (1, 2, 3):
+        out.append(_case(f"simd_opt{opt}_Y32_96x64_tap3_nan_neginf", "Y32", (96, 64), (192, 128), dict(tap=3), seed=41, opt=opt,
+                         nonfinite=7, nonfinite_kinds=NO_POS_INF))
+        out.append(_case(f"simd_opt{opt}_YUV444PS_90x62_tap4_nan_neginf", "YUV444PS", (90, 62), (135, 93), dict(tap=4), seed=42, opt=opt,
+                         nonfinite=8, nonfinite_kinds=NO_POS_INF))
     assert len({c["name"] for c in out}) == len(out)
     return out
 
@@ -335,14 +346,19 @@ def cases():
 # ------------------------------------------------------------------------------------------------------------------
 # running a case
 # ------------------------------------------------------------------------------------------------------------------
+SPECIALS = {"+inf": [np.inf], "-inf": [-np.inf], "nan": [np.nan], "denormal": [1e-41, -3e-39, 1.1e-38]}
+NO_POS_INF = ("-inf", "nan", "denormal")
+
+
 def source_frame(O, case):
-    """The seeded LCG frame of the case; `nonfinite_seed` scatters +inf, -inf, NaN and denormals over every plane."""
+    """The seeded LCG frame of the case; `nonfinite_seed` scatters +inf, -inf, NaN and denormals over every plane -- or, where the
+    case names them in `nonfinite_kinds`, only those kinds of SPECIALS."""
     fmt = O.FORMATS[case["format"]]
     sw, sh = case["src"]
     planes = O.lcg_frame(fmt, sw, sh, seed=case["seed"])
     if "nonfinite_seed" in case:
         rng = np.random.default_rng(case["nonfinite_seed"])
-        specials = np.array([np.inf, -np.inf, np.nan, 1e-41, -3e-39, 1.1e-38], np.float32)
+        specials = np.array([v for kind in case.get("nonfinite_kinds", SPECIALS) for v in SPECIALS[kind]], np.float32)
         for p, (pw, ph) in zip(planes, fmt.plane_dims(sw, sh)):
             for k in range(24):
                 p[int(rng.integers(0, ph)), int(rng.integers(0, pw))] = specials[k % len(specials)]

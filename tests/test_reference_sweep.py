@@ -93,11 +93,13 @@ def test_plugin_under_the_mock_host_gives_the_references_frames(host, gpu_pkg, O
 @pytest.mark.parametrize("opt", [1, 2, 3])
 def test_simd_orders_give_the_references_opt_frames(gpu_pkg, O, opt):
     """jinc_filter_set_simd_order(1 / 2 / 3) against the reference's SSE4.1 / AVX2 / AVX-512 frames (8-bit at C1's shape, 16-bit,
-    float, float 4:2:0)."""
+    float, float 4:2:0, and the two float rows whose frames carry NaN, -inf and denormals: the lower clamp turns NaN and -inf
+    into the plane's min_val, 0 on luma and -0.5 on chroma)."""
     rows = [r for r in ROWS if r["opt"] == opt]
-    assert len(rows) == 4
+    assert len(rows) == 6
     for row in rows:
         got, dims, out_dims, _ = abi_frame(gpu_pkg, O, row, simd_order=opt)
+        assert set(REACHED[row["name"]][0]) == {"ewa_simd_order_kernel"}, REACHED[row["name"]]
         assert out_dims == row["out_dims"]
         crcs = M.plane_crcs(got, dims)
         if crcs != row["crc32"]:

@@ -73,7 +73,7 @@ def test_fixture_rows_are_the_generators_cases():
     assert 85 <= len(ROWS) <= 110
     small = [r for r in ROWS if not r.get("gpu_only") and not r["opt"]]
     assert all(r["out_dims"][0] <= 400 and r["out_dims"][1] <= 260 for r in small)
-    assert sum(1 for r in ROWS if r["opt"]) == 12 and {r["opt"] for r in ROWS} == {0, 1, 2, 3}
+    assert sum(1 for r in ROWS if r["opt"]) == 18 and {r["opt"] for r in ROWS} == {0, 1, 2, 3}
 
 
 def test_small_cases_are_those_of_the_parity_suite():
@@ -149,6 +149,26 @@ def test_oracle_simd_orders_reproduce_the_reference_opt123(O, row):
             pytest.skip("simd_order.c order 3 checked; simd_avx512.c needs AVX-512, which this CPU lacks")
         out = of.get_frame_simd(3, src, threads=4, avx512=True)
         assert M.plane_crcs(out, of.out_dims()) == row["crc32"], first_difference(O, M.reference_library(), row, out, "simd_avx512.c")
+
+
+def test_simd_non_finite_rows_hold_what_they_are_for(O):
+    """Two rows per opt put NaN, -inf and denormals -- and no +inf, whose answer in the reference depends on memory to the right of
+    the window -- into every source plane; the recorded chroma crcs are not the luma clamp's: NaN and -inf become the plane's
+    min_val (0 on plane 0, -0.5 on planes 1 and 2), which simd_order.c reproduces above only with the right one."""
+    rows = [r for r in ROWS if r["opt"] and "nonfinite_seed" in r]
+    assert sorted((r["opt"], r["format"]) for r in rows) == [(o, f) for o in (1, 2, 3) for f in ("Y32", "YUV444PS")]
+    for row in rows:
+        assert row["nonfinite_kinds"] == list(M.NO_POS_INF)
+        of, src = oracle_frame(O, row)
+        assert {1: 7, 3: 9}[len(src)] == of.tables[0].filter_size   # tap 3 (an unrolled size of the kernel) and tap 4 at 1.5x
+        for p, (w, h) in zip(src, O.FORMATS[row["format"]].plane_dims(*row["src"])):
+            v = p[:h, :w]
+            assert not np.isposinf(v).any() and np.isneginf(v).any() and np.isnan(v).any()
+            assert ((np.abs(v) < np.float32(1.1754944e-38)) & (v != 0)).any()
+        if len(src) == 3:   # the clamp by plane kind is visible in these rows: chroma under the luma clamp gives another plane
+            wrong = O.alloc_plane(*of.out_dims()[1], np.float32)
+            of.tables[0].resize_simd(row["opt"], src[1], wrong, 0.0, threads=4)
+            assert M.plane_crc(wrong, *of.out_dims()[1]) != row["crc32"][1]
 
 
 def test_simd_rows_differ_from_opt0_where_the_orders_do(O):
