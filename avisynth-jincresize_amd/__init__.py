@@ -93,7 +93,7 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_set_pipeline_group", "jinc_filter_pipeline_group", "jinc_filter_flush", "jinc_filter_adopt_host_range", "jinc_filter_release_host_range", "jinc_batch_set_affinity", "jinc_batch_device_cpus", "jinc_debug_numa_cpus", "jinc_debug_batch_set_registrars", "jinc_debug_batch_refused", "jinc_debug_host_registrations", "jinc_debug_last_call", "jinc_filter_direct_premise", "jinc_debug_valu_pair_probe", "jinc_debug_clock_sampler_start", "jinc_debug_clock_sampler_stop",
            "jinc_filter_submit", "jinc_filter_wait", "jinc_shard_device", "jinc_batch_create", "jinc_batch_devices",
            "jinc_batch_device_of_frame", "jinc_batch_process", "jinc_batch_free", "jinc_batch_last_error",
-           "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share",
+           "jinc_filter_last_instance", "jinc_filter_last_finite_flags", "jinc_filter_last_border", "jinc_debug_last_instance", "jinc_debug_set_knob", "jinc_debug_clear_knob", "jinc_debug_get_knob", "jinc_debug_knob_name", "jinc_debug_chord_pattern", "jinc_debug_quad2_share", "jinc_debug_quad2_share_products",
            "jinc_filter_process_device_strided", "jinc_debug_strided_groups", "jinc_debug_last_strided", "jinc_debug_last_groups",
            "jinc_filter_process_device_shifted", "jinc_filter_process_device_packed10", "jinc_packed10_layout",
            "jinc_filter_process_device_v210", "jinc_v210_row_bytes", "jinc_filter_process_device_widened",
@@ -248,6 +248,9 @@ def lib():
         L.jinc_debug_chord_pattern.restype = C.c_int
         L.jinc_debug_quad2_share.argtypes = [C.c_void_p, C.c_void_p]
         L.jinc_debug_quad2_share.restype = C.c_int
+        if hasattr(L, "jinc_debug_quad2_share_products"):   # (JINC_LIB may name an older build: A/B runs)
+            L.jinc_debug_quad2_share_products.argtypes = [C.c_int]
+            L.jinc_debug_quad2_share_products.restype = C.c_int
         L.jinc_debug_knob_name.argtypes = [C.c_int]
         L.jinc_debug_knob_name.restype = C.c_char_p
         _lib = L

@@ -91,8 +91,11 @@ struct Rules {
     static constexpr bool kQuad8 = true;
     // two-periods-per-lane quad form on the trimmed 6 x 6 support from this many half-height workgroups per launch on
     static constexpr long long kQuad2MinWorkgroups = 256;
-    // ... and its half-height tiles (24 period-rows) below this many full-tile workgroups per launch
-    static constexpr long long kQuad2HalfTileMaxWorkgroups = 12000;  // (C2 at 16 frames: 734 against 718 Gpix/s; at 64: 803 against 827)
+    // ... and its half-height tiles below this many workgroups per launch, counted in units of 128 periods x 48 period rows (the
+    // window kernels' full tile; the quad2 instances' own tiles are 128 x 16 at half height, 128 x 32 at full height and 128 x 64 for
+    // 8-bit frame pairs: the unit is kept so that the threshold means the same amount of work for all of them, C2 from 35 frames on)
+    static constexpr long long kQuad2HalfTileMaxWorkgroups = 12000;  // (C2 at 16 frames: 734 against 718 Gpix/s; at 64: 803 against 827;
+                                                                     // 8-bit 128 x 64 tiles at 40 frames: level with 128 x 32, profiles/quad2_bf16_tile/)
     // fs-7 quad form from this many periods (2 x 2 pixels each) per plane on: 1080p -> 4K has 2.05 M, 360p -> 720p 0.22 M
     static constexpr long long kQuadMinPeriods = 1000000;
     // workgroups a quasi-periodic launch aims for when it splits a tile's phases (fs 9 tiles cost more to stage)
@@ -734,6 +737,7 @@ void launch_plane(jinc_filter& f, const Choice& c, int i, const void* const src[
                 }
                 if (quad) {
                     const int cols = pfs == 6 ? 128 : 64;  // periods per tile row
+                    // (a measure of the launch's work in tiles of 8 * pfs period rows, not the grid of the instance that runs: Rules)
                     const long long quad_wgs = static_cast<long long>((t.periodic.ni + cols - 1) / cols) * ((t.periodic.nj + 8 * pfs - 1) / (8 * pfs)) * nframes;
                     // (the quad forms' tile height follows from their own workgroup count alone -- the window kernels'
                     // half-tile rule above once left variant 2 standing under a chosen quad form)

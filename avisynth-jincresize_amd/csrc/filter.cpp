@@ -1419,6 +1419,14 @@ int jinc_debug_quad2_share(const float* sets, float* share_w) {
     const float* const phase_sets[4] = {sets, sets + 36, sets + 72, sets + 108};
     return jinc::quad2_share_classes(phase_sets, share_w) ? 1 : 0;
 }
+int jinc_debug_quad2_share_products(int strip_rows) {
+    switch (strip_rows) {
+        case 2: return jinc::quad2_share_products<2>();
+        case 8: return jinc::quad2_share_products<8>();
+        case 16: return jinc::quad2_share_products<16>();
+        default: return -1;
+    }
+}
 
 // Shader-clock sampler beside the kernels being timed (kernel_probe.hip).
 struct jinc_clock_sampler {

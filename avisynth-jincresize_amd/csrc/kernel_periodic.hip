@@ -1069,8 +1069,14 @@ __device__ __forceinline__ float frame_hi(f32x2 v) { return v.y; }
 // (v_pk_mul_f32 with the coefficient broadcast, v_pk_add_f32: each half is the per-frame chain, same order, un-fused) and leave to
 // drsrc and, when hi_ok, drsrc_hi.  ES: staged samples per tile word of type V (2: one frame's half of the frame-pair tile, read as floats
 // with `tile` pointing at that half of the first pair -- the half-tile instance, whose 80 VGPRs do not hold a window of pairs).
-template <typename T, typename Cfg, int NR, int NC, typename V = float, int ES = 1>
-__device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const PlaneIO& io, const V* tile, int tile_x, int j0, int wave, int lane,
+// W: the tile's word, V itself or the bf16 pair word of the 8-bit full tiles (quad2_pair_of rebuilds the f32 pair: same bits).
+__device__ __forceinline__ float quad2_pair_of(float v) { return v; }
+__device__ __forceinline__ f32x2 quad2_pair_of(f32x2 v) { return v; }
+__device__ __forceinline__ f32x2 quad2_pair_of(uint32_t v) {  // low half: the low frame's bf16, high half: the high frame's
+    return f32x2{__builtin_bit_cast(float, v << 16), __builtin_bit_cast(float, v & 0xffff0000u)};
+}
+template <typename T, typename Cfg, int NR, int NC, typename V = float, int ES = 1, typename W = V>
+__device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const PlaneIO& io, const W* tile, int tile_x, int j0, int wave, int lane,
                                                    BufferRsrc drsrc, BufferRsrc drsrc_hi, bool hi_ok) {
     constexpr bool kPair = !std::is_same_v<V, float>;
     constexpr int NCP = (NC + 3) & ~3;  // floats per coefficient row
@@ -1084,15 +1090,22 @@ __device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const 
         // The window: lane l reads the NC samples of tile row l, rows l + 1 .. l + NR - 1 come over from the lanes above by whole-wave
         // shifts (read from LDS, the lanes' rows lie a pitch apart: four banks for 64 lanes, a 16-way conflict per read.  Measured
         // level with this form all the same -- round5/edge_cols_ab.log -- the chains are what the edge tiles pay for).
-        static_assert(Cfg::kLdsRows <= 64, "one tile row per lane");
-        const V* wp = tile + ((lane < Cfg::kLdsRows ? lane : 0) * Cfg::kLdsPitch + a.edge.lds_col[s]) * ES;
+        // Tiles of 64 period rows (69 staged rows) have no lane above lane 63 to shift from: every lane reads its NR rows itself (the
+        // bf16 pair tile's rows lie 138 words apart, a two-way conflict): NR x NC LDS reads and two VALU instructions per pair to
+        // rebuild it, against NC reads and (NR - 1) x NC x 2 shifts.  Not measured on its own: the edge tiles' time is part of the
+        // interior kernel's, which was measured whole (profiles/quad2_bf16_tile/).
+        static_assert(Cfg::kLdsRows <= 64 || Cfg::kTileRows + NR - 1 <= Cfg::kLdsRows, "one tile row per lane");
+        const W* wp = tile + ((lane < Cfg::kLdsRows ? lane : 0) * Cfg::kLdsPitch + a.edge.lds_col[s]) * ES;
         V w[NR][NC];
 #pragma unroll
-        for (int lx = 0; lx < NC; ++lx) w[0][lx] = wp[lx * ES];
+        for (int lx = 0; lx < NC; ++lx) w[0][lx] = quad2_pair_of(wp[lx * ES]);
 #pragma unroll
         for (int ly = 1; ly < NR; ++ly)
 #pragma unroll
-            for (int lx = 0; lx < NC; ++lx) w[ly][lx] = wave_shl1(w[ly - 1][lx]);
+            for (int lx = 0; lx < NC; ++lx) {
+                if constexpr (Cfg::kLdsRows <= 64) w[ly][lx] = wave_shl1(w[ly - 1][lx]);
+                else w[ly][lx] = quad2_pair_of(wp[(ly * Cfg::kLdsPitch + lx) * ES]);
+            }
         const uint32_t row_off = static_cast<uint32_t>(a.iy0 + 2 * (j0 + lane) + q) * static_cast<uint32_t>(io.dst_pitch);
         for (int k0 = k_begin; k0 < k_end; k0 += 4) {  // wave-uniform
             const int nk = k_end - k0 < 4 ? k_end - k0 : 4;
@@ -1157,13 +1170,25 @@ __device__ __forceinline__ void quad2_edge_columns(const PeriodicArgs& a, const 
 // them out is exact for integer samples, see Quad2Cfg).  The last pair of an odd frame count stages the low frame twice and stores
 // it once.  Per output pair the per-frame form above issues 34 multiplies + 34 adds, strips of H = 2 (2 x 2-period blocks)
 // 21.9 + 31, strips of H = 8 15.5 + 31; a chain's first product opens it (quad2_share_adds), so one add of the 31 is not issued.
-//   Full tiles (RG 8, long batches): 128 x 32 periods, one strip of 8 period rows per wave, 37 staged rows of f32 pairs (40.9 KB of
+//   Full tiles (RG 8, long batches; 16-bit planes): 128 x 32 periods, one strip of 8 period rows per wave, 37 staged rows of f32 pairs (40.9 KB of
 // LDS: four workgroups per CU, as many as the 96 live accumulators leave waves per SIMD).  Its products come one class at a time,
 // the adds of each behind the next multiply: all of a sample's products at once would not fit beside the accumulators.
 //   Half tiles (RG 4, short batches): 128 x 16 periods, two strips of 2 period rows per wave (23.2 KB, six workgroups per CU), all
 // of a sample's products in front of their adds, so that no add waits on the multiply just issued.
-template <int H, int StripsPerWave, int MulLead>
+//   8-bit full tiles (Bf16): a sample 0 .. 255 is exact in bfloat16, and a bf16 over 16 zero bits is that sample's f32.  The tile
+// holds one 32-bit word per pair (the low frame's bf16 in the low half), 128 x 64 periods, one strip of 16 period rows per wave,
+// 69 staged rows in 38.1 KB: still four workgroups per CU, and the strip's end rows (their samples serve fewer period rows) are
+// paid once per 128 output pairs, 13.4 products per pair.  The walk reads each half with ds_read_u16_d16_hi into a register whose
+// low half was zeroed once (quad2_share_walk16): the window arrives as f32 pairs with no VALU instruction per sample.
+template <int H, int StripsPerWave, int MulLead, bool Bf16 = false>
 struct Quad2ShareTile {
+    static constexpr bool kBf16 = Bf16;
+    using Word = std::conditional_t<Bf16, uint32_t, f32x2>;  // one staged pair
+    using Half = std::conditional_t<Bf16, uint16_t, float>;  // one frame's half of it: the staging writes halves, frame f's at [2 * pair + f]
+    static __device__ __forceinline__ Half half_of(float v) {
+        if constexpr (Bf16) return static_cast<uint16_t>(__builtin_bit_cast(uint32_t, v) >> 16);
+        else return v;
+    }
     static constexpr int kTileCols = 128;                    // periods per tile row (Quad2Cfg's: the edge columns' tile_x)
     static constexpr int kStripRows = H;                     // period rows per strip
     static constexpr int kStripsPerWave = StripsPerWave;     // strips per lane, one below the other
@@ -1173,12 +1198,15 @@ struct Quad2ShareTile {
     static constexpr int kLdsSpare = 4;                      // pairs between the rows: what the staging's dwords hold beside the row,
     static constexpr int kLdsPitch = kLdsCols + kLdsSpare;   // and column -1 of the next row (pairs: rows 16-byte aligned)
     static constexpr int kLdsRows = kTileRows + 5;
-    static constexpr int kLdsFloats = 2 * (kLdsSpare + kLdsRows * kLdsPitch);  // the spare pairs in front of row 0 too
+    static constexpr int kLdsFloats = (Bf16 ? 1 : 2) * (kLdsSpare + kLdsRows * kLdsPitch);  // the spare pairs in front of row 0 too
     static_assert(kLdsPitch % 2 == 0 && kLdsSpare % 2 == 0, "16-byte aligned rows");
-    static_assert(8 * H <= 64, "a strip's outputs index one 64-bit mask");
+    static_assert(H <= Quad2ShareOuts::kMaxStripRows, "a strip's outputs index one Quad2ShareOuts");
+    static_assert(!Bf16 || (StripsPerWave == 1 && MulLead == 1), "quad2_share_walk16");
 };
-template <int RG>
-using Quad2ShareCfg = std::conditional_t<RG == 8, Quad2ShareTile<8, 1, 1>, Quad2ShareTile<2, 2, kQuad2ShareClasses>>;
+// Full tiles (RG 8) of 8-bit planes take the bf16 pair tile and strips of 16; 16-bit samples do not fit bf16.
+template <typename T, int RG>
+using Quad2ShareCfg = std::conditional_t<RG == 8, std::conditional_t<sizeof(T) == 1, Quad2ShareTile<16, 1, 1, true>, Quad2ShareTile<8, 1, 1>>,
+                                         Quad2ShareTile<2, 2, kQuad2ShareClasses>>;
 
 // Both launcher and kernel: does this launch of the integer kInnerTap3 instance (launched for plans with quad_share only) run the
 // frame-pair form?  The full-tile instance (RG 8: long batches) has no other body -- the per-frame form's window and tile would cost
@@ -1186,31 +1214,18 @@ using Quad2ShareCfg = std::conditional_t<RG == 8, Quad2ShareTile<8, 1, 1>, Quad2
 template <int RG>
 __host__ __device__ inline bool quad2_share_runs(const PlaneIO& io) { return RG == 8 || io.nframes > 1; }
 
-// The strip's outputs (bit 4 * oy + ox; oy = 2 * period row + q, ox = 2 * period column + p) that take sample (r, c) of its
-// 7-column x (H + 5)-row window with a coefficient of class k.
-template <int H>
-constexpr uint64_t quad2_share_outs(int r, int c, int k) {
-    uint64_t m = 0;
-    for (int oy = 0; oy < 2 * H; ++oy)
-        for (int ox = 0; ox < 4; ++ox) {
-            const int ly = r - (oy >> 1), lx = c - (ox >> 1);
-            if (ly < 0 || ly > 5 || lx < 0 || lx > 5) continue;
-            if (quad2_share_class(quad2_share_m(ox & 1, lx), quad2_share_m(oy & 1, ly)) == k) m |= uint64_t{1} << (4 * oy + ox);
-        }
-    return m;
-}
-
+// The strip's outputs that take sample (r, c) of its window with a coefficient of class k: kernels.h quad2_share_outs.
 // The outputs among quad2_share_outs(r, c, k) whose chain sample (r, c) opens: it is their first tap with a non-zero coefficient.
 template <int H>
-constexpr uint64_t quad2_share_opens(int r, int c, int k) {
-    const uint64_t outs = r < H ? quad2_share_outs<H>(r, c, k) : 0;
-    uint64_t m = 0;
-    for (int o = 8 * r; outs != 0 && o < 8 * r + 8; ++o) {  // period row r's outputs: their kernel row 0 is source row r
-        if (!((outs >> o) & 1u)) continue;
+constexpr Quad2ShareOuts quad2_share_opens(int r, int c, int k) {
+    const Quad2ShareOuts outs = r < H ? quad2_share_outs<H>(r, c, k) : Quad2ShareOuts{};
+    Quad2ShareOuts m;
+    for (int o = 8 * r; outs.any() && o < 8 * r + 8; ++o) {  // period row r's outputs: their kernel row 0 is source row r
+        if (!outs.has(o)) continue;
         const int p = o & 1, q = (o >> 2) & 1, lx = c - ((o & 3) >> 1);
         bool first = true;
         for (int l = 0; l < lx; ++l) first = first && quad2_share_class(quad2_share_m(p, l), quad2_share_m(q, 0)) < 0;
-        if (first) m |= uint64_t{1} << o;
+        if (first) m.set(o);
     }
     return m;
 }
@@ -1225,7 +1240,7 @@ static_assert(quad2_share_row0_opens(0, 0) && quad2_share_row0_opens(1, 0) && qu
 // Sample (R, C) times class K (the high / low half of SGPR pair K / 2, for both frames), where the strip needs that product.
 template <int H, int R, int C, int K>
 __device__ __forceinline__ void quad2_share_mul(f32x2& t, f32x2 s, const f32x2 (&w)[kQuad2ShareClasses / 2]) {
-    if constexpr (quad2_share_outs<H>(R, C, K) != 0) {
+    if constexpr (quad2_share_outs<H>(R, C, K).any()) {
         if constexpr (K & 1)
             asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(t) : "v"(s), "s"(w[K >> 1]));
         else
@@ -1240,15 +1255,15 @@ __device__ __forceinline__ void quad2_share_mul(f32x2& t, f32x2 s, const f32x2 (
 // do not run this body (quad2_share_instance).
 template <int H, int R, int C, int K>
 __device__ __forceinline__ void quad2_share_adds(f32x2 (&acc)[8 * H], f32x2 t) {
-    constexpr uint64_t outs = quad2_share_outs<H>(R, C, K), opens = quad2_share_opens<H>(R, C, K);
+    constexpr Quad2ShareOuts outs = quad2_share_outs<H>(R, C, K), opens = quad2_share_opens<H>(R, C, K);
 #pragma unroll
     for (int o = 0; o < 8 * H; ++o)
-        if constexpr (outs != 0)
-            if (((outs & ~opens) >> o) & 1u) asm("v_pk_add_f32 %0, %0, %1" : "+v"(acc[o]) : "v"(t));
+        if constexpr (outs.any())
+            if (outs.has(o) && !opens.has(o)) asm("v_pk_add_f32 %0, %0, %1" : "+v"(acc[o]) : "v"(t));
 #pragma unroll
     for (int o = 0; o < 8 * H; ++o)
-        if constexpr (opens != 0)
-            if ((opens >> o) & 1u) acc[o] = t;
+        if constexpr (opens.any())
+            if (opens.has(o)) acc[o] = t;
 }
 // Step K of a sample: the multiply of class K, then the adds of class K - kMulLead.
 template <typename Cfg, int R, int C, int K>
@@ -1285,10 +1300,58 @@ __device__ __forceinline__ void quad2_share_strip(f32x2 (&acc)[8 * Cfg::kStripRo
     ((quad2_share_row<Cfg, R>(acc, wb, w, std::make_integer_sequence<int, 7>{}), store(std::integral_constant<int, R - 5>{})), ...);
 }
 
+// The same walk over the bf16 pair tile.  Window column C lives in s[C]: two registers whose low halves are zero from the start of the
+// strip and stay zero -- ds_read_u16_d16_hi writes the high half and keeps the low one (or, on parts with SRAM ECC, writes zero
+// there: the same thing here, and the only value of the low half this code may rely on) -- each register is the sample's f32 as loaded.
+// What the compiler does not know: between the load asm and the matching s_waitcnt asm, up to a row later, s[C] is NOT yet defined,
+// although the asm's output says so.  A copy, a re-pairing move or a spill of s[C] placed in between would read stale data without any
+// warning.  Today's listing has none (the only moves of the walk zero the registers, in front of the first wait; every wait is one of
+// these); tests/test_quad2_bf16_tile.py holds the listing to that, and the GPU tests compare every byte.  Sample
+// (R + 1, C) is loaded into s[C] behind the last product of sample (R, C), so 14 loads are in flight all the time and sample (R, C)
+// waits for its own two only: LDS loads return in order, and the twelve issued behind them are columns C + 1 .. 6 of row R and columns
+// 0 .. C - 1 of row R + 1 (none of the latter in the last row).  The compiler does not count loads issued by inline assembly, hence the
+// s_waitcnt here; whatever else is in flight on that counter only makes the wait longer.
+template <typename Cfg, int R, int C>
+__device__ __forceinline__ void quad2_share_load16(float (&s)[2], uint32_t at) {
+    constexpr int off = 4 * (R * Cfg::kLdsPitch + C);
+    static_assert(off + 2 < 65536, "the offset field");
+    asm volatile("ds_read_u16_d16_hi %0, %2 offset:%3\n\tds_read_u16_d16_hi %1, %2 offset:%4"
+                 : "+v"(s[0]), "+v"(s[1])
+                 : "v"(at), "n"(off), "n"(off + 2)
+                 : "memory");
+}
+template <typename Cfg, int R, int C>
+__device__ __forceinline__ void quad2_share_sample16(f32x2 (&acc)[8 * Cfg::kStripRows], float (&s)[7][2], uint32_t at,
+                                                     const f32x2 (&w)[kQuad2ShareClasses / 2]) {
+    constexpr bool last = R == Cfg::kStripRows + 4;
+    constexpr int behind = 2 * ((6 - C) + (last ? 0 : C));
+    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(s[C][0]), "+v"(s[C][1]) : "n"(behind));
+    quad2_share_sample<Cfg, R, C>(acc, f32x2{s[C][0], s[C][1]}, w, std::make_integer_sequence<int, kQuad2ShareClasses + Cfg::kMulLead>{});
+    if constexpr (!last) quad2_share_load16<Cfg, R + 1, C>(s[C], at);
+}
+template <typename Cfg, int R, int... C>
+__device__ __forceinline__ void quad2_share_row16(f32x2 (&acc)[8 * Cfg::kStripRows], float (&s)[7][2], uint32_t at,
+                                                  const f32x2 (&w)[kQuad2ShareClasses / 2], std::integer_sequence<int, C...>) {
+    (quad2_share_sample16<Cfg, R, C>(acc, s, at, w), ...);
+}
+template <typename Cfg, int... C>
+__device__ __forceinline__ void quad2_share_open16(float (&s)[7][2], uint32_t at, std::integer_sequence<int, C...>) {
+    (quad2_share_load16<Cfg, 0, C>(s[C], at), ...);
+}
+template <typename Cfg, int... R, typename Store>
+__device__ __forceinline__ void quad2_share_walk16(f32x2 (&acc)[8 * Cfg::kStripRows], const uint32_t* wb, const f32x2 (&w)[kQuad2ShareClasses / 2],
+                                                   std::integer_sequence<int, R...>, Store&& store) {
+    const uint32_t at = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) uint32_t*)wb));
+    float s[7][2] = {};
+    quad2_share_open16<Cfg>(s, at, std::make_integer_sequence<int, 7>{});
+    ((quad2_share_row16<Cfg, R>(acc, s, at, w, std::make_integer_sequence<int, 7>{}), store(std::integral_constant<int, R - 5>{})), ...);
+}
+
 template <typename T, int RG>
 __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const PlaneIO& io, float* lds) {
-    using Cfg = Quad2ShareCfg<RG>;
-    f32x2* const tile = reinterpret_cast<f32x2*>(lds) + Cfg::kLdsSpare;
+    using Cfg = Quad2ShareCfg<T, RG>;
+    using Word = typename Cfg::Word;
+    Word* const tile = reinterpret_cast<Word*>(lds) + Cfg::kLdsSpare;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int tile_x, tile_y;
@@ -1299,7 +1362,7 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
     const bool f1_ok = f0 + 1 < static_cast<size_t>(io.nframes);  // the last pair of an odd count: the high half repeats the low frame
     const size_t f1 = f1_ok ? f0 + 1 : f0;
     const bool edge_tile = edge_tile_of<T>(a, tile_x);
-    {   // Stage both frames' source tiles as f32 pairs, all loads in front of the LDS writes (see ewa_periodic_kernel).  A lane loads
+    {   // Stage both frames' source tiles as pairs (f32, or the high halves of the f32: Cfg::half_of), all loads in front of the LDS writes (see ewa_periodic_kernel).  A lane loads
         // the aligned dword(s) that hold four samples of a row, through a descriptor over the frame's plane (widened to whole dwords:
         // an aligned dword lies in one page, and a dword past the plane's last one reads as zero), the row's offset in an SGPR.  The
         // dword that holds the tile's first sample starts up to three samples in front of it: the row lands that far to the left in
@@ -1334,7 +1397,8 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
                 for (int k = 0; k < kDwords; ++k) d[i][f][k] = __builtin_amdgcn_raw_buffer_load_b32(f ? rs1 : rs0, voff + 4u * k, so & ~3u, 0);
             }
         }
-        float* const tf = reinterpret_cast<float*>(tile) + 8 * lane;
+        // (the lane's first pair as a pointer of its own: what indexes it below is wave-uniform and stays in SGPRs)
+        typename Cfg::Half* const tf = reinterpret_cast<typename Cfg::Half*>(tile) + 8 * lane;
         auto sample = [&](int i, int f, int b) {
             if constexpr (sizeof(T) == 1) return static_cast<float>((d[i][f][0] >> (8 * b)) & 0xffu);
             else return static_cast<float>((d[i][f][b >> 1] >> (16 * (b & 1))) & 0xffffu);
@@ -1345,7 +1409,7 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
                 const int r = wave + 4 * i;
                 if (r >= Cfg::kLdsRows) continue;  // wave-uniform
 #pragma unroll
-                for (int f = 0; f < 2; ++f) tf[2 * (r * Cfg::kLdsPitch - shift[i][f]) + f] = sample(i, f, 0);
+                for (int f = 0; f < 2; ++f) tf[2 * (r * Cfg::kLdsPitch - shift[i][f]) + f] = Cfg::half_of(sample(i, f, 0));
             }
         }
         if (lane < kLoadLanes - 1) {
@@ -1356,13 +1420,13 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
 #pragma unroll
                 for (int f = 0; f < 2; ++f)
 #pragma unroll
-                    for (int b = 1; b < 4; ++b) tf[2 * (r * Cfg::kLdsPitch - shift[i][f] + b) + f] = sample(i, f, b);
+                    for (int b = 1; b < 4; ++b) tf[2 * (r * Cfg::kLdsPitch - shift[i][f] + b) + f] = Cfg::half_of(sample(i, f, b));
             }
         }
         // The tile column that reaches past the plane's last column: those columns replicate it (the dwords held the pitch's padding, the
         // next row or zero there).  Behind the writes above, by the wave that wrote the row.
         if (gx0 + Cfg::kLdsCols > a.src_w) {  // workgroup-uniform
-            float* const tr = reinterpret_cast<float*>(tile);
+            typename Cfg::Half* const tr = reinterpret_cast<typename Cfg::Half*>(tile);
 #pragma unroll
             for (int i = 0; i < kRowsPerWave; ++i) {
                 const int r = wave + 4 * i;
@@ -1375,8 +1439,8 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
                 for (int k = 0; k < (Cfg::kLdsCols + 63) / 64; ++k) {
                     const int c = lane + 64 * k;
                     if (gx0 + c >= a.src_w && c < Cfg::kLdsCols) {
-                        tr[2 * (r * Cfg::kLdsPitch + c)] = v0;
-                        tr[2 * (r * Cfg::kLdsPitch + c) + 1] = v1;
+                        tr[2 * (r * Cfg::kLdsPitch + c)] = Cfg::half_of(v0);
+                        tr[2 * (r * Cfg::kLdsPitch + c) + 1] = Cfg::half_of(v1);
                     }
                 }
             }
@@ -1384,12 +1448,14 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
         // an edge window that starts one column in front of the tile: that column into the pair in front of each row (stage_edge_column)
         const bool in_front = edge_tile && ((a.edge.n[0] > 0 && tile_x == a.edge.tile_x[0] && a.edge.lds_col[0] < 0) ||
                                             (a.edge.n[1] > 0 && tile_x == a.edge.tile_x[1] && a.edge.lds_col[1] < 0));
-        if (in_front && wave == 0 && lane < Cfg::kLdsRows && gx0 > 0) {
-            int gy = gy0 + lane;
+        constexpr int kFrontWaves = (Cfg::kLdsRows + 63) / 64;  // a lane per tile row: wave 0 alone up to 64 staged rows
+        const int fr = kFrontWaves == 1 ? lane : lane + 64 * wave;
+        if (in_front && (kFrontWaves == 1 ? wave == 0 : wave < kFrontWaves) && fr < Cfg::kLdsRows && gx0 > 0) {
+            int gy = gy0 + fr;
             gy = gy < a.src_h ? gy : a.src_h - 1;
-            float* const tc = reinterpret_cast<float*>(tile + lane * Cfg::kLdsPitch - 1);
-            tc[0] = to_float(reinterpret_cast<const T*>(sb0 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1]);
-            tc[1] = to_float(reinterpret_cast<const T*>(sb1 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1]);
+            typename Cfg::Half* const tc = reinterpret_cast<typename Cfg::Half*>(tile + fr * Cfg::kLdsPitch - 1);
+            tc[0] = Cfg::half_of(to_float(reinterpret_cast<const T*>(sb0 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1]));
+            tc[1] = Cfg::half_of(to_float(reinterpret_cast<const T*>(sb1 + static_cast<size_t>(gy) * io.src_pitch)[gx0 - 1]));
         }
     }
     __syncthreads();
@@ -1398,7 +1464,7 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
     const BufferRsrc d1 = make_rsrc(static_cast<char*>(io.dst) + f1 * io.dst_frame_stride, plane_bytes);
     if (edge_tile) {
         if constexpr (RG == 8) {
-            quad2_edge_columns<T, Cfg, 6, 7, f32x2>(a, io, tile, tile_x, j0, wave, lane, d0, d1, f1_ok);
+            quad2_edge_columns<T, Cfg, 6, 7, f32x2, 1, Word>(a, io, tile, tile_x, j0, wave, lane, d0, d1, f1_ok);
         } else {
             quad2_edge_columns<T, Cfg, 6, 7, float, 2>(a, io, reinterpret_cast<const float*>(tile), tile_x, j0, wave, lane, d0, d0, false);
             if (f1_ok) quad2_edge_columns<T, Cfg, 6, 7, float, 2>(a, io, reinterpret_cast<const float*>(tile) + 1, tile_x, j0, wave, lane, d1, d1, false);
@@ -1414,9 +1480,9 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
     for (int st = 0; st < Cfg::kStripsPerWave; ++st) {
         const int jb = Cfg::kStripRows * (wave * Cfg::kStripsPerWave + st);  // the strip's first period row in the tile
         if (j0 + jb >= a.nj) break;                                          // wave-uniform: bottom tiles
-        const f32x2* wb = tile + jb * Cfg::kLdsPitch + 2 * lane;
+        const Word* wb = tile + jb * Cfg::kLdsPitch + 2 * lane;
         f32x2 acc[8 * Cfg::kStripRows];
-        quad2_share_strip<Cfg>(acc, wb, w, std::make_integer_sequence<int, Cfg::kStripRows + 5>{}, [&](auto PR) {
+        auto store = [&](auto PR) {
             constexpr int pr = decltype(PR)::value;
             if constexpr (pr >= 0) {
                 const int j = j0 + jb + pr;
@@ -1430,7 +1496,9 @@ __device__ __forceinline__ void quad2_share_body(const PeriodicArgs& a, const Pl
                     }
                 }
             }
-        });
+        };
+        if constexpr (Cfg::kBf16) quad2_share_walk16<Cfg>(acc, wb, w, std::make_integer_sequence<int, Cfg::kStripRows + 5>{}, store);
+        else quad2_share_strip<Cfg>(acc, wb, w, std::make_integer_sequence<int, Cfg::kStripRows + 5>{}, store);
     }
 }
 
@@ -1453,7 +1521,7 @@ __global__ __launch_bounds__(256, (quad2_share_instance<T, INNER, NT>() && RG ==
     // (two words in front of the tile: row 0's "column -1", see the edge columns below; the tile stays 8-byte aligned)
     // The frame-pair form (quad2_share_body) of the integer kInnerTap3 instances stages its tile into the same words.
     constexpr bool kShare = quad2_share_instance<T, INNER, NT>();
-    using ShareCfg = Quad2ShareCfg<RG>;
+    using ShareCfg = Quad2ShareCfg<T, RG>;
     constexpr int kWords = 2 + Cfg::kLdsRows * Cfg::kLdsPitch;
     if constexpr (kShare && RG == 8) {  // (what follows is dead code here: neither its registers nor its tile are allocated)
         __shared__ __attribute__((aligned(16))) float share_words[ShareCfg::kLdsFloats];
@@ -2110,7 +2178,7 @@ int launch_periodic_quad2_t(const PeriodicArgs& pa, const PlaneIO& io, hipStream
         bool share = false;
         if constexpr (!is_float_sample_v<T>) share = true;
         if (share && pa.quad_share) {  // integer planes: the frame-pair form, on tiles of its own (quad2_share_body)
-            using ShareCfg = Quad2ShareCfg<RG>;
+            using ShareCfg = Quad2ShareCfg<T, RG>;
             if (quad2_share_runs<RG>(io))
                 grid = dim3((pa.ni + ShareCfg::kTileCols - 1) / ShareCfg::kTileCols, (pa.nj + ShareCfg::kTileRows - 1) / ShareCfg::kTileRows,
                             (io.nframes + 1) / 2);

@@ -106,6 +106,41 @@ constexpr int quad2_share_class(int mx, int my) {
 static_assert(quad2_share_class(4, 4) == kQuad2ShareClasses - 1 && quad2_share_class(5, 2) == 14 && quad2_share_class(3, 5) < 0 &&
                   quad2_share_m(0, 2) == 0 && quad2_share_m(1, 3) == 0 && quad2_share_m(0, 5) == 5 && quad2_share_m(1, 0) == 5,
               "class numbering");
+// The frame-pair form walks strips 2 periods across and H period rows down (kernel_periodic.hip quad2_share_body).  A set of the strip's
+// outputs: bit 4 * oy + ox, oy = 2 * period row + q, ox = 2 * period column + p.
+struct Quad2ShareOuts {
+    static constexpr int kMaxStripRows = 16;
+    uint64_t w[kMaxStripRows / 8] = {};
+    constexpr bool any() const {
+        for (uint64_t v : w)
+            if (v != 0) return true;
+        return false;
+    }
+    constexpr bool has(int o) const { return ((w[o >> 6] >> (o & 63)) & 1u) != 0; }
+    constexpr void set(int o) { w[o >> 6] |= uint64_t{1} << (o & 63); }
+};
+// The strip's outputs that take sample (r, c) of its 7-column x (H + 5)-row window with a coefficient of class k.
+template <int H>
+constexpr Quad2ShareOuts quad2_share_outs(int r, int c, int k) {
+    static_assert(H <= Quad2ShareOuts::kMaxStripRows, "a strip's outputs index the words of one Quad2ShareOuts");
+    Quad2ShareOuts m;
+    for (int oy = 0; oy < 2 * H; ++oy)
+        for (int ox = 0; ox < 4; ++ox) {
+            const int ly = r - (oy >> 1), lx = c - (ox >> 1);
+            if (ly < 0 || ly > 5 || lx < 0 || lx > 5) continue;
+            if (quad2_share_class(quad2_share_m(ox & 1, lx), quad2_share_m(oy & 1, ly)) == k) m.set(4 * oy + ox);
+        }
+    return m;
+}
+// Products per strip and frame pair: the (sample, class) pairs some output of the strip takes, one v_pk_mul_f32 each.
+template <int H>
+constexpr int quad2_share_products() {
+    int n = 0;
+    for (int r = 0; r < H + 5; ++r)
+        for (int c = 0; c < 7; ++c)
+            for (int k = 0; k < kQuad2ShareClasses; ++k) n += quad2_share_outs<H>(r, c, k).any() ? 1 : 0;
+    return n;
+}
 struct PeriodicArgs {
     const float* coeffs = nullptr;
     int px = 1, py = 1;

@@ -173,6 +173,9 @@ JINC_API int jinc_debug_chord_pattern(int taps_per_row, uint64_t spans);
  * sets of the trimmed support, set (p, q) at sets + 36 * (2 * q + p).  Returns 1 and the 18 class coefficients in share_w if every tap
  * equals its class's coefficient bit for bit and every tap outside the disc is 0.0f, else 0.  Host only: no device call. */
 JINC_API int jinc_debug_quad2_share(const float *sets, float *share_w);
+/* Products (v_pk_mul_f32) per strip of `strip_rows` period rows in that form's walk: the (source sample, class) pairs of the strip's
+ * 7-column x (strip_rows + 5)-row window that some output of the strip takes.  -1 for a strip height no instance walks (2, 8, 16 do). */
+JINC_API int jinc_debug_quad2_share_products(int strip_rows);
 JINC_API const char *jinc_debug_knob_name(int knob);        /* lower-case name ("quad_rg"); NULL beyond the last knob */
 /* Taps per axis the periodic interior kernels of `table` execute under the current kernel mode: the plan's filter size, or
  * the side of the trimmed support on integer planes (kernel mode 15 switches trimming off); 0 when the table has no
