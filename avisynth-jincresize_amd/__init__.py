@@ -106,7 +106,7 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_process_device_widened_packed10_scaled", "jinc_filter_process_device_widened_v210_scaled",
            "jinc_debug_widen_fields", "jinc_debug_widen_v210",
            "jinc_filter_create_out", "jinc_batch_create_out",
-           "jinc_filter_process_device_shifted_packed10", "jinc_filter_process_device_v210_packed10"]
+           "jinc_filter_process_device_shifted_packed10", "jinc_filter_process_device_v210_packed10", "jinc_debug_plane_extent_check"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -159,6 +159,8 @@ def lib():
         L.jinc_debug_strided_groups.argtypes = [_P4, _I4, C.c_void_p, C.c_void_p, _I4, _I4, C.c_int, C.c_int, _I4, _I4]
         L.jinc_debug_last_strided.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         L.jinc_debug_last_groups.argtypes = [C.POINTER(GroupInfo), C.c_int]
+        if hasattr(L, "jinc_debug_plane_extent_check"):   # (JINC_LIB may name an older build: A/B runs)
+            L.jinc_debug_plane_extent_check.argtypes = [C.c_void_p, _I4, _I4]
         L.jinc_filter_sync.argtypes = [C.c_void_p]
         L.jinc_filter_set_pipeline.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.jinc_filter_set_pipeline_group.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
@@ -1362,6 +1364,13 @@ class Filter:
         self._check(lib().jinc_filter_process_device_v210_packed10(
             self._h, C.c_void_p(src_ptr), int(src_pitch), C.c_size_t(int(src_stride or 0)), C.c_void_p(dst_ptr), int(dst_pitch), off,
             C.c_uint(dst_fill & 0xFFFFFFFF), C.c_size_t(int(dst_stride or 0)), int(nframes), C.c_void_p(stream)))
+
+    def plane_extent_check(self, src_pitches, dst_pitches) -> None:
+        """The limits every device call puts on its planes' extent (test header; works without a device): raises the refusal."""
+        sp, dp = _I4(), _I4()
+        for i in range(self.fmt.planes):
+            sp[i], dp[i] = src_pitches[i], dst_pitches[i]
+        self._check(lib().jinc_debug_plane_extent_check(self._h, sp, dp))
 
     last_strided = staticmethod(last_strided)
     last_groups = staticmethod(last_groups)

@@ -120,9 +120,25 @@ void validate_planes(const jinc_filter& f, const void* const src[4], const int s
         if (static_cast<size_t>(src_pitch[i]) < static_cast<size_t>(t.plan.src_w) * sb ||
             static_cast<size_t>(dst_pitch[i]) < static_cast<size_t>(t.plan.dst_w) * sb)
             throw ArgError("JincResize: plane pitch is smaller than the row size.");
-        if (static_cast<uint64_t>(dst_pitch[i]) * t.plan.dst_h >= (1ull << 32))
-            throw ArgError("JincResize: destination plane larger than 4 GiB is not supported (32-bit store offsets).");
+        if (const char* says = plane_size_refusal(src_pitch[i], t.plan.src_w, t.plan.src_h, dst_pitch[i], t.plan.dst_h, sb)) throw ArgError(says);
     }
+}
+
+// The two limits on a plane's extent (jinc_filter_process_device asks before it looks for a device, validate_planes for every call).
+// Destination: every kernel stores through a per-frame buffer resource with 32-bit offsets.  Source: ewa_strip_kernel and the 8-bit
+// frame-pair tile of ewa_periodic_quad2_kernel fetch through buffer resources whose length and row offsets are 32-bit, the direct
+// kernel likewise (direct_fetch_is_safe), and the frame-lane family forms the row offsets INSIDE a tile in 32 bits (fl_stage: tile
+// height x pitch must stay below 2^32; the tile's origin is 64-bit).  The other kernels -- the rest of the periodic family, row-pair,
+// column-pair, column-strip, quasi, gather, SIMD-order, the finite scans -- form size_t(row) * pitch and would read such a plane.
+// Which kernels a call reaches depends on its frame count, border form and knobs, so the limit is the plane's, not a kernel's: a
+// plane is not accepted at one batch size and refused at the next.  Frames may lie any distance apart: frame bases are 64-bit
+// everywhere.
+const char* plane_size_refusal(int src_pitch, int src_w, int src_h, int dst_pitch, int dst_h, int sample_bytes) {
+    if (static_cast<uint64_t>(dst_pitch) * dst_h >= (1ull << 32))
+        return "JincResize: destination plane larger than 4 GiB is not supported (32-bit store offsets).";
+    if (static_cast<uint64_t>(src_pitch) * (src_h > 0 ? src_h - 1 : 0) + static_cast<uint64_t>(src_w) * sample_bytes >= (1ull << 32))
+        return "JincResize: source plane larger than 4 GiB is not supported (32-bit fetch offsets).";
+    return nullptr;
 }
 
 namespace {

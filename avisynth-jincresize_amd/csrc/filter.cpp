@@ -806,6 +806,16 @@ int jinc_debug_last_strided(int* split_launches, int* merge_launches, int* slice
     return JINC_OK;
 }
 
+int jinc_debug_plane_extent_check(jinc_filter* f, const int src_pitch[4], const int dst_pitch[4]) {
+    if (!f || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    for (int i = 0; i < f->planecount; ++i) {
+        const jinc::TableGeometry& g = f->plans[static_cast<size_t>(f->table_of_plane(i))].g;
+        if (const char* says = plane_size_refusal(src_pitch[i], g.src_w, g.src_h, dst_pitch[i], g.dst_h, f->vi_in.component_size))
+            return fail(JINC_ERR_INVALID_ARG, says);
+    }
+    return JINC_OK;
+}
+
 int jinc_debug_last_groups(jinc_group_info* groups, int capacity) {
     const GroupsReport& r = last_groups_report();
     for (int i = 0; groups && i < r.count && i < capacity; ++i) {

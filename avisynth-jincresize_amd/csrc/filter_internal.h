@@ -329,6 +329,8 @@ void enqueue(jinc_filter& f, const void* const src[4], const int src_pitch[4], c
 const char* last_interior_kernel_in_process();
 void validate_planes(const jinc_filter& f, const void* const src[4], const int src_pitch[4], const size_t src_fs[4], void* const dst[4],
                      const int dst_pitch[4], const size_t dst_fs[4], int nframes);  // what enqueue checks before it queues anything; throws ArgError
+// ... and its limits on a plane's extent alone (no device needed): the message, or nullptr
+const char* plane_size_refusal(int src_pitch, int src_w, int src_h, int dst_pitch, int dst_h, int sample_bytes);
 // stand_ins.cpp: enqueue for device frames that do not lie as the filter's dense planes.  One side of such a call, as the caller gave
 // it and as filter.cpp has checked it against the filter (a destination's bases are written through):
 struct SideSpec {

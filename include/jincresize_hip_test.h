@@ -271,6 +271,10 @@ typedef struct jinc_group_info {
     int direction, n, members, sample_bytes, sample_type, scaled, unit, vec_pixels, width, rows, shifted;
 } jinc_group_info;
 JINC_API int jinc_debug_last_groups(jinc_group_info *groups, int capacity);
+/* What every device call checks of its planes' extent before it queues anything (validate_planes), for a filter without a device:
+ * JINC_OK, or the refusal of the first plane whose destination (pitch * height) or source (pitch * (height - 1) + row bytes) is
+ * 2^32 bytes or more, with its message in jinc_last_error. */
+JINC_API int jinc_debug_plane_extent_check(jinc_filter *f, const int src_pitch[4], const int dst_pitch[4]);
 /* Border frame of exactly periodic plans: -1 (default) = by call size (strip kernels from ~5e9 taps per call on, one gather
  * launch below); 1 = rows and columns on the round-4 strip kernels (ewa_direct_kernel's row strips, ewa_colstrip_kernel or, in batches,
  * the frame-lane kernel), corners on the gather kernel; 2 = rows on the strip kernel, columns and corners on the gather kernel;
