@@ -321,7 +321,7 @@ void trim_periodic(const jinc::PlanePlan& p, DeviceTable& t, bool integer_sample
             }
     }
     // per phase and kernel row: the zero coefficients in front of and behind the row's span (the disc's chord), the smaller of
-    // the two counts -- the rows kernel leaves that many taps out on either side (kernel_periodic.hip rows_kernel_row)
+    // the two counts -- the rows kernel leaves that many taps out on either side (kernel_periodic_rows.hip rows_kernel_row)
     std::vector<int32_t> row_trim(static_cast<size_t>(nphase) * 32, 0);
     if (n <= 32)
         for (int ph = 0; ph < nphase; ++ph)
@@ -856,7 +856,7 @@ void plan_edge_columns(const jinc::PlanePlan& p, DeviceTable& t, bool integer_sa
     if (r0 < 0 || r0 + nr > fs) return;
     const int x_end = pa.ix0 + 2 * pa.ni, W = p.g.dst_w;
     constexpr int kTileCols = 128, kMax = jinc::PeriodicArgs::EdgeColumns::kMaxPerSide;
-    const int kLdsCols = kTileCols + nr;  // Quad2Cfg / Quad2x8Cfg (kernel_periodic.hip)
+    const int kLdsCols = kTileCols + nr;  // Quad2Cfg / Quad2x8Cfg (kernel_periodic_quad2.inc / kernel_periodic_quad2x8.hip)
     const size_t block = static_cast<size_t>(nr) * ncp;
     jinc::PeriodicArgs::EdgeColumns e;
     std::vector<float> blob(static_cast<size_t>(2) * kMax * 2 * block, 0.f);

@@ -1,6 +1,6 @@
 // kernel_direct_impl.inc -- ewa_direct_kernel (included by kernel_direct.hip and the kernel_direct_walk_*.hip units):
 // exactly phase-periodic plans of ANY filter size and source step 1..4, without an LDS tile.  Two roles (MODE):
-//   kDirectInterior  the interior of plans the register/LDS kernels of kernel_periodic.hip do not cover: integer and
+//   kDirectInterior  the interior of plans the register/LDS kernels of kernel_periodic*.hip do not cover: integer and
 //                    rational down-scales (1/2: fs 13 step 2, 1/3: fs 20 step 3, 2/3: fs 10 step 3 period 2, ...)
 //                    and up-scales with taps 9..16 (fs 19..33);
 //   kDirectRowStrip  the top/bottom border rows of EVERY exactly periodic plan (interior column range): a border row

@@ -1,4 +1,4 @@
-// kernel_periodic_common.inc -- pieces shared by the kernels of the periodic family (kernel_periodic.hip, kernel_rowpair.hip);
+// kernel_periodic_common.inc -- pieces shared by the kernels of the periodic family (kernel_periodic*.hip, kernel_rowpair.hip);
 // included INSIDE namespace jinc { namespace { of the including translation unit.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -30,3 +30,32 @@ struct NonFinite {
         }
     }
 };
+
+constexpr int kTileCols = 64;  // source-aligned columns per tile = lanes of a wave
+
+// Tile of the window kernel (ewa_periodic_kernel) and of the one-period quad forms (kernel_periodic_quad.hip).
+// RG: row groups of FS rows per tile.  A/B on MI355X: fs 7 (C2) 8 groups = 4 groups (was +2.3 % before the staging loads
+// were issued together), 16 groups 10 % slower; fs 9 (C4, 88 VGPRs = 5 waves/SIMD) 9 groups +3.9 % over 6 -- 27 KB of
+// LDS per block still allows the 5 blocks per CU the registers allow.
+template <int FS, int RG = (FS <= 7 ? 8 : 9)>
+struct PeriodicCfg {
+    static constexpr int kRowGroups = RG;
+    static constexpr int kTileRows = FS * kRowGroups;     // period-rows per tile (multiple of FS)
+    static constexpr int kLdsCols = kTileCols + FS;       // 64 + (FS-1) halo + 1 phase spread
+    static constexpr int kLdsPitch = kLdsCols + 1;        // odd pitch not needed for row reads; keeps staging writes spread
+    static constexpr int kLdsRows = kTileRows + FS;       // TJ + (FS-1) halo + 1 phase spread
+};
+
+// The sample type of a launch: f(T{}) with T = uint8_t, uint16_t, half_t, bf16_t or float as io describes the planes.  Every
+// launcher of the family that crosses a unit boundary (kernel_periodic_launch.h) picks its instantiations through this.
+template <typename F>
+int for_sample_type(const PlaneIO& io, F&& f) {
+    switch (io.sample_bytes) {
+        case 1: return f(uint8_t{});
+        case 2:
+            if (io.sample_kind == kSampleHalf) return f(half_t{});
+            if (io.sample_kind == kSampleBFloat16) return f(bf16_t{});
+            return f(uint16_t{});
+        default: return f(float{});
+    }
+}

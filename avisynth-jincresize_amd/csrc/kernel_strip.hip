@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kStripLanes) void ewa_strip_kernel(const StripArgs 
                         staged[r][v] = __builtin_bit_cast(T4, __builtin_amdgcn_raw_buffer_load_b64(srsrc, off, 0, 0));
                     } else {
                         // (single dwords: the compiler merges two 8-byte loads into one of 16 bytes, which at a 4-byte boundary does not
-                        // return its dwords where they belong -- as the 16-byte stores of kernel_periodic.hip)
+                        // return its dwords where they belong -- as the 16-byte stores of kernel_periodic_quad_common.inc, store_quad_buf)
                         staged[r][v] = T4{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srsrc, off, 0, 0)),
                                           __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srsrc, off + 4u, 0, 0)),
                                           __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srsrc, off + 8u, 0, 0)),

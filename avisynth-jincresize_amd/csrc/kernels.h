@@ -106,7 +106,7 @@ constexpr int quad2_share_class(int mx, int my) {
 static_assert(quad2_share_class(4, 4) == kQuad2ShareClasses - 1 && quad2_share_class(5, 2) == 14 && quad2_share_class(3, 5) < 0 &&
                   quad2_share_m(0, 2) == 0 && quad2_share_m(1, 3) == 0 && quad2_share_m(0, 5) == 5 && quad2_share_m(1, 0) == 5,
               "class numbering");
-// The frame-pair form walks strips 2 periods across and H period rows down (kernel_periodic.hip quad2_share_body).  A set of the strip's
+// The frame-pair form walks strips 2 periods across and H period rows down (kernel_periodic_quad2.inc quad2_share_body).  A set of the strip's
 // outputs: bit 4 * oy + ox, oy = 2 * period row + q, ox = 2 * period column + p.
 struct Quad2ShareOuts {
     static constexpr int kMaxStripRows = 16;
@@ -160,7 +160,7 @@ struct PeriodicArgs {
     // the 6 x 7 support: zero coefficients in front of / behind the span of kernel row ly at row phase q for BOTH phases p, two bits each
     // (capped at 3) at 4 * (2 * ly + q) and 4 * (2 * ly + q) + 2
     uint64_t quad_span7 = 0;
-    // ... and the span FORM of every (ly, q) the kernel is instantiated for (kernel_periodic.hip quad2_row7_span: 0 = all seven taps, 1 =
+    // ... and the span FORM of every (ly, q) the kernel is instantiated for (kernel_periodic_quad2.inc quad2_row7_span: 0 = all seven taps, 1 =
     // taps 1 .. 6, 2 = taps 1 .. 5, 3 = taps 2 .. 5), two bits at 2 * (2 * ly + q): chroma planes sited as MPEG-2 at 2x with tap 3 --
     // q = 0: forms 3 1 0 0 0 2 for ly = 0 .. 5, q = 1: 2 0 0 0 1 3.  36 of 42 taps.
     static constexpr uint32_t kQuadSpan7Mpeg2 = span7_form(0, 0, 3) | span7_form(1, 0, 1) | span7_form(5, 0, 2) | span7_form(0, 1, 2) |
@@ -202,7 +202,7 @@ struct PeriodicArgs {
     const uint32_t* frame_flags = nullptr;
     uint32_t run_when = 0;
     // run_when == kRunAllAndFlag: the launch computes EVERY frame and sets frame_flags[frame] = 1 where it stages a non-finite
-    // sample (the trimmed launch of a float plane is its own finite-sample scan; kernel_periodic.hip NonFinite)
+    // sample (the trimmed launch of a float plane is its own finite-sample scan; kernel_periodic_common.inc NonFinite)
     static constexpr uint32_t kRunAllAndFlag = 2;
     // ewa_periodic_quad2_kernel / ewa_periodic_quad2x8_kernel on integer planes: the plane's border COLUMNS beside the interior rows, computed by the first / last
     // tile column out of the tile it has staged anyway (device_plan.cpp plan_edge_columns; as kernels of their own the columns were
@@ -229,7 +229,7 @@ inline constexpr uint32_t PeriodicArgs::kQuad8TrimTap4 = kQuad8TrimTap4Value;
 // Does the plan leave out at least what the span forms of `pattern` leave out?  (form -> taps left out in front / behind)
 // The 8-row x 9-column support (chroma planes sited as MPEG-2 at 2x with tap 4; ewa_periodic_quad2x8_kernel with nine taps per kernel
 // row): span FORM of every (ly, q), three bits at 3 * (2 * ly + q) -- 0 = all nine taps, 1 = taps 1 .. 8, 2 = 1 .. 7, 3 = 2 .. 7, 4 =
-// 2 .. 6 (kernel_periodic.hip quad2_row9_span).  Blur 1: q = 0 forms 4 2 1 0 0 0 2 3 for ly = 0 .. 7, q = 1: 3 2 0 0 0 1 2 4 -- 60 of 72.
+// 2 .. 6 (kernel_periodic_quad2x8.hip quad2_row9_span).  Blur 1: q = 0 forms 4 2 1 0 0 0 2 3 for ly = 0 .. 7, q = 1: 3 2 0 0 0 1 2 4 -- 60 of 72.
 constexpr uint64_t span9_form(int ly, int q, uint64_t form) { return form << (3 * (2 * ly + q)); }
 constexpr uint64_t kQuadSpan9Mpeg2 = span9_form(0, 0, 4) | span9_form(1, 0, 2) | span9_form(2, 0, 1) | span9_form(6, 0, 2) | span9_form(7, 0, 3) |
                                      span9_form(0, 1, 3) | span9_form(1, 1, 2) | span9_form(5, 1, 1) | span9_form(6, 1, 2) | span9_form(7, 1, 4);

@@ -1,5 +1,5 @@
 """The bf16 pair tile of the 8-bit full-tile frame-pair kernel (ewa_periodic_quad2_kernel<unsigned char, 8, 1026u, 6>,
-kernel_periodic.hip Quad2ShareTile<16, 1, 1, true>): the staged tile holds one 32-bit word per frame pair, each half a sample's bfloat16,
+kernel_periodic_quad2.inc Quad2ShareTile<16, 1, 1, true>): the staged tile holds one 32-bit word per frame pair, each half a sample's bfloat16,
 and a lane walks a strip of 16 period rows (tiles of 128 x 64 periods), reading each half with a d16_hi LDS load into a register whose low
 half stays zero.  16-bit planes keep the f32 pair tile and strips of 8.
 
@@ -136,7 +136,7 @@ def test_products_per_strip(pkg):
 
 
 def _kernel_ops(pkg, mangled_part):
-    path = [p for p in pkg.ISA_PATHS if p.endswith("kernel_periodic-gfx950.s")][0]
+    path = [p for p in pkg.ISA_PATHS if p.endswith("kernel_periodic_quad2_rg8-gfx950.s")][0]
     if not os.path.exists(path):
         pkg.build()
     lines = open(path).read().splitlines()

@@ -1,4 +1,4 @@
-"""The frame-pair form of the 2x tap-3 interior (ewa_periodic_quad2_kernel<integer, RG, 1026u, 6>, kernel_periodic.hip
+"""The frame-pair form of the 2x tap-3 interior (ewa_periodic_quad2_kernel<integer, RG, 1026u, 6>, kernel_periodic_quad2.inc
 quad2_share_body): one product per (source sample, symmetry class), added into every chain of the lane's 4 x 4 outputs that takes it.
 
 CPU: the compile-time class map (csrc/kernels.h quad2_share_class) against the oracle's own coefficient sets -- the classes are

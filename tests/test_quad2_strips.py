@@ -1,4 +1,4 @@
-"""The strip walk of the frame-pair 2x tap-3 interior (ewa_periodic_quad2_kernel<integer, RG, 1026u, 6>, kernel_periodic.hip
+"""The strip walk of the frame-pair 2x tap-3 interior (ewa_periodic_quad2_kernel<integer, RG, 1026u, 6>, kernel_periodic_quad2.inc
 quad2_share_body): a lane walks a strip of H period rows (8 on full tiles of 32 period rows, 2 on half tiles of 16) and stores each
 period row when its six source rows are done.  Bottom tiles end in partial strips, so the plane heights here leave every kind of last
 strip: interior period rows nj with nj mod 32 in {1, 5, 7, 8, 9, 31} and nj < 8.  Widths give edge tiles on both sides (the border

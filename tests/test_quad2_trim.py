@@ -1,4 +1,4 @@
-"""What the trimmed frame-pair 2x tap-3 interior (ewa_periodic_quad2_kernel<integer, RG, 1026u, 6>, kernel_periodic.hip quad2_share_body)
+"""What the trimmed frame-pair 2x tap-3 interior (ewa_periodic_quad2_kernel<integer, RG, 1026u, 6>, kernel_periodic_quad2.inc quad2_share_body)
 puts at risk, against the oracle's bytes, 8- and 16-bit planes, both tile heights through quad_rg:
   * a chain opens with its first product instead of 0 + product, so it may carry -0 where it carried +0: frames of nothing but zeros,
     and zero runs wider than the 6 x 6 support next to full-scale samples;
