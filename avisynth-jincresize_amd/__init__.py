@@ -28,7 +28,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JINC_LIB") or os.path.join(_HERE, "lib", "libjincresize_hip.so")  # JINC_LIB: A/B runs against another build
 SIMD_ORDER_ISA_PATH = os.path.join(_HERE, "lib", "kernel_simdorder-gfx950.s")  # the one unit with (explicit) fused multiply-adds
-ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_interleave", "kernel_widen", "kernel_narrow", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_periodic_quad", "kernel_periodic_quad2_rg8", "kernel_periodic_quad2_rg4", "kernel_periodic_quad2x8", "kernel_periodic_rows", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "bf16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
+ISA_PATHS = [os.path.join(_HERE, "lib", f"{k}-gfx950.s") for k in ("kernel_gather", "kernel_interleave", "kernel_widen", "kernel_narrow", "kernel_matrix", "kernel_framelane", "kernel_framelane_sub", "kernel_framelane_pair", "kernel_periodic", "kernel_periodic_quad", "kernel_periodic_quad2_rg8", "kernel_periodic_quad2_rg4", "kernel_periodic_quad2x8", "kernel_periodic_rows", "kernel_rowpair", "kernel_strip", "kernel_colpair", "kernel_direct", *[f"kernel_direct_walk_{t}_sx{x}" for t in ("u8", "u16", "f16", "bf16", "f32") for x in (1, 2, 3, 4)], "kernel_colstrip", "kernel_quasi_fs7", "kernel_quasi_fs9", "kernel_quasi_exact_fs7",
                        "kernel_quasi_exact_fs9", "kernel_quasi_lane_fs7", "kernel_quasi_lane_fs9")]
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip.h")
 TEST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "jincresize_hip_test.h")  # introspection, knobs, hooks
@@ -106,7 +106,8 @@ EXPORTS = ["jinc_device_count", "jinc_pick_device", "jinc_last_error", "jinc_fil
            "jinc_filter_process_device_widened_packed10_scaled", "jinc_filter_process_device_widened_v210_scaled",
            "jinc_debug_widen_fields", "jinc_debug_widen_v210",
            "jinc_filter_create_out", "jinc_batch_create_out",
-           "jinc_filter_process_device_shifted_packed10", "jinc_filter_process_device_v210_packed10", "jinc_debug_plane_extent_check"]
+           "jinc_filter_process_device_shifted_packed10", "jinc_filter_process_device_v210_packed10", "jinc_debug_plane_extent_check",
+           "jinc_filter_set_output_matrix", "jinc_colour_matrix", "jinc_debug_matrix_rows", "jinc_debug_last_matrix_launches"]
 
 _lib = None
 _P4 = C.c_void_p * 4
@@ -255,6 +256,11 @@ def lib():
             L.jinc_debug_quad2_share_products.restype = C.c_int
         L.jinc_debug_knob_name.argtypes = [C.c_int]
         L.jinc_debug_knob_name.restype = C.c_char_p
+        if hasattr(L, "jinc_filter_set_output_matrix"):   # (JINC_LIB may name an older build: A/B runs)
+            L.jinc_filter_set_output_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.jinc_colour_matrix.argtypes = [C.c_int, C.c_int, C.c_void_p]
+            L.jinc_debug_matrix_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+            L.jinc_debug_last_matrix_launches.argtypes = []
         _lib = L
     return _lib
 
@@ -703,6 +709,40 @@ def code_range(bits: int, range: int, plane_kind: int) -> Tuple[float, float, fl
     return tuple(np.float32(x.value) for x in v)
 
 
+MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020_NCL = 0, 1, 2   # jinc_colour_matrix: standard
+YCBCR_TO_RGB, RGB_TO_YCBCR = 0, 1                         # ... and direction
+
+
+def colour_matrix(standard: int, direction: int) -> np.ndarray:
+    """jinc_colour_matrix: the 3 x 3 float32 matrix between normalised Y' (0 .. 1), Cb / Cr (-0.5 .. 0.5) and R'G'B' (0 .. 1), rows
+    in R, G, B (to RGB) or Y', Cb, Cr (from RGB) order; needs no device."""
+    m = (C.c_float * 9)()
+    rc = lib().jinc_colour_matrix(int(standard), int(direction), m)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return np.array(list(m), dtype=np.float32).reshape(3, 3)
+
+
+def last_matrix_launches() -> int:
+    """jinc_debug_last_matrix_launches: the output matrix launches of this thread's most recent process_device* call."""
+    return int(lib().jinc_debug_last_matrix_launches())
+
+
+def debug_matrix_rows(rows, m, offset=None, bfloat16: bool = False, device: int = 0):
+    """The output matrix pass applied to three dense rows on the device (test hook): float32 or float16 values, or with bfloat16=True
+    uint16 bit patterns; returns the three rows after o = M r + offset in the rows' own type."""
+    rows, kind = _hook_planes(rows, bfloat16)
+    if len({r.size for r in rows}) != 1:
+        raise ValueError("three rows of one length are needed")
+    rows = [r.copy() for r in rows]
+    ptrs = (C.c_void_p * 3)(*[r.ctypes.data for r in rows])
+    mm = (C.c_float * 9)(*[float(v) for v in np.asarray(m, dtype=np.float32).reshape(9)])
+    rc = lib().jinc_debug_matrix_rows(ptrs, kind, rows[0].size, mm, _three_floats(offset), device)
+    if rc != 0:
+        raise JincError(rc, lib().jinc_last_error().decode())
+    return rows
+
+
 # Sample types of jinc_filter_create_ex / jinc_batch_create_ex
 SAMPLE_DEFAULT = 0
 SAMPLE_FLOAT16 = 1
@@ -992,6 +1032,12 @@ class Filter:
     def set_simd_order(self, order: int) -> None:
         """0: opt=0 results (default); 1 / 2 / 3: summation order of the reference's SSE4.1 / AVX2 / AVX-512 path."""
         self._check(lib().jinc_filter_set_simd_order(self._h, int(order)))
+
+    def set_output_matrix(self, m=None, offset=None) -> None:
+        """jinc_filter_set_output_matrix: every process_device* call hands its destination side o = M r + offset of the result planes
+        0 .. 2 (nine row-major values, three offsets or None for zeros; each product and sum rounded to float32).  m=None clears it."""
+        mm = None if m is None else (C.c_float * 9)(*[float(v) for v in np.asarray(m, dtype=np.float32).reshape(9)])
+        self._check(lib().jinc_filter_set_output_matrix(self._h, mm, _three_floats(offset)))
 
     # -- GetFrame on host planes (H2D, kernels, D2H) --
     def get_frame(self, src_planes: Sequence[np.ndarray]) -> List[np.ndarray]:

@@ -17,6 +17,10 @@ using namespace jinc::host;
 
 namespace {
 thread_local std::string g_last_error;
+// What jinc_filter_get_frame and jinc_filter_submit (and so a jinc_batch, which submits) tell a filter with an output matrix.
+const char* const kMatrixOnHostFrames =
+    "JincResize: this filter has an output matrix (jinc_filter_set_output_matrix), which only the jinc_filter_process_device* calls apply; "
+    "host frames are not supported with one.";
 }  // namespace
 
 namespace jinc {
@@ -226,6 +230,7 @@ int jinc_filter_set_chroma_location_mode(jinc_filter* f, int mode) {
 int jinc_filter_get_frame(jinc_filter* f, const void* const src[4], const int src_pitch[4], void* const dst[4],
                           const int dst_pitch[4]) {
     if (!f || !src || !dst || !src_pitch || !dst_pitch) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->has_matrix) return fail(JINC_ERR_UNSUPPORTED, kMatrixOnHostFrames);
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
     return guarded([&] {
         hip_check(hipSetDevice(f->device), "hipSetDevice");
@@ -253,6 +258,7 @@ int jinc_filter_pipeline_group(const jinc_filter* f) { return f ? f->group_frame
 int jinc_filter_submit(jinc_filter* f, const void* const src[4], const int src_pitch[4], void* const dst[4],
                        const int dst_pitch[4], long long* ticket) {
     if (!f || !src || !dst || !src_pitch || !dst_pitch || !ticket) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (f->has_matrix) return fail(JINC_ERR_UNSUPPORTED, kMatrixOnHostFrames);
     if (f->device < 0) return fail(JINC_ERR_NO_DEVICE, "JincResize: filter was created without a HIP device (device < 0).");
     return guarded([&] {
         hip_check(hipSetDevice(f->device), "hipSetDevice");
@@ -322,7 +328,9 @@ int jinc_filter_process_device(jinc_filter* f, const void* const src[4], const i
     return guarded([&] {
         hip_check(hipSetDevice(f->device), "hipSetDevice");
         hipStream_t s = static_cast<hipStream_t>(hip_stream);  // NULL = the HIP null stream, ordered with the caller's default-stream work
+        reset_matrix_launches();
         enqueue(*f, src, src_pitch, src_frame_stride, dst, dst_pitch, dst_frame_stride, nframes, s);
+        apply_output_matrix(*f, dst, dst_pitch, dst_frame_stride, nframes, s);  // (jinc_filter_set_output_matrix; nothing without one)
     });
 }
 
@@ -1356,6 +1364,89 @@ int jinc_filter_set_simd_order(jinc_filter* f, int order) {
         return fail(JINC_ERR_UNSUPPORTED, "JincResize: SIMD-order modes do not exist for bfloat16 clips (the reference has no bfloat16 path).");
     f->simd_order = order;
     return JINC_OK;
+}
+
+int jinc_filter_set_output_matrix(jinc_filter* f, const float m[9], const float offset[3]) {
+    if (!f) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (!m) {  // (clearing needs no check: what a filter without a matrix does is what it always did)
+        f->has_matrix = false;
+        g_last_error.clear();
+        return JINC_OK;
+    }
+    if (!f->float_samples())
+        return fail(JINC_ERR_UNSUPPORTED, "JincResize: an output matrix needs a float, half or bfloat16 filter (this one has integer samples of " +
+                                              std::to_string(f->vi_in.bits_per_component) + " bits).");
+    if (f->planecount < 3)
+        return fail(JINC_ERR_UNSUPPORTED, "JincResize: an output matrix needs three planes (this filter has " + std::to_string(f->planecount) + ").");
+    int w[3], h[3];
+    for (int i = 0; i < 3; ++i) f->plane_dims(f->vi_out, i, w[i], h[i]);
+    if (w[1] != w[0] || w[2] != w[0] || h[1] != h[0] || h[2] != h[0])
+        return fail(JINC_ERR_UNSUPPORTED, "JincResize: an output matrix needs output planes 0..2 of one size (4:4:4; jinc_filter_create_out(..., 0, 0) "
+                                          "gives that from 4:2:0 and 4:2:2 input); this filter's output has sub_w " + std::to_string(f->vi_out.sub_w) + " and sub_h " +
+                                              std::to_string(f->vi_out.sub_h) + ".");
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(m[k])) return fail(JINC_ERR_INVALID_ARG, "JincResize: entry " + std::to_string(k) + " of the output matrix is not finite.");
+    for (int k = 0; offset && k < 3; ++k)
+        if (!std::isfinite(offset[k])) return fail(JINC_ERR_INVALID_ARG, "JincResize: entry " + std::to_string(k) + " of the output matrix's offset is not finite.");
+    for (int k = 0; k < 9; ++k) f->matrix[k] = m[k];
+    for (int k = 0; k < 3; ++k) f->matrix_offset[k] = offset ? offset[k] : 0.f;
+    f->has_matrix = true;
+    g_last_error.clear();
+    return JINC_OK;
+}
+
+int jinc_colour_matrix(int standard, int direction, float m[9]) {
+    if (!m) return fail(JINC_ERR_INVALID_ARG, "JincResize: null argument.");
+    if (standard != JINC_MATRIX_BT601 && standard != JINC_MATRIX_BT709 && standard != JINC_MATRIX_BT2020_NCL)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: the standard of a colour matrix must be JINC_MATRIX_BT601, JINC_MATRIX_BT709 or JINC_MATRIX_BT2020_NCL.");
+    if (direction != JINC_YCBCR_TO_RGB && direction != JINC_RGB_TO_YCBCR)
+        return fail(JINC_ERR_INVALID_ARG, "JincResize: the direction of a colour matrix must be JINC_YCBCR_TO_RGB or JINC_RGB_TO_YCBCR.");
+    const double kr = standard == JINC_MATRIX_BT601 ? 0.299 : standard == JINC_MATRIX_BT709 ? 0.2126 : 0.2627;
+    const double kb = standard == JINC_MATRIX_BT601 ? 0.114 : standard == JINC_MATRIX_BT709 ? 0.0722 : 0.0593;
+    const double kg = 1.0 - kr - kb;
+    // (every entry in double, in the order the header writes it, rounded once)
+    const double to_rgb[9] = {1.0, 0.0, 2.0 * (1.0 - kr),
+                              1.0, -2.0 * kb * (1.0 - kb) / kg, -2.0 * kr * (1.0 - kr) / kg,
+                              1.0, 2.0 * (1.0 - kb), 0.0};
+    const double to_ycbcr[9] = {kr, kg, kb,
+                                -kr / (2.0 * (1.0 - kb)), -kg / (2.0 * (1.0 - kb)), 0.5,
+                                0.5, -kg / (2.0 * (1.0 - kr)), -kb / (2.0 * (1.0 - kr))};
+    for (int k = 0; k < 9; ++k) m[k] = static_cast<float>(direction == JINC_YCBCR_TO_RGB ? to_rgb[k] : to_ycbcr[k]);
+    return JINC_OK;
+}
+
+int jinc_debug_last_matrix_launches(void) { return last_matrix_launches(); }
+
+int jinc_debug_matrix_rows(void* const rows[3], int in_kind, int n, const float m[9], const float offset[3], int device) {
+    const bool kind_ok = in_kind == JINC_SAMPLE_DEFAULT || in_kind == JINC_SAMPLE_FLOAT16 || in_kind == JINC_SAMPLE_BFLOAT16;
+    if (!rows || !rows[0] || !rows[1] || !rows[2] || !m || n < 0 || !kind_ok) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(m[k])) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    for (int k = 0; offset && k < 3; ++k)
+        if (!std::isfinite(offset[k])) return fail(JINC_ERR_INVALID_ARG, "JincResize: bad argument.");
+    if (n == 0) return JINC_OK;
+    const size_t bytes = (in_kind == JINC_SAMPLE_DEFAULT ? 4 : 2) * static_cast<size_t>(n);
+    return guarded([&] {
+        hip_check(hipSetDevice(device), "hipSetDevice");
+        char* d[3] = {nullptr, nullptr, nullptr};
+        jinc::MatrixArgs a;  // three dense rows: whole lanes by 16-byte accesses, the rest sample by sample
+        for (int c = 0; c < 3; ++c) {
+            hip_check(hipMalloc(&d[c], bytes + 16), "hipMalloc");
+            bounce_upload(d[c], rows[c], bytes, "upload of the values");
+            a.plane[c] = d[c], a.pitch[c] = static_cast<uint32_t>(align_up(bytes, 16));  // (one row: the pitch only has to suit the unit)
+        }
+        const uint32_t lane_pixels = in_kind == JINC_SAMPLE_DEFAULT ? 4u : 8u;
+        a.width = static_cast<uint32_t>(n), a.rows = 1, a.unit = 16, a.vec_pixels = a.width / lane_pixels * lane_pixels;
+        for (int k = 0; k < 9; ++k) a.m[k] = m[k];
+        for (int k = 0; k < 3; ++k) a.offset[k] = offset ? offset[k] : 0.f;
+        const int kind = in_kind == JINC_SAMPLE_FLOAT16 ? jinc::kSampleHalf : in_kind == JINC_SAMPLE_BFLOAT16 ? jinc::kSampleBFloat16 : 0;
+        hip_check(static_cast<hipError_t>(jinc::launch_output_matrix(a, kind, 1, nullptr)), "output matrix launch");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        for (int c = 0; c < 3; ++c) {
+            bounce_download(rows[c], d[c], bytes, "download of the samples");
+            (void)hipFree(d[c]);
+        }
+    });
 }
 
 int jinc_debug_buffer_range_check(int device) {

@@ -232,6 +232,10 @@ struct jinc_filter {
     bool direct_premise = false;  // buffer_range_check_covers_soffset(device) == 1
     int simd_order = 0;  // 0: opt=0 results (default); 1 / 2 / 3: summation order of the reference's SSE4.1 / AVX2 / AVX-512 path
     int overlap_border = -1;  // -1: automatic (side stream unless the call is tiny: dispatch.cpp), 0: off, 1: on
+    // jinc_filter_set_output_matrix: o = M r + offset on planes 0 .. 2 of every device call's results, between the resampling kernels
+    // and the call's destination pass (stand_ins.cpp apply_output_matrix); the host-frame entries refuse a filter that has one.
+    bool has_matrix = false;
+    float matrix[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, matrix_offset[3] = {0.f, 0.f, 0.f};
 
     int device = -1;  // -1: host-only instance (plan inspection); frame calls fail
     hipStream_t stream = nullptr;
@@ -380,6 +384,14 @@ struct GroupsReport {
     GroupRecord g[kCapacity];
 };
 const GroupsReport& last_groups_report();
+// The output matrix of `f` (jinc_filter_set_output_matrix) on `nframes` frames of planes 0 .. 2 of dense result planes, in place, on
+// `stream` behind whatever has been queued there: one launch of kernel_matrix.hip, counted for jinc_debug_last_matrix_launches.
+// Nothing at all with no matrix set.  reset_matrix_launches: what a device call starts with (where t_last_strided is reset, and in
+// jinc_filter_process_device, which has no report of that kind).
+void apply_output_matrix(const jinc_filter& f, void* const planes[4], const int pitch[4], const size_t frame_stride[4], int nframes,
+                         hipStream_t stream);
+void reset_matrix_launches();
+int last_matrix_launches();  // of the calling thread's most recent device call
 int last_call_frames_in_process();
 const char* last_interior_instance_in_process();
 // pipeline.cpp: frames in flight on one instance

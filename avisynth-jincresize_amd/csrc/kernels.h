@@ -698,6 +698,27 @@ struct NarrowV210Args : V210Args {
 int launch_narrow_fields(const NarrowFieldArgs& a, int in_kind, int nframes, void* stream, bool scaled = false);
 int launch_narrow_v210(const NarrowV210Args& a, int in_kind, int nframes, void* stream, bool scaled = false);
 
+// The 3x3 output matrix of a float filter (kernel_matrix.hip, matrix_rows.h; jinc_filter_set_output_matrix): planes 0 .. 2 of an
+// fp32 / binary16 / bfloat16 filter's results, three planes of ONE size, updated in place.  Sample x of row y of frame n of plane c
+// lies at plane[c] + n * frame_stride[c] + y * pitch[c] + x * sample bytes (4: fp32; 2: binary16 or bfloat16); with r0, r1, r2 the
+// three samples of a pixel widened exactly to fp32, plane i gets
+//   fl32(fl32(fl32(fl32(m[3i] * r0) + fl32(m[3i+1] * r1)) + fl32(m[3i+2] * r2)) + offset[i])
+// -- three multiplies and three adds, each rounded to fp32, in this order, never an FMA -- rounded to nearest even into the sample
+// type by the conversions the kernels' own stores use.  The planes are the result stand-ins (256-byte aligned) or the caller's own
+// destination planes: unit is 16 where every base, pitch and frame stride is a multiple of 16 bytes, 4 where of 4 only, else 0;
+// vec_pixels: the leading pixels of every row moved by 16-byte (unit 16) or dword (unit 4) accesses, a multiple of the 16 / sample
+// bytes pixels a lane owns, 0 with unit 0.  Nothing beyond `width` samples of a row is read or written.
+struct MatrixArgs {
+    char* plane[3] = {nullptr, nullptr, nullptr};
+    size_t frame_stride[3] = {0, 0, 0};
+    uint32_t pitch[3] = {0, 0, 0};
+    uint32_t width = 0, rows = 0, vec_pixels = 0, unit = 0;
+    float m[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, offset[3] = {0.f, 0.f, 0.f};
+};
+// One launch over every row and frame of `a`: kind 0 (fp32), kSampleHalf or kSampleBFloat16; anything else, a null plane or a
+// unit / vec_pixels pair that is none of the above is hipErrorInvalidValue, never a silent skip.
+int launch_output_matrix(const MatrixArgs& a, int kind, int nframes, void* stream);
+
 // Measurement hook (kernel_probe.hip): `samplers` single-lane workgroups stamp the shader clock counter and the 100 MHz
 // real-time counter until *stop_flag (device memory) becomes non-zero or max_seconds pass; out[2 k] = shader ticks,
 // out[2 k + 1] = real-time ticks of sampler k.

@@ -39,6 +39,7 @@ namespace host {
 namespace {
 thread_local StridedReport t_last_strided;
 thread_local GroupsReport t_last_groups;  // cleared wherever t_last_strided is: what a call that runs no pass leaves
+thread_local int t_matrix_launches = 0;   // likewise: the output matrix launches of the call (jinc_debug_last_matrix_launches)
 
 // GroupRecord::direction
 enum : int { kWiden = 0, kNarrow = 1, kSplit = 2, kMerge = 3, kUnpackFields = 4, kPackFields = 5, kWidenFields = 6, kUnpackV210 = 7, kPackV210 = 8, kWidenV210 = 9, kNarrowFields = 10, kNarrowV210 = 11 };
@@ -445,6 +446,7 @@ void run_on_stand_ins(jinc_filter& f, const SideSpec& src, const SideSpec& dst, 
         // kernel: the merge queued below follows both streams' kernels.
         report.split_launches += pass_side(f, src, in, false, scratch, k0, slice, n, nframes, stream);
         enqueue(f, s_now, sp_run, sfs_run, d_now, dp_run, dfs_run, n, stream);
+        apply_output_matrix(f, d_now, dp_run, dfs_run, n, stream);  // (nothing without a matrix; behind ev_join, in front of the merge)
         report.merge_launches += pass_side(f, dst, out, true, scratch, k0, slice, n, nframes, stream);
         ++report.slices;
     }
@@ -467,9 +469,37 @@ int strided_groups(const void* const base[4], const int pitch[4], const int* ste
 const StridedReport& last_strided_report() { return t_last_strided; }
 const GroupsReport& last_groups_report() { return t_last_groups; }
 
+// The pass of jinc_filter_set_output_matrix over planes 0 .. 2 as the resampling kernels have left them (the setter has seen to it
+// that they have one size): in place, one launch, on the caller's stream -- enqueue has joined its side stream back by now.
+void apply_output_matrix(const jinc_filter& f, void* const planes[4], const int pitch[4], const size_t frame_stride[4], int nframes,
+                         hipStream_t stream) {
+    if (!f.has_matrix) return;
+    jinc::MatrixArgs a;
+    int w = 0, h = 0;
+    f.plane_dims(f.vi_out, 0, w, h);
+    uintptr_t al = 0;
+    for (int c = 0; c < 3; ++c) {
+        a.plane[c] = static_cast<char*>(planes[c]);
+        a.pitch[c] = static_cast<uint32_t>(pitch[c]);
+        a.frame_stride[c] = (nframes > 1 && frame_stride) ? frame_stride[c] : 0;
+        al |= reinterpret_cast<uintptr_t>(planes[c]) | static_cast<uintptr_t>(pitch[c]) | static_cast<uintptr_t>(a.frame_stride[c]);
+    }
+    a.width = static_cast<uint32_t>(w), a.rows = static_cast<uint32_t>(h);
+    a.unit = al % 16 == 0 ? 16u : al % 4 == 0 ? 4u : 0u;  // (as fill_groups has it, over all three planes)
+    const uint32_t lane_pixels = 16u / static_cast<uint32_t>(f.vi_in.component_size);
+    a.vec_pixels = a.unit ? a.width / lane_pixels * lane_pixels : 0u;
+    for (int k = 0; k < 9; ++k) a.m[k] = f.matrix[k];
+    for (int k = 0; k < 3; ++k) a.offset[k] = f.matrix_offset[k];
+    launched(jinc::launch_output_matrix(a, f.sample_kind(), nframes, stream), "output matrix launch");
+    ++t_matrix_launches;
+}
+void reset_matrix_launches() { t_matrix_launches = 0; }
+int last_matrix_launches() { return t_matrix_launches; }
+
 void enqueue_sides(jinc_filter& f, const SideSpec& src, const SideSpec& dst, int nframes, hipStream_t stream) {
     t_last_strided = {0, 0, 0, static_cast<long long>(f.strided_scratch_bytes)};  // (also what a refused call leaves: it launched nothing)
     t_last_groups.count = 0;
+    t_matrix_launches = 0;
     // The source side is planned and checked first, then the destination side.  (Before the two sides were described apart, the
     // widened calls for words and blocks checked their destination planes first: their source checks repeat what filter.cpp has
     // refused with texts of its own, all but the odd width of a v210 source, which a call with a faulty destination as well now
@@ -479,6 +509,7 @@ void enqueue_sides(jinc_filter& f, const SideSpec& src, const SideSpec& dst, int
     plan_side(f, dst, true, nframes, out);
     if (in.ngroups == 0 && out.ngroups == 0) {  // dense planes on both sides (Planes, not converting): the call IS jinc_filter_process_device
         enqueue(f, src.base, src.pitch, src.frame_stride, const_cast<void* const*>(dst.base), dst.pitch, dst.frame_stride, nframes, stream);
+        apply_output_matrix(f, const_cast<void* const*>(dst.base), dst.pitch, dst.frame_stride, nframes, stream);
         return;
     }
     run_on_stand_ins(f, src, dst, in, out, nframes, stream);

@@ -790,6 +790,48 @@ JINC_API int jinc_alias_args(int taps, const jinc_args *alias_in, jinc_args *out
  * A private switch: the public `opt` argument does not select it.  Slow path (no LDS staging). */
 JINC_API int jinc_filter_set_simd_order(jinc_filter *f, int order);
 
+/* ---- A 3x3 colour matrix on a float filter's result planes ----
+ * Decoders give Y'CbCr, networks and displays take R'G'B': with a matrix set, every jinc_filter_process_device* call -- the planar
+ * call, _strided, _shifted, _packed10, _v210, _shifted_packed10, _v210_packed10 and every _widened* and _narrowed* call -- hands
+ * its destination side o = M r + offset where it handed r.  For each output pixel with planar results r0, r1, r2 (what the call
+ * would have left in planes 0 .. 2, widened exactly to fp32)
+ *     o_i = fl32( fl32( fl32( fl32(m[3i] * r0) + fl32(m[3i+1] * r1) ) + fl32(m[3i+2] * r2) ) + offset[i] )      i = 0, 1, 2
+ * -- three multiplies and three adds, each rounded to fp32, in this order, never a fused multiply-add.  `m` is row-major.  An fp32
+ * filter stores o_i; a binary16 or bfloat16 filter rounds once more here: o_i goes to nearest even into the filter's sample type (the
+ * conversion its kernels store results with) -- on top of the rounding the resampling kernels ended in -- and a destination pass
+ * that narrows (the _narrowed* calls) reads that rounded sample.  Non-finite inputs follow IEEE arithmetic; NaN payloads are not
+ * specified.
+ *   Output i goes to plane i: the caller orders the rows of `m` to suit its plane order (and its columns to suit the planes the
+ * filter resamples).  jinc_colour_matrix gives rows in R, G, B order, which is the order of a packed RGB destination whose channels
+ * the call's pointers and steps place; AviSynth's planar RGB is G, B, R, so a caller that writes RGBPS planes passes rows 1, 2, 0 of
+ * it.  A fourth plane (alpha) is not touched.  Everything behind the matrix is unchanged: a destination pass (merge, narrow with its
+ * scale / offset, pack into words or blocks) sees o where it saw r.  It is a pass of its own -- one kernel launch per slice of a
+ * call, in place on the dense result planes -- and the resampling kernels, jinc_filter_set_simd_order and the kernel modes are
+ * independent of it: the matrix reads whatever the chosen kernel wrote.
+ *   m == NULL clears the matrix (offset is not read); offset == NULL means zeros.  Needs no device.  Refused where the filter
+ * decides it: an integer filter, a filter with fewer than three planes and a filter whose output planes 0 .. 2 are not of one size
+ * (the output must be 4:4:4: RGB, YUV444, or a 4:2:0 / 4:2:2 input through jinc_filter_create_out(..., 0, 0)) are JINC_ERR_UNSUPPORTED; a
+ * NaN or an infinity in m or offset is JINC_ERR_INVALID_ARG.
+ *   With a matrix set the host-frame entries -- jinc_filter_get_frame, jinc_filter_submit, and so a jinc_batch built on them --
+ * return JINC_ERR_UNSUPPORTED and launch nothing: the matrix belongs to the device calls. */
+JINC_API int jinc_filter_set_output_matrix(jinc_filter *f, const float m[9], const float offset[3]);
+
+/* The usual matrices between normalised Y' in 0 .. 1, Cb / Cr in -0.5 .. 0.5 (exactly what jinc_code_range produces) and R'G'B' in
+ * 0 .. 1, row-major in m.  Needs no device.  With Kr / Kb = 0.299 / 0.114 (JINC_MATRIX_BT601), 0.2126 / 0.0722 (JINC_MATRIX_BT709),
+ * 0.2627 / 0.0593 (JINC_MATRIX_BT2020_NCL) and Kg = 1.0 - Kr - Kb:
+ *   JINC_YCBCR_TO_RGB (rows R, G, B; columns Y', Cb, Cr)        JINC_RGB_TO_YCBCR (rows Y', Cb, Cr; columns R, G, B)
+ *       1    0                          2.0 * (1.0 - Kr)             Kr                         Kg                         Kb
+ *       1    -2.0 * Kb * (1.0 - Kb) / Kg   -2.0 * Kr * (1.0 - Kr) / Kg    -Kr / (2.0 * (1.0 - Kb))   -Kg / (2.0 * (1.0 - Kb))   0.5
+ *       1    2.0 * (1.0 - Kb)           0                            0.5                        -Kg / (2.0 * (1.0 - Kr))   -Kb / (2.0 * (1.0 - Kr))
+ * Every entry is computed in double, in the order written, and rounded to float once.  Any other standard or direction, or a NULL m,
+ * is JINC_ERR_INVALID_ARG. */
+#define JINC_MATRIX_BT601 0
+#define JINC_MATRIX_BT709 1
+#define JINC_MATRIX_BT2020_NCL 2
+#define JINC_YCBCR_TO_RGB 0
+#define JINC_RGB_TO_YCBCR 1
+JINC_API int jinc_colour_matrix(int standard, int direction, float m[9]);
+
 /* Plan introspection, kernel-selection knobs for A/B measurements, test hooks and kernel timing live in
  * jincresize_hip_test.h: they are exported by the same library but are not part of the drop-in boundary. */
 

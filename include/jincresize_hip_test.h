@@ -311,6 +311,15 @@ JINC_API int jinc_debug_narrow(const void *in, int in_kind, void *out, int n, in
  * lrintf(clamp(fl32(fl32(value * scale) + offset), 0, (1 << dst_bits) - 1)) << shift.  scale and offset finite, scale not zero. */
 JINC_API int jinc_debug_narrow_scaled(const void *in, int in_kind, void *out, int n, int dst_bits, int shift, float scale, float offset,
                                       int device);
+/* ... the output matrix pass of jinc_filter_set_output_matrix itself: output_matrix_kernel on THREE dense rows of `n` caller-given
+ * values of in_kind each (JINC_SAMPLE_DEFAULT: fp32; JINC_SAMPLE_FLOAT16 / JINC_SAMPLE_BFLOAT16: 16-bit patterns), updated in place
+ * on the device: rows[i] is read and receives o_i of include/jincresize_hip.h for m (nine values, row-major) and offset (three; NULL:
+ * zeros): whole lanes through the 16-byte accesses, the rest sample by sample. */
+JINC_API int jinc_debug_matrix_rows(void *const rows[3], int in_kind, int n, const float m[9], const float offset[3], int device);
+/* The output matrix launches of the calling thread's most recent jinc_filter_process_device* call: one per slice of a call on a
+ * filter with a matrix set (1 for a call on dense planes), 0 when none ran.  Reset where the counts of jinc_debug_last_strided are,
+ * and by jinc_filter_process_device itself. */
+JINC_API int jinc_debug_last_matrix_launches(void);
 /* ... the narrowing passes of jinc_filter_process_device_narrowed_packed10 / _narrowed_v210 themselves: narrow_fields_kernel on ONE
  * dense row of `n` caller-given values per plane (in[0 .. 2], of in_kind as above), out_words receives n words
  * (v0 << field_offset[0]) | (v1 << field_offset[1]) | (v2 << field_offset[2]) | (fill & ~fields) with
